@@ -1,6 +1,6 @@
 """bench.py -- meshes/sec of the ico2ico training step (BASELINE.json metric) on N MI355X of one node.
 
-  python bench.py --gpus 1 --steps 50 --warmup 5
+  python bench.py --gpus 1 --steps 50 --warmup 5 [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
   python bench.py --gpus N ...        (no WORLD_SIZE in the environment: starts the N ranks itself, see launch_ranks)
@@ -8,7 +8,9 @@
 A step = one pass of the hot path over one batch: forward -> P2P loss -> zero_grad -> backward -> Adam -> CyclicLR
 (reference run.py:244-254) on 36 synthetic I5 meshes per GPU already resident in HBM.  Weak scaling: per-GPU
 batch fixed; gradients averaged by bucketed RCCL all-reduce overlapped with backward.
-Rank 0 prints ONE JSON line, with
+Rank 0 prints ONE JSON line.  A plain run sets up, runs W warm-up steps, times EXACTLY K steps and prints the headline
+(value, ms_per_step, ...; roofline = null).  --dump-outputs DIR writes what the last timed step left to its caller (see
+dump_outputs).  --full adds, in the same process:
   roofline     : the dominant MFMA kernel, timed live with HIP events on its launch stream (achieved = algorithmic FLOPs per
                  launch / mean launch duration), vs 157.3 TFLOP/s dense fp32 MFMA.  The training step runs its weight
                  gradients on a second stream beside the other launches; a launch that shares the chip has no
@@ -213,7 +215,7 @@ def _measure(cfg, args, ctx, headline):
     # HIP events around EVERY MFMA launch cost the step ~2.5 % (a marker packet between back-to-back kernels).  So: all
     # kernels are timed during the last warm-up steps (table of kernels, executed FLOPs per step, which kernel dominates),
     # and in the timed region only the dominant kernel carries events -- that is the `roofline` measurement.
-    events = not args.no_kernel_events
+    events = args.full and not args.no_kernel_events
     # (four survey steps -- 52 launches of the dominant kernel -- after the W warm-up steps the caller asked for and before the
     #  timed region, untimed like them: surveyed earlier, among the first steps of the process, the same launches take 3 - 4 %
     #  longer; and a roofline block must not depend on the caller asking for warm-up)
@@ -248,6 +250,8 @@ def _measure(cfg, args, ctx, headline):
     barrier()
     elapsed = time.perf_counter() - t0
     prof = _lib.profile_stop() if dominant and not overlapped else []
+    if headline and args.dump_outputs and rank == 0:
+        dump_outputs(tr, loss, args.dump_outputs)
     if dominant and overlapped and headline:
         _lib.profile_start(200, only=dominant)
         for _ in range(2):
@@ -367,6 +371,31 @@ def _measure(cfg, args, ctx, headline):
     return {'value': round(value, 2), 'ms_per_step': round(elapsed / args.steps * 1e3, 3), 'final_loss': final_loss,
             'roofline': roofline, 'ddp': ddp, 'replicas_identical': replicas_identical,
             'rank_ms_per_step': {'min': round(min(per_rank) / args.steps * 1e3, 3), 'max': round(max(per_rank) / args.steps * 1e3, 3)}}
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(tr, loss, out_dir):
+    """What the last timed step hands its caller, as float32 DIR/<name>.npy: `loss` (the value Trainer.step returns) and the
+    model that step trained -- `param.<key>` every parameter after the Adam update, `grad.<key>` its gradient of that step,
+    `buffer.<key>` the BatchNorm running statistics.  Whole tensors (37 MB for ico2ico, 48 MB for ico2ico_vae); inputs and
+    initial weights are seeded, so two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    arrays = {'loss': loss}
+    for key, q in tr.model.named_parameters():
+        arrays['param.' + key] = q
+        if q.grad is not None:
+            arrays['grad.' + key] = q.grad
+    for key, b in tr.model.named_buffers():
+        if b.is_floating_point():
+            arrays['buffer.' + key] = b
+    total = sum(4 * t.numel() for t in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        raise SystemExit('bench.py: --dump-outputs would write %d bytes (cap %d)' % (total, DUMP_CAP_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.detach().float().contiguous().cpu().numpy())
 
 
 def is_split_kernel(name):
@@ -506,7 +535,7 @@ def run(args):
                                                                                   else 'none')},
         }
     # BASELINE configs 4 and 5 behind the headline, same process, same --steps / --warmup (N = 1; the scaling runs stay short)
-    if world == 1 and not forced and args.config == 'ae' and not args.no_also:
+    if args.full and world == 1 and not forced and args.config == 'ae' and not args.no_also:
         try:
             also = []
             if arith != 'f32':
@@ -546,7 +575,7 @@ def run(args):
             out['also'] = None
             out['also_error'] = '%s: %s' % (type(e).__name__, e)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(cfg)
         print(json.dumps(out), flush=True)
     if group:
@@ -560,14 +589,22 @@ def main():
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--config', choices=sorted(CONFIGS), default='ae')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-events', action='store_true', help='skip the per-launch HIP events (roofline = null)')
-    ap.add_argument('--no-also', action='store_true', help='skip the vae / i6 configurations behind the headline (N = 1)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the roofline (survey steps with HIP events), the other configurations (also[]) and the '
+                         'CPU baseline; off: the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the loss and the trained parameters, gradients and BatchNorm statistics '
+                         'of the last timed step as float32 DIR/<name>.npy (rank 0)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-kernel-events', action='store_true', help='with --full: skip the per-launch HIP events (roofline = null)')
+    ap.add_argument('--no-also', action='store_true', help='with --full: skip the vae / i6 configurations behind the headline (N = 1)')
     ap.add_argument('--arith', choices=['f32', 'bf16x3'], default=None,
                     help="arithmetic of the channel-mixing contraction (default: the library's, i.e. ICN_ARITH or bf16x3)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit('bench.py: --gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('bench.py: --steps must be >= 1 and --warmup >= 0')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))
     run(args)

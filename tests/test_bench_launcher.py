@@ -129,3 +129,36 @@ def test_sigterm_to_the_launcher_stops_its_ranks(tmp_path):
             time.sleep(0.1)
         else:
             raise AssertionError('rank process %d survived the launcher' % pid)
+
+
+def test_steps_below_one_are_refused():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], cwd=ROOT, env=_env(), capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode != 0 and '--steps must be >= 1' in r.stderr
+
+
+def test_dump_outputs_writes_what_the_last_step_left(tmp_path):
+    """bench.dump_outputs on a CPU trainer (the oracle's model stands in for the HIP one): one float32 .npy per array -- the loss,
+    every parameter after the update, its gradient, the BatchNorm statistics -- equal to the trainer's, under the size cap."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from geniconet_amd import data, models
+    from geniconet_amd.train import Trainer, build_criterion
+    from oracle import models_ref
+    p = models.default_params('ico2ico', subdivisions=5)
+    torch.manual_seed(0)
+    tr = Trainer(p, 'cpu', model=models_ref.ico2ico(R=5).train(), criterion=build_criterion(p, 'cpu'), channels_last=False)
+    x, t = data.synthetic_batch(1, 5, seed=1234)
+    loss = tr.step(x, t)
+    bench.dump_outputs(tr, loss, str(tmp_path))
+    names = sorted(f[:-4] for f in os.listdir(tmp_path))
+    keys = [k for k, _ in tr.model.named_parameters()]
+    stats = [k for k, b in tr.model.named_buffers() if b.is_floating_point()]
+    assert names == sorted(['loss'] + ['param.' + k for k in keys] + ['grad.' + k for k in keys] + ['buffer.' + k for k in stats])
+    assert sum(os.path.getsize(tmp_path / (n + '.npy')) for n in names) <= bench.DUMP_CAP_BYTES
+    assert np.load(tmp_path / 'loss.npy') == np.float32(float(loss))
+    for k, q in tr.model.named_parameters():
+        a, g = np.load(tmp_path / ('param.%s.npy' % k)), np.load(tmp_path / ('grad.%s.npy' % k))
+        assert a.dtype == np.float32 and np.array_equal(a, q.detach().numpy()) and np.array_equal(g, q.grad.numpy())

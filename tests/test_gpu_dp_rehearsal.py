@@ -99,7 +99,7 @@ def test_bench_launch_forms_rehearsal(launcher):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(ICN_BENCH_REHEARSAL='1', PYTHONFAULTHANDLER='1')
-    bench = [os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1']
+    bench = [os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full']
     if launcher == 'self':
         cmd = [sys.executable] + bench
     else:

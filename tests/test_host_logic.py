@@ -1,8 +1,6 @@
 """Host-side logic of the product (no GPU): module tree, state_dict keys, parameter counts, argument checks,
 loud failure on CPU tensors, loss + data format against the numpy oracle, reference drop-in import."""
-import importlib
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -12,8 +10,6 @@ from conftest import rel_l2
 from geniconet_amd import data, geometry, losses, models
 from geniconet_amd.ico_conv import IcoConvS2S, IcoUpsampleS2S
 from oracle import loss_ref, models_ref
-
-REFERENCE = '/root/reference'
 
 
 def test_parameter_counts_and_keys():
@@ -38,23 +34,16 @@ def test_parameter_counts_and_keys():
     assert sum(p.numel() for p in ae6.parameters()) == 4627715
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason='reference checkout only exists in the build container')
-def test_reference_models_py_drops_in_unchanged():
-    """The reference's own models.py imports `icocnn` (models.py:4-6); with this repo's icocnn package on the
-    path it builds both networks with the same state_dict layout as our mirror."""
-    sys.path.insert(0, REFERENCE)
-    try:
-        sys.modules.pop('models', None)
-        ref = importlib.import_module('models')
-        assert ref.__file__.startswith(REFERENCE)
-        for name in ('ico2ico', 'ico2ico_vae'):
-            p = models.default_params(name)
-            a, b = getattr(ref, name)(p).state_dict(), getattr(models, name)(p).state_dict()
-            assert list(a) == list(b)
-            assert all(a[k].shape == b[k].shape for k in a)
-    finally:
-        sys.path.remove(REFERENCE)
-        sys.modules.pop('models', None)
+def test_reference_models_py_drops_in_unchanged(golden_dir):
+    """The reference's own models.py imports `icocnn` (models.py:4-6); with this repo's icocnn package on the path it builds
+    both networks with the same state_dict layout as our mirror.  The layout it built is stored in tests/golden/ref_dropin.npz
+    (oracle/make_ref_goldens.py, layout_case)."""
+    g = np.load(os.path.join(golden_dir, 'ref_dropin.npz'))
+    for name in ('ico2ico', 'ico2ico_vae'):
+        b = getattr(models, name)(models.default_params(name)).state_dict()
+        assert list(b) == g['layout_%s_keys' % name].tolist()
+        shapes = [tuple(int(d) for d in row if d >= 0) for row in g['layout_%s_shapes' % name]]
+        assert [tuple(v.shape) for v in b.values()] == shapes
 
 
 def test_operators_reject_cpu_tensors_loudly():

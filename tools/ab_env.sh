@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$1; REPS=$2; A=$3; B=$4; shift 4
 : > $OUT
 for rep in $(seq $REPS); do
   for e in "$A" "$B"; do
-    env $e timeout -k 10 300 python3 $R/bench.py --no-cpu-baseline --no-also "$@" 2>/dev/null | python3 -c "
+    env $e timeout -k 10 300 python3 $R/bench.py --full --no-cpu-baseline --no-also "$@" 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -40,7 +40,7 @@ def write_stats(sub, bench_json, out_name, note):
     steps_total = bench['steps'] + bench['warmup'] + 4 + (2 if (bench.get('roofline') or {}).get('weight_gradients_on_second_stream') else 0)
     rows = list(csv.DictReader(open(stats[0])))
     with open(os.path.join(dst, rnd + out_name), 'w') as f:
-        f.write('# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps %d --warmup %d --no-cpu-baseline%s  (%d steps traced; '
+        f.write('# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps %d --warmup %d --no-cpu-baseline%s  (%d steps traced; '
                 'bench line under the profiler: %.1f meshes/s, %.3f ms/step)\n' % (bench['steps'], bench['warmup'], note, steps_total,
                                                                                bench['value'], bench['ms_per_step']))
         f.write('kernel,calls,calls_per_step,total_ms,avg_us,min_us,max_us,percent\n')
