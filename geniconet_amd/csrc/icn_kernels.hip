@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -122,10 +123,14 @@ __global__ __launch_bounds__(256) void k_conv_prologue(PrologueArgs a, int npack
                     else if (a.transpose == 1) { t = tt; ci = n; co = k; }
                     else { ci = n; t = k / Ct; co = k - t * Ct; }
                     const float x = co < a.Cout ? a.w[((size_t)co * a.Cin + ci) * 7 + t] : a.w2[((size_t)(co - a.Cout) * a.Cin + ci) * 7 + t];
-                    const unsigned u1 = __float_as_uint(x) & 0xffff0000u;
-                    const float r = x - __uint_as_float(u1);
+                    // (+-inf: the first two pieces from x clamped to the finite range, the third +-inf.  Only the third piece of one
+                    //  operand meets nothing but the first piece of the other, which is non-zero for every non-zero fp32 value, so
+                    //  inf * v is +-inf, and NaN only for v = 0, as in the exact kernel.  A NaN leaves a NaN piece.)
+                    const float xc = __builtin_amdgcn_fmed3f(x, -FLT_MAX, FLT_MAX);
+                    const unsigned u1 = __float_as_uint(xc) & 0xffff0000u;
+                    const float r = xc - __uint_as_float(u1);
                     const unsigned u2 = __float_as_uint(r) & 0xffff0000u;
-                    const unsigned u3 = __float_as_uint(r - __uint_as_float(u2));
+                    const unsigned u3 = __float_as_uint((r - __uint_as_float(u2)) + (x - xc));
                     const int sh = 16 * (e & 1);
                     pl[0][e >> 1] |= (u1 >> 16) << sh;
                     pl[1][e >> 1] |= (u2 >> 16) << sh;
@@ -471,7 +476,7 @@ __device__ __forceinline__ Pieces3 split_bf16x3(const f32x4 lo, const f32x4 hi) 
 #pragma unroll
     for (int e = 0; e < 4; ++e) { const float l_ = lo[e], h_ = hi[e]; x[e] = __float_as_uint(l_); x[4 + e] = __float_as_uint(h_); }   // (__builtin_bit_cast of a vector ELEMENT reads element 0: hipcc 7.2)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
+    for (int e = 0; e < 8; ++e) {          // (+-inf gives inf - inf = NaN residual pieces here: see DESIGN 4.0 on why this stays)
         const float rf = __uint_as_float(x[e]) - __uint_as_float(x[e] & 0xffff0000u);
         r[e] = __float_as_uint(rf);
         r2[e] = __float_as_uint(rf - __uint_as_float(r[e] & 0xffff0000u));
