@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get('ICN_LIB_PATH') or os.path.join(_HERE, 'libicn.so')
 
 OP_CONV_FWD, OP_CONV_BWD_DATA, OP_CONV_BWD_WEIGHT = 0, 1, 2
 CORNER_MODES = {'zeros': 0, 'average': 1}
-ABI_VERSION = 7
+ABI_VERSION = 8
 LAP_MODES = {'mean-v': 0, 'v-mean': 1, 'sum-kv': 2, 'kv-sum': 3}   # ICN_LAP_* of include/icn.h
 
 _c_float_p = ctypes.c_void_p      # device pointers travel as plain addresses
@@ -75,6 +75,8 @@ SIGNATURES = {
     'icn_host_selfcheck': (ctypes.c_long, [ctypes.c_int] * 2),
     'icn_debug_trace': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),
     'icn_point_to_mesh': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 4 + [_c_float_p] * 3 + [ctypes.c_void_p]),
+    'icn_point_to_mesh_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
+    'icn_point_to_mesh_bwd': (ctypes.c_int, [_c_float_p] * 6 + [ctypes.c_int] * 4 + [_c_float_p] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     'icn_table_conv_fwd': (ctypes.c_long, [ctypes.c_int] * 3 + [_i32p, ctypes.c_size_t]),
     'icn_table_wgrad7': (ctypes.c_long, [ctypes.c_int] * 3 + [_i32p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint16), ctypes.c_size_t, _intp]),
     'icn_table_conv_bwd': (ctypes.c_long, [ctypes.c_int] * 3 + [_i32p, ctypes.c_size_t, _intp]),
@@ -333,7 +335,7 @@ def table_tile_lists(r_in, B, bm, ntn, grid, corner_mode='average'):
 
 
 def profile_start(max_launches=4096, only=None):
-    """Start timing MFMA launches with HIP events; only='k_conv_dma<64, 64, false>' restricts it to one kernel (an event pair
+    """Start timing MFMA launches (and the point-to-mesh kernels) with HIP events; only='k_conv_dma<64, 64, false>' restricts it to one kernel (an event pair
     around every launch of a step costs about 2.5 % of it)."""
     check(lib().icn_profile_select(only.encode() if only else None), 'icn_profile_select')
     check(lib().icn_profile_start(max_launches), 'icn_profile_start')

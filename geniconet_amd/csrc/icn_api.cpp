@@ -710,7 +710,8 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_wgrad_dense<64, 128>", "k_wgrad_dense<64, 64>",
                                             "k_conv_b3_sk<128, 128, 8>", "k_conv_b3_sk<128, 64, 4>", "k_conv_b3_dense_sk<128, 128, 8>",
                                             "k_conv_b3_dense_sk<128, 64, 4>", "k_wgrad7<.., 1>", "k_wgrad_dma<.., 1>", "k_wgrad_dense<.., 1>", "k_conv_b3<128, BN, NW>",
-                                            "k_conv_b3_single_sk<128, 128, 8>", "k_conv_b3_single_sk<128, 64, 4>"};
+                                            "k_conv_b3_single_sk<128, 128, 8>", "k_conv_b3_single_sk<128, 64, 4>",
+                                            "k_point_to_mesh", "k_point_to_mesh_bwd_point", "k_point_to_mesh_bwd_vertex"};
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1305,6 +1306,31 @@ int icn_point_to_mesh(const float* points, const float* vertices, const int32_t*
         if (!points || !vertices || !faces || !dist2 || !face || !kind) throw std::invalid_argument("icn_point_to_mesh: null pointer");
         if (B < 1 || B > 65535 || P < 1 || V < 1 || F < 1) throw std::invalid_argument("icn_point_to_mesh: bad sizes");
         icn::launch_point_to_mesh(points, vertices, faces, B, P, V, F, dist2, face, kind, static_cast<hipStream_t>(stream));
+        ICN_HIP(hipGetLastError());
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(e.what());
+    }
+}
+
+size_t icn_point_to_mesh_bwd_workspace_bytes(int B, int P, int V, int F) {
+    return (B < 1 || B > 65535 || P < 1 || V < 1 || F < 1) ? 0 : icn::point_to_mesh_bwd_record_bytes(B, P);
+}
+
+int icn_point_to_mesh_bwd(const float* points, const float* vertices, const int32_t* faces, const int32_t* face, const int32_t* kind,
+                          const float* ddist, int B, int P, int V, int F, float* dpoints, float* dvertices, void* ws, size_t ws_bytes,
+                          void* stream) {
+    try {
+        if (!points || !vertices || !faces || !face || !kind || !ddist) throw std::invalid_argument("icn_point_to_mesh_bwd: null pointer");
+        if (B < 1 || B > 65535 || P < 1 || V < 1 || F < 1) throw std::invalid_argument("icn_point_to_mesh_bwd: bad sizes");
+        if (dvertices) {
+            if (!ws || ws_bytes < icn::point_to_mesh_bwd_record_bytes(B, P))
+                throw std::invalid_argument("icn_point_to_mesh_bwd: workspace smaller than icn_point_to_mesh_bwd_workspace_bytes");
+            if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) throw std::invalid_argument("icn_point_to_mesh_bwd: workspace must be 16-byte aligned");
+        }
+        if (!dpoints && !dvertices) return 0;                        // no gradient asked for
+        icn::launch_point_to_mesh_bwd(points, vertices, faces, face, kind, ddist, B, P, V, F, dpoints, dvertices, ws,
+                                      static_cast<hipStream_t>(stream));
         ICN_HIP(hipGetLastError());
         return 0;
     } catch (const std::exception& e) {

@@ -212,6 +212,11 @@ void launch_reparam_bwd(const float* dz, const float* logvar, const float* eps, 
 // point-to-mesh distance (icn_loss.hip): squared distance, closest face and feature kind per point; faces (F, 3) shared
 void launch_point_to_mesh(const float* pts, const float* vts, const int32_t* faces, int B, int P, int V, int F, float* dist,
                           int32_t* face, int32_t* kind, hipStream_t s);
+// its backward from the forward's (face, kind): dpts (B, P, 3) and / or dvts (B, V, 3), either may be null; ws (only read when
+// dvts is wanted): point_to_mesh_bwd_record_bytes(B, P) bytes, 16-byte aligned.  Fixed summation order, no atomics.
+size_t point_to_mesh_bwd_record_bytes(int B, int P);
+void launch_point_to_mesh_bwd(const float* pts, const float* vts, const int32_t* faces, const int32_t* face, const int32_t* kind,
+                              const float* ddist, int B, int P, int V, int F, float* dpts, float* dvts, void* ws, hipStream_t s);
 
 // developer routing flags (ICN_DEBUG / icn_set_debug_flags): 16 = convs on k_gather_gemm, 32 = wgrads on k_wgrad,
 // 128 = no stream-K, 256 = fault injection: every stream-K finisher reports its partners lost (tests of the failure path),
@@ -222,7 +227,8 @@ void launch_point_to_mesh(const float* pts, const float* vts, const int32_t* fac
 int debug_flags();
 int set_debug_flags(int flags);
 
-// ---- optional per-launch HIP-event timing of the MFMA kernels (bench.py's live roofline measurement) ----------
+// ---- optional per-launch HIP-event timing of the MFMA kernels (bench.py's live roofline measurement) and of the
+// point-to-mesh kernels ----------
 enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA_64x64, PROF_GG_128x128, PROF_GG_128x64,
                 PROF_GG_64x128, PROF_GG_64x64, PROF_WGD_128x128, PROF_WGD_128x64, PROF_WGD_64x128, PROF_WGD_64x64, PROF_WG_128x128,
                 PROF_WG_128x64, PROF_WG_64x128, PROF_WG_64x64,
@@ -235,6 +241,7 @@ enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA
                 PROF_WGDENSE_128x128, PROF_WGDENSE_128x64, PROF_WGDENSE_64x128, PROF_WGDENSE_64x64,   // k_wgrad_dense: the heads' dW = x^T g
                 PROF_B3K_128x128, PROF_B3K_128x64, PROF_B3DENSEK_128x128, PROF_B3DENSEK_128x64,       // ARITH = 1 forms (round 6)
                 PROF_WG7_B3, PROF_WGD_B3, PROF_WGDENSE_B3, PROF_B3_MASKED, PROF_B3SINGLEK_128x128, PROF_B3SINGLEK_128x64,
+                PROF_P2M, PROF_P2M_BWD_POINT, PROF_P2M_BWD_VERTEX,    // point-to-mesh distance and its backward (not MFMA; flops 0)
                 PROF_KINDS };
 extern const char* const PROF_NAMES[PROF_KINDS];
 void prof_mark_begin(int kind, double flops, hipStream_t s);   // no-ops unless profiling is on

@@ -471,12 +471,154 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_point_to_mesh(const float* __res
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Backward of the distance above.  With q = wa a + wb b + wc c the closest point of p on its selected triangle (a, b, c),
+// p - q is orthogonal to the feature q lies on, so the derivative through the weights vanishes:
+//     d dist / d p = 2 (p - q)        d dist / d a = -2 wa (p - q)   (likewise b, c)
+// No second search: q and the weights are recomputed from the forward's (face, kind) with the expressions of tri_dist2.
+//   k_point_to_mesh_bwd_point   one thread per point: g = 2 ddist (p - q) -> dpoints; a record (the three vertex ids, g, the three
+//                               weights; id -1 where the weight is zero by construction) -> workspace, 40 bytes per point
+//   k_point_to_mesh_bwd_vertex  one thread per vertex: the records of its sample go through LDS in tiles of 256 points and every
+//                               thread adds those addressed to it IN POINT ORDER (then vertex 0, 1, 2 of the face) -- a fixed
+//                               order, no atomics, bit-identical run to run.  P * V integer compares per sample, one broadcast
+//                               ds_read_b128 per record and wave; a vertex no point selected gets an exact zero.
+// A face index outside [0, F), a kind outside [0, 6] or a vertex id outside [0, V) gives that point a zero gradient (nothing
+// is read out of bounds).
+// ---------------------------------------------------------------------------------------------------------
+struct P2MRecords {                 // the caller's workspace, cut into three arrays of B * P entries (16-byte aligned base)
+    int4* id;                       // vertex ids of the face (or -1), .w unused
+    float4* gw;                     // g.x, g.y, g.z, weight of vertex 0
+    float2* w12;                    // weights of vertex 1 and 2
+};
+
+__global__ __launch_bounds__(LOSS_BLOCK) void k_point_to_mesh_bwd_point(const float* __restrict__ pts, const float* __restrict__ vts,
+                                                                         const int32_t* __restrict__ faces,
+                                                                         const int32_t* __restrict__ face,
+                                                                         const int32_t* __restrict__ kind,
+                                                                         const float* __restrict__ ddist, int P, int V, int F,
+                                                                         float* __restrict__ dpts, P2MRecords rec) {
+    const int bi = blockIdx.y, i = blockIdx.x * LOSS_BLOCK + threadIdx.x;
+    if (i >= P) return;
+    const size_t at = (size_t)bi * P + i;
+    const int f = face[at], k = kind[at];
+    int ia = -1, ib = -1, ic = -1;
+    float wa = 0.f, wb = 0.f, wc = 0.f;
+    f3 g = {0.f, 0.f, 0.f};
+    bool ok = f >= 0 && f < F && k >= 0 && k <= 6;
+    if (ok) {
+        ia = faces[(size_t)f * 3]; ib = faces[(size_t)f * 3 + 1]; ic = faces[(size_t)f * 3 + 2];
+        ok = ia >= 0 && ia < V && ib >= 0 && ib < V && ic >= 0 && ic < V;
+    }
+    if (ok) {
+        const float* pp = pts + at * 3;
+        const float* pa = vts + ((size_t)bi * V + ia) * 3;
+        const float* pb = vts + ((size_t)bi * V + ib) * 3;
+        const float* pc = vts + ((size_t)bi * V + ic) * 3;
+        const f3 p = {pp[0], pp[1], pp[2]}, a = {pa[0], pa[1], pa[2]}, b = {pb[0], pb[1], pb[2]}, c = {pc[0], pc[1], pc[2]};
+        const f3 ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c;
+        const float d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp);
+        f3 q;
+        if (k == 1) { q = a; wa = 1.f; }
+        else if (k == 2) { q = b; wb = 1.f; }
+        else if (k == 3) { q = c; wc = 1.f; }
+        else if (k == 4) {
+            const float den = d1 - d3, t = den != 0.f ? d1 / den : 0.f;
+            q = a + f3{ab.x * t, ab.y * t, ab.z * t}; wa = 1.f - t; wb = t;
+        } else if (k == 6) {
+            const float den = d2 - d6, t = den != 0.f ? d2 / den : 0.f;
+            q = a + f3{ac.x * t, ac.y * t, ac.z * t}; wa = 1.f - t; wc = t;
+        } else if (k == 5) {
+            const float den = (d4 - d3) + (d5 - d6), t = den != 0.f ? (d4 - d3) / den : 0.f;
+            const f3 bc = c - b;
+            q = b + f3{bc.x * t, bc.y * t, bc.z * t}; wb = 1.f - t; wc = t;
+        } else {
+            const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+            const float den = va + vb + vc, inv = den != 0.f ? 1.f / den : 0.f;
+            const float v = vb * inv, w = vc * inv;
+            q = a + f3{ab.x * v + ac.x * w, ab.y * v + ac.y * w, ab.z * v + ac.z * w}; wa = 1.f - v - w; wb = v; wc = w;
+        }
+        const f3 d = p - q;
+        const float up = 2.f * ddist[at];
+        g = {up * d.x, up * d.y, up * d.z};
+        // vertices whose weight is zero by the kind take no part in the accumulation
+        if (k == 2 || k == 3 || k == 5) ia = -1;
+        if (k == 1 || k == 3 || k == 6) ib = -1;
+        if (k == 1 || k == 2 || k == 4) ic = -1;
+    } else {
+        ia = ib = ic = -1;
+    }
+    if (dpts) { dpts[at * 3] = g.x; dpts[at * 3 + 1] = g.y; dpts[at * 3 + 2] = g.z; }
+    if (rec.id) {
+        rec.id[at] = make_int4(ia, ib, ic, -1);
+        rec.gw[at] = make_float4(g.x, g.y, g.z, wa);
+        rec.w12[at] = make_float2(wb, wc);
+    }
+}
+
+__global__ __launch_bounds__(LOSS_BLOCK) void k_point_to_mesh_bwd_vertex(P2MRecords rec, int P, int V, float* __restrict__ dvts) {
+    __shared__ int4 s_id[LOSS_BLOCK];
+    __shared__ float4 s_gw[LOSS_BLOCK];
+    __shared__ float2 s_w12[LOSS_BLOCK];
+    const int bi = blockIdx.y, j = blockIdx.x * LOSS_BLOCK + threadIdx.x;
+    const int me = j < V ? j : -2;                                         // -2 matches no record (unused ids are -1)
+    const size_t base = (size_t)bi * P;
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    for (int p0 = 0; p0 < P; p0 += LOSS_BLOCK) {
+        __syncthreads();
+        const int i = p0 + threadIdx.x;
+        if (i < P) {
+            s_id[threadIdx.x] = rec.id[base + i];
+            s_gw[threadIdx.x] = rec.gw[base + i];
+            s_w12[threadIdx.x] = rec.w12[base + i];
+        }
+        __syncthreads();
+        const int np = min(LOSS_BLOCK, P - p0);                            // the same in every thread of the block
+        for (int t = 0; t < np; ++t) {
+            const int4 id = s_id[t];                                       // one address for the whole wave: a broadcast read
+            if (id.x == me || id.y == me || id.z == me) {
+                const float4 gw = s_gw[t];
+                const float2 w12 = s_w12[t];
+                if (id.x == me) { ax -= gw.w * gw.x; ay -= gw.w * gw.y; az -= gw.w * gw.z; }
+                if (id.y == me) { ax -= w12.x * gw.x; ay -= w12.x * gw.y; az -= w12.x * gw.z; }
+                if (id.z == me) { ax -= w12.y * gw.x; ay -= w12.y * gw.y; az -= w12.y * gw.z; }
+            }
+        }
+    }
+    if (j < V) {
+        float* o = dvts + ((size_t)bi * V + j) * 3;
+        o[0] = ax; o[1] = ay; o[2] = az;
+    }
+}
+
 }  // namespace
 
 void launch_point_to_mesh(const float* pts, const float* vts, const int32_t* faces, int B, int P, int V, int F, float* dist,
                           int32_t* face, int32_t* kind, hipStream_t s) {
+    prof_mark_begin(PROF_P2M, 0.0, s);
     hipLaunchKernelGGL(k_point_to_mesh, dim3((P + LOSS_BLOCK - 1) / LOSS_BLOCK, B), dim3(LOSS_BLOCK), 0, s, pts, vts, faces, P, V, F,
                        dist, face, kind);
+    prof_mark_end(s);
+}
+
+size_t point_to_mesh_bwd_record_bytes(int B, int P) { return (size_t)B * P * (sizeof(int4) + sizeof(float4) + sizeof(float2)); }
+
+void launch_point_to_mesh_bwd(const float* pts, const float* vts, const int32_t* faces, const int32_t* face, const int32_t* kind,
+                              const float* ddist, int B, int P, int V, int F, float* dpts, float* dvts, void* ws, hipStream_t s) {
+    P2MRecords rec = {nullptr, nullptr, nullptr};
+    if (dvts) {                                                            // ws: 16-byte aligned, point_to_mesh_bwd_record_bytes
+        const size_t n = (size_t)B * P;
+        rec.id = static_cast<int4*>(ws);
+        rec.gw = reinterpret_cast<float4*>(rec.id + n);
+        rec.w12 = reinterpret_cast<float2*>(rec.gw + n);
+    }
+    prof_mark_begin(PROF_P2M_BWD_POINT, 0.0, s);
+    hipLaunchKernelGGL(k_point_to_mesh_bwd_point, dim3((P + LOSS_BLOCK - 1) / LOSS_BLOCK, B), dim3(LOSS_BLOCK), 0, s, pts, vts, faces,
+                       face, kind, ddist, P, V, F, dpts, rec);
+    prof_mark_end(s);
+    if (!dvts) return;
+    prof_mark_begin(PROF_P2M_BWD_VERTEX, 0.0, s);
+    hipLaunchKernelGGL(k_point_to_mesh_bwd_vertex, dim3((V + LOSS_BLOCK - 1) / LOSS_BLOCK, B), dim3(LOSS_BLOCK), 0, s, rec, P, V, dvts);
+    prof_mark_end(s);
 }
 
 }  // namespace icn

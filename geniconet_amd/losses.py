@@ -16,6 +16,8 @@ On ROCm fp32 tensors Point2Point_Loss runs on HIP kernels (libicn's icn_p2p_loss
 factors; the torch formulation below is what runs for other dtypes and for CPU tensors (as used by the CPU restatement in
 bench.py), and it is what the HIP kernels are tested against besides the numpy oracle.  The KLD term (losses.py:105) runs
 on icn_kld_fwd / icn_kld_bwd under the same conditions.
+
+Point2Mesh_Loss is not in the reference: the surface distance it reports at test time (ico_utils.py:26-44) as a loss term.
 """
 import os
 
@@ -207,6 +209,42 @@ class Point2Point_Loss(torch.nn.Module):
 
     def get_last_losses(self):
         return float(self.last_loss_mse), self.last_loss_cos, self.last_loss_lap, float(self.last_loss_total)
+
+
+class Point2Mesh_Loss(torch.nn.Module):
+    """Mean squared distance of the output's vertices (grid pixels, then the two pole means) to a reference SURFACE:
+    point_to_mesh_distance(grid_to_vertices(inputs), ref_vertices, ref_faces)[0].mean() -- the number the reference reports at
+    test time (ico_utils.py:26-44, metrics.compute_distance), averaged over the batch, as a differentiable reconstruction term:
+    vertices may slide along the target surface instead of being tied to target vertex i as in Point2Point_Loss.  Not in the
+    reference (it has no surface loss); a stand-alone module, not part of Trainer / build_criterion.
+
+        forward(inputs (B, 3, 5n, 2n), ref_vertices (B, V, 3), ref_faces (F, 3)) -> scalar tensor
+
+    ROCm fp32 tensors run on icn_point_to_mesh and, for the gradient (to inputs and / or ref_vertices), icn_point_to_mesh_bwd.
+    Cost: the forward is a brute-force search, P * F triangle tests per mesh (2.1e8 at I5); the backward is O(1) geometry per
+    point plus P * V integer compares per mesh.  Measured on an MI355X at I5 / batch 36 (10 242 points against 20 480 triangles
+    per mesh, HIP events, median of 10, profiles/point_to_mesh_bwd.txt): k_point_to_mesh 15.1 ms, the two backward kernels
+    1.05 ms together, the whole term forward + backward 16.5 ms, beside a training step of 6.3 ms (python bench.py, same
+    batch) -- 2.6 training steps' worth per evaluation, nearly all of it the forward search."""
+
+    def __init__(self, subdivisions):
+        super().__init__()
+        self.subdivisions = subdivisions
+        self.last_loss_total = 0
+
+    def forward(self, inputs, ref_vertices, ref_faces):
+        from .metrics import point_to_mesh_distance
+        n = 2 ** self.subdivisions
+        if inputs.dim() != 4 or tuple(inputs.shape[1:]) != (3, 5 * n, 2 * n):
+            raise ValueError('Point2Mesh_Loss: expected inputs (B, 3, %d, %d), got %s' % (5 * n, 2 * n, tuple(inputs.shape)))
+        dist, _, _ = point_to_mesh_distance(grid_to_vertices(inputs, self.subdivisions), ref_vertices, ref_faces)
+        loss = dist.mean()
+        self.last_loss_total = loss.detach()
+        return loss
+
+    def get_last_losses(self):
+        """(the loss, 0, 0, the loss): position-like term, no normal / Laplacian term, total -- the tuple of Point2Point_Loss."""
+        return float(self.last_loss_total), 0, 0, float(self.last_loss_total)
 
 
 class KLD_Loss(torch.nn.Module):

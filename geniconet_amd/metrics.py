@@ -9,6 +9,11 @@ upstream takes from kaolin's CUDA extension (`kaolin.metrics.trianglemesh.point_
 The reference consumes `torch.mean(dist2)` (ico_utils.py:41).  ROCm fp32 tensors run on a HIP kernel (icn_point_to_mesh in
 include/icn.h: one thread per point, triangles staged through LDS); anything else on the chunked torch formulation below,
 which is also the kernel's second check in the tests (the first is the numpy oracle, oracle/metrics_ref.py).
+
+Like kaolin's function, dist2 is differentiable in the points and in the mesh vertices on either path: the torch formulation
+through autograd, the HIP path through icn_point_to_mesh_bwd (_PointToMeshFn below) whenever one of the two requires a gradient;
+face and kind never carry one.  Where two different closest points are equally near the gradient is discontinuous (either side
+is a valid subgradient).
 """
 import torch
 
@@ -71,6 +76,62 @@ def _torch_point_to_mesh(points, vertices, faces, chunk=256):
 _MAX_GRID_Y = 65535
 
 
+def _hip_point_to_mesh(pts, vts, f32):
+    """icn_point_to_mesh on contiguous fp32 ROCm tensors and int32 faces -> (dist, face int32, kind)."""
+    L = _lib.lib()
+    B, P, _ = pts.shape
+    dist = torch.empty(B, P, dtype=torch.float32, device=pts.device)
+    face = torch.empty(B, P, dtype=torch.int32, device=pts.device)
+    kind = torch.empty(B, P, dtype=torch.int32, device=pts.device)
+    with torch.cuda.device(pts.device):
+        for b0 in range(0, B, _MAX_GRID_Y):                  # the batch index is gridDim.y (<= 65535 per launch)
+            nb = min(_MAX_GRID_Y, B - b0)
+            rc = L.icn_point_to_mesh(pts[b0:].data_ptr(), vts[b0:].data_ptr(), f32.data_ptr(), nb, P, vts.shape[1],
+                                     f32.shape[0], dist[b0:].data_ptr(), face[b0:].data_ptr(), kind[b0:].data_ptr(),
+                                     torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, 'icn_point_to_mesh')
+    return dist, face, kind
+
+
+class _PointToMeshFn(torch.autograd.Function):
+    """point_to_mesh_distance on the HIP path with a gradient (icn_point_to_mesh / icn_point_to_mesh_bwd in include/icn.h).
+    The closest point q of p minimises over the feature it lies on, so d dist / d p = 2 (p - q) and the triangle's vertices
+    receive -2 w (p - q) with q's weights w; the backward recomputes q from the saved (face, kind), O(1) per point, and sums
+    the vertex gradient in a fixed order (bit-identical run to run).  Only the gradients autograd asks for are computed."""
+
+    @staticmethod
+    def forward(ctx, pointclouds, vertices, f32):
+        pts, vts = pointclouds.contiguous(), vertices.contiguous()
+        dist, face, kind = _hip_point_to_mesh(pts, vts, f32)
+        ctx.save_for_backward(pts, vts, f32, face, kind)
+        face64 = face.long()
+        ctx.mark_non_differentiable(face64, kind)
+        return dist, face64, kind
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, ddist, _gface, _gkind):
+        L = _lib.lib()
+        pts, vts, f32, face, kind = ctx.saved_tensors
+        (B, P, _), V, F = pts.shape, vts.shape[1], f32.shape[0]
+        up = ddist.contiguous().to(torch.float32)
+        dpts = torch.empty_like(pts) if ctx.needs_input_grad[0] else None
+        dvts = torch.empty_like(vts) if ctx.needs_input_grad[1] else None
+        ws_bytes = L.icn_point_to_mesh_bwd_workspace_bytes(min(B, _MAX_GRID_Y), P, V, F) if dvts is not None else 0
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pts.device) if ws_bytes else None
+        with torch.cuda.device(pts.device):
+            for b0 in range(0, B, _MAX_GRID_Y):              # as the forward: the batch index is gridDim.y
+                nb = min(_MAX_GRID_Y, B - b0)
+                rc = L.icn_point_to_mesh_bwd(pts[b0:].data_ptr(), vts[b0:].data_ptr(), f32.data_ptr(), face[b0:].data_ptr(),
+                                             kind[b0:].data_ptr(), up[b0:].data_ptr(), nb, P, V, F,
+                                             dpts[b0:].data_ptr() if dpts is not None else None,
+                                             dvts[b0:].data_ptr() if dvts is not None else None,
+                                             ws.data_ptr() if ws is not None else None, ws_bytes,
+                                             torch.cuda.current_stream().cuda_stream)
+                _lib.check(rc, 'icn_point_to_mesh_bwd')
+        return dpts, dvts, None
+
+
 def point_to_mesh_distance(pointclouds, vertices, faces):
     """See the module docstring.  `faces` may be int32 / int64, (F, 3), shared by the batch (as in kaolin 0.9.1)."""
     if pointclouds.dim() != 3 or vertices.dim() != 3 or pointclouds.shape[-1] != 3 or vertices.shape[-1] != 3:
@@ -86,20 +147,10 @@ def point_to_mesh_distance(pointclouds, vertices, faces):
             raise IndexError('point_to_mesh_distance: face indices span [%d, %d] but there are %d vertices'
                              % (lo, hi, vertices.shape[1]))
     if pointclouds.is_cuda and pointclouds.dtype == torch.float32 and vertices.dtype == torch.float32 and faces.shape[0] > 0:
-        L = _lib.lib()
-        B, P, _ = pointclouds.shape
-        pts, vts = pointclouds.contiguous(), vertices.contiguous()
-        f32 = faces.to(device=pts.device, dtype=torch.int32).contiguous()
-        dist = torch.empty(B, P, dtype=torch.float32, device=pts.device)
-        face = torch.empty(B, P, dtype=torch.int32, device=pts.device)
-        kind = torch.empty(B, P, dtype=torch.int32, device=pts.device)
-        with torch.cuda.device(pts.device):
-            for b0 in range(0, B, _MAX_GRID_Y):                  # the batch index is gridDim.y (<= 65535 per launch)
-                nb = min(_MAX_GRID_Y, B - b0)
-                rc = L.icn_point_to_mesh(pts[b0:].data_ptr(), vts[b0:].data_ptr(), f32.data_ptr(), nb, P, vertices.shape[1],
-                                         faces.shape[0], dist[b0:].data_ptr(), face[b0:].data_ptr(), kind[b0:].data_ptr(),
-                                         torch.cuda.current_stream().cuda_stream)
-                _lib.check(rc, 'icn_point_to_mesh')
+        f32 = faces.to(device=pointclouds.device, dtype=torch.int32).contiguous()
+        if torch.is_grad_enabled() and (pointclouds.requires_grad or vertices.requires_grad):
+            return _PointToMeshFn.apply(pointclouds, vertices, f32)
+        dist, face, kind = _hip_point_to_mesh(pointclouds.contiguous(), vertices.contiguous(), f32)
         return dist, face.long(), kind
     return _torch_point_to_mesh(pointclouds, vertices, faces.to(pointclouds.device))
 

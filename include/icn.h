@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ICN_ABI_VERSION 7
+#define ICN_ABI_VERSION 8
 
 #define ICN_CORNER_ZEROS 0
 #define ICN_CORNER_AVERAGE 1
@@ -208,6 +208,22 @@ int icn_reparam_bwd(const float* dz, const float* logvar, const float* eps, size
 int icn_point_to_mesh(const float* points, const float* vertices, const int32_t* faces, int B, int P, int V, int F, float* dist2,
                       int32_t* face, int32_t* kind, void* stream);
 
+/* Backward of icn_point_to_mesh (ABI 8; kaolin's function is differentiable in the points and in the mesh vertices).  With q the
+ * closest point of p on its selected triangle (a, b, c), q = wa a + wb b + wc c (weights by `kind`: one-hot at a vertex, (1 - t, t)
+ * on an edge, barycentric inside), p - q is orthogonal to the feature q lies on, so
+ *     dpoints = 2 ddist (p - q)        dvertices[a] += -2 ddist wa (p - q)   (likewise b, c)
+ * face / kind (B, P): the forward's outputs -- no second search, q and the weights are recomputed from them; ddist (B, P): the
+ * upstream gradient; dpoints (B, P, 3) and dvertices (B, V, 3): either may be NULL and is then not computed (both NULL: nothing is
+ * launched).  dvertices is summed in a fixed order (per vertex, by point index; no floating-point atomics): bit-identical run to run,
+ * and a vertex no point selected gets an exact zero.  A face / kind / vertex index out of range gives that point a zero gradient.
+ * ws: icn_point_to_mesh_bwd_workspace_bytes(B, P, V, F) bytes (host-only query; 0 for sizes the call would reject), 16-byte aligned,
+ * owned by the caller, only needed for dvertices; its contents need not survive the call.  B <= 65535 per call, as the forward.
+ * Asynchronous on `stream`; 0 on success, negative with icn_last_error() otherwise (arguments are checked before any device call). */
+size_t icn_point_to_mesh_bwd_workspace_bytes(int B, int P, int V, int F);
+int icn_point_to_mesh_bwd(const float* points, const float* vertices, const int32_t* faces, const int32_t* face, const int32_t* kind,
+                          const float* ddist, int B, int P, int V, int F, float* dpoints, float* dvertices, void* ws, size_t ws_bytes,
+                          void* stream);
+
 /* Adam step (reference run.py:253 `optimizer.step()` on the optimiser of run.py:446, torch.optim.Adam without amsgrad /
  * maximize) over `count` fp32 tensors, one launch per 96 tensors that share a step count (normally: one launch).  The four pointer arrays and numel / step_size / bc2_sqrt
  * are HOST arrays of length count; the pointers in them are device pointers (param, grad, exp_avg, exp_avg_sq of tensor i,
@@ -263,8 +279,8 @@ long icn_table_upconv_bwd(int r_in, int corner_mode, int32_t* idx, float* coef, 
  * does not exist for this (r_in, stride): P_out % 16 != 0 or a union that does not fit. */
 long icn_table_wgrad7(int r_in, int stride, int corner_mode, int32_t* rows, size_t cap_rows, uint16_t* pos, size_t cap_pos, int* meta);
 
-/* Optional diagnostics: HIP-event timing of every MFMA kernel launch between start and stop, on the launch
- * stream.  `stop` synchronises the device and returns the number of entries written (one per kernel that ran).
+/* Optional diagnostics: HIP-event timing of every MFMA kernel launch (and, ABI 8, of k_point_to_mesh and its two backward kernels,
+ * with total_flops 0) between start and stop, on the launch stream.  `stop` synchronises the device and returns the number of entries written (one per kernel that ran).
  * total_flops counts what a launch multiplies: 2*7*Cin*Cout*B*P_out per pass of an ordinary convolution (= its algorithmic
  * FLOPs; the small virtual-row launch of a stride-1 bwd-data adds time, not FLOPs); the composite icn_upconv_* launches execute
  * fewer FLOPs than the two operators they replace (0.68 x forward, 0.25 x backward) and are credited with the executed ones.  The 2 * max_launches events are created once and reused.  Off by default. */
