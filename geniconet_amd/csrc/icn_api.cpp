@@ -711,7 +711,9 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_conv_b3_sk<128, 128, 8>", "k_conv_b3_sk<128, 64, 4>", "k_conv_b3_dense_sk<128, 128, 8>",
                                             "k_conv_b3_dense_sk<128, 64, 4>", "k_wgrad7<.., 1>", "k_wgrad_dma<.., 1>", "k_wgrad_dense<.., 1>", "k_conv_b3<128, BN, NW>",
                                             "k_conv_b3_single_sk<128, 128, 8>", "k_conv_b3_single_sk<128, 64, 4>",
-                                            "k_point_to_mesh", "k_point_to_mesh_bwd_point", "k_point_to_mesh_bwd_vertex"};
+                                            "k_point_to_mesh", "k_point_to_mesh_bwd_point", "k_point_to_mesh_bwd_vertex",
+                                            "k_p2m_grid_bounds", "k_p2m_grid_count", "k_p2m_grid_scan", "k_p2m_grid_fill",
+                                            "k_p2m_grid_query"};
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1331,6 +1333,26 @@ int icn_point_to_mesh_bwd(const float* points, const float* vertices, const int3
         if (!dpoints && !dvertices) return 0;                        // no gradient asked for
         icn::launch_point_to_mesh_bwd(points, vertices, faces, face, kind, ddist, B, P, V, F, dpoints, dvertices, ws,
                                       static_cast<hipStream_t>(stream));
+        ICN_HIP(hipGetLastError());
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(e.what());
+    }
+}
+
+size_t icn_point_to_mesh_grid_workspace_bytes(int B, int P, int V, int F) {
+    return (B < 1 || B > 65535 || P < 1 || V < 1 || F < 1) ? 0 : icn::point_to_mesh_grid_bytes(B, F);
+}
+
+int icn_point_to_mesh_grid(const float* points, const float* vertices, const int32_t* faces, int B, int P, int V, int F, float* dist2,
+                           int32_t* face, int32_t* kind, void* ws, size_t ws_bytes, void* stream) {
+    try {
+        if (!points || !vertices || !faces || !dist2 || !face || !kind) throw std::invalid_argument("icn_point_to_mesh_grid: null pointer");
+        if (B < 1 || B > 65535 || P < 1 || V < 1 || F < 1) throw std::invalid_argument("icn_point_to_mesh_grid: bad sizes");
+        if (!ws || ws_bytes < icn::point_to_mesh_grid_bytes(B, F))
+            throw std::invalid_argument("icn_point_to_mesh_grid: workspace smaller than icn_point_to_mesh_grid_workspace_bytes");
+        if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) throw std::invalid_argument("icn_point_to_mesh_grid: workspace must be 16-byte aligned");
+        ICN_HIP(icn::launch_point_to_mesh_grid(points, vertices, faces, B, P, V, F, dist2, face, kind, ws, static_cast<hipStream_t>(stream)));
         ICN_HIP(hipGetLastError());
         return 0;
     } catch (const std::exception& e) {

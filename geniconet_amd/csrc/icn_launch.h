@@ -218,6 +218,13 @@ size_t point_to_mesh_bwd_record_bytes(int B, int P);
 void launch_point_to_mesh_bwd(const float* pts, const float* vts, const int32_t* faces, const int32_t* face, const int32_t* kind,
                               const float* ddist, int B, int P, int V, int F, float* dpts, float* dvts, void* ws, hipStream_t s);
 
+// the same forward through a uniform grid over each mesh (exact: bit-identical outputs).  ws: point_to_mesh_grid_bytes(B, F) bytes,
+// 16-byte aligned; G = p2m_grid_res(F) cells per axis.  One hipMemsetAsync and five launches on s, no allocation, no sync.
+int p2m_grid_res(int F);
+size_t point_to_mesh_grid_bytes(int B, int F);
+hipError_t launch_point_to_mesh_grid(const float* pts, const float* vts, const int32_t* faces, int B, int P, int V, int F, float* dist,
+                                     int32_t* face, int32_t* kind, void* ws, hipStream_t s);
+
 // developer routing flags (ICN_DEBUG / icn_set_debug_flags): 16 = convs on k_gather_gemm, 32 = wgrads on k_wgrad,
 // 128 = no stream-K, 256 = fault injection: every stream-K finisher reports its partners lost (tests of the failure path),
 // 512 = masked launches walk tiles b, b + G, ... instead of the balanced tile lists, 1024 = the sparse passes of the decoder-block
@@ -242,6 +249,7 @@ enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA
                 PROF_B3K_128x128, PROF_B3K_128x64, PROF_B3DENSEK_128x128, PROF_B3DENSEK_128x64,       // ARITH = 1 forms (round 6)
                 PROF_WG7_B3, PROF_WGD_B3, PROF_WGDENSE_B3, PROF_B3_MASKED, PROF_B3SINGLEK_128x128, PROF_B3SINGLEK_128x64,
                 PROF_P2M, PROF_P2M_BWD_POINT, PROF_P2M_BWD_VERTEX,    // point-to-mesh distance and its backward (not MFMA; flops 0)
+                PROF_P2M_GRID_BOUNDS, PROF_P2M_GRID_COUNT, PROF_P2M_GRID_SCAN, PROF_P2M_GRID_FILL, PROF_P2M_GRID_QUERY,   // grid search
                 PROF_KINDS };
 extern const char* const PROF_NAMES[PROF_KINDS];
 void prof_mark_begin(int kind, double flops, hipStream_t s);   // no-ops unless profiling is on

@@ -590,6 +590,278 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_point_to_mesh_bwd_vertex(P2MReco
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Grid-accelerated forward of the same distance: the result of k_point_to_mesh, bit for bit (same tri_dist2, same tie rule),
+// from a uniform grid of G^3 cells over the mesh's bounding cube (G a host-side function of F alone, p2m_grid_res).
+//
+// Build, per mesh (blockIdx.y):
+//   k_p2m_grid_bounds  bounding box of the mesh's vertices -> header: lo, cell size h = largest extent / G, 1 / h, amax = largest
+//                      |coordinate|, mode.  mode 1 (no grid, every triangle on the always-tested list) for a mesh with a non-finite
+//                      vertex, extent or amax outside [1e-8, 1e8], or extent < 1e-3 amax.
+//   k_p2m_grid_count   per triangle: centroid c (fp32), r = largest |vertex - c|, cell of c (clamped) or, if r > 2 h or mode 1, the
+//                      always-tested list (stored as cell G^3) -> tcell[f]; integer atomicAdd on the cell's count, integer
+//                      atomicMax (float bits, r >= 0) of r over the binned triangles -> rmax.
+//   k_p2m_grid_scan    exclusive scan of the G^3 + 1 counts in place: e[c] = first slot of cell c, e[G^3 + 1] = F.
+//   k_p2m_grid_fill    slot = atomicAdd(e[c + 1]) (afterwards e[c + 1] is the END of cell c = the begin of c + 1, e[0] stays 0);
+//                      the triangle's three resolved vertices and its index go to the slot (three float4, 48 contiguous bytes: the
+//                      query reads a triangle with three 16-byte loads and no faces -> vertices double gather).
+// Every triangle is stored exactly once, so the index size depends on F alone.  The order inside a cell depends on the order of
+// the atomics; the result does not, because the query's update rule is a total order on (d2, face index).
+//
+// Query (k_p2m_grid_query, one thread per point): the always-tested list, then shells of cells at Chebyshev distance k = 0, 1, ...
+// from the point's clamped cell; cells of one x-row are one contiguous slot range.  After shell k the visited block is
+// [c - k, c + k]^3 cut to the grid.  A binned triangle not yet visited has its centroid's cell beyond one of the block's faces that
+// is not on the grid border, so |p - centroid| >= dmin, the smallest distance of p to such a face, and every point of the triangle
+// is within rmax of the centroid (a convex function on a triangle peaks at a vertex, whatever fp32 value the centroid got): its
+// distance is >= dmin - rmax.  The search stops when that bound is positive and its square exceeds the best distance strictly.
+//
+// The bound is evaluated in fp32 and made conservative (u = 2^-24 = 6e-8):
+//   * cells are assigned by t(x) = fl(fl(x - lo) * inv_h), index = clamp(floor t), for centroids and points alike.  t is monotone
+//     and t(x) = (x - lo) / h' (1 + e), |e| <= 2.1 u, h' = 1 / inv_h.  A centroid in a cell beyond the face at integer m has
+//     t(c) >= m (clamping only moves indices at border faces, which are ignored), so whichever side of the nominal boundary
+//     rounding put it, (c.x - p.x) / h' >= (m - t(p)) - 2.1 u (|t(c)| + |t(p)|) and |t(c)| <= G + 1.  Shrinking the cell-unit
+//     distance by 1e-6 (G + 1 + |t(p)|) covers that and the rounding of the subtraction five times over; h vs h' and the product
+//     are two more roundings (factor 1 - 1e-6).
+//   * r is a square root of three squares of differences, a few u relative; the mesh extent is >= 1e-8, so h >= 1e-10 and an
+//     underflowing square (r < 2e-19) is far below the absolute 1e-6 h that is added: rmax (1 + 1e-5) + 1e-6 h.
+//   * the brute-force value itself is fp32: tri_dist2 returns |p - q|^2 for a q that is a convex combination (weights from its
+//     region tests, all in [0, 1]) of the vertices up to about 8 u (amax + |p|), so it can undercut the true distance by that
+//     much.  4e-6 (amax + |p|_inf) is subtracted, and the square is compared with a factor 1 - 1e-5.
+// Cost bounds: a point far from the surface walks shells that are mostly empty, two dependent loads per slot range and at most
+// 2 (2k + 1)^2 ranges in shell k -- latency-bound, and measured 8 x slower than the brute-force kernel when such a walk was allowed
+// to cover the grid.  So the walk is cut after kmax = max(2, G / 4) shells (<= ~(8 / 3) kmax^3 range reads); a point that is not done
+// by then (farther from the mesh than about a quarter of its extent, or NaN / infinite: it never stops early) scans the whole
+// sorted list instead, F tests, which is the brute-force pass without its LDS staging.  The worst case per point is therefore the
+// bounded walk plus F tests, and a NaN point ends with the brute-force output 3.4e38 / 0 / 0.  One huge triangle does not inflate
+// rmax: it is on the always-tested list (length <= F, device side), as is every triangle of a mode-1 mesh.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int GRID_SCAN_BLOCK = 1024;
+constexpr int GRID_HDR_WORDS = 16;           // lo.xyz, h, inv_h, amax, mode (int), rmax (float bits); 64 bytes per mesh
+
+struct P2MGrid {                             // the caller's workspace, per-mesh strides in elements
+    uint32_t* hdr;                           // [B][GRID_HDR_WORDS]
+    int32_t* e;                              // [B][e_stride]: G^3 + 2 used
+    int32_t* tcell;                          // [B][t_stride]: F used
+    float* tris;                             // [B][s_stride]: F * 12 used (a.xyz, face index bits | b.xyz, 0 | c.xyz, 0)
+    size_t e_stride, t_stride, s_stride;
+    int G;
+};
+
+__device__ __forceinline__ int grid_cell(float x, float lo, float inv_h, int G, float& t) {
+    t = (x - lo) * inv_h;
+    return !(t >= 0.f) ? 0 : (t >= (float)G ? G - 1 : (int)t);            // NaN -> 0
+}
+
+__global__ __launch_bounds__(GRID_SCAN_BLOCK) void k_p2m_grid_bounds(const float* __restrict__ vts, int V, P2MGrid g) {
+    __shared__ float red[7][GRID_SCAN_BLOCK / 64];
+    const int b = blockIdx.x;
+    const float* v = vts + (size_t)b * V * 3;
+    float lo[3] = {3.4e38f, 3.4e38f, 3.4e38f}, hi[3] = {-3.4e38f, -3.4e38f, -3.4e38f}, bad = 0.f;
+    for (int i = threadIdx.x; i < V; i += GRID_SCAN_BLOCK)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float x = v[(size_t)i * 3 + c];
+            if (!(fabsf(x) <= 3.0e38f)) bad = 1.f;
+            lo[c] = fminf(lo[c], x);
+            hi[c] = fmaxf(hi[c], x);
+        }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            lo[c] = fminf(lo[c], __shfl_xor(lo[c], d, 64));
+            hi[c] = fmaxf(hi[c], __shfl_xor(hi[c], d, 64));
+        }
+        bad = fmaxf(bad, __shfl_xor(bad, d, 64));
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        for (int c = 0; c < 3; ++c) { red[c][w] = lo[c]; red[3 + c][w] = hi[c]; }
+        red[6][w] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < GRID_SCAN_BLOCK / 64; ++k) {
+            for (int c = 0; c < 3; ++c) { lo[c] = fminf(lo[c], red[c][k]); hi[c] = fmaxf(hi[c], red[3 + c][k]); }
+            bad = fmaxf(bad, red[6][k]);
+        }
+        float ext = 0.f, amax = 0.f;
+        for (int c = 0; c < 3; ++c) {
+            ext = fmaxf(ext, hi[c] - lo[c]);
+            amax = fmaxf(amax, fmaxf(fabsf(lo[c]), fabsf(hi[c])));
+        }
+        // grid only where the slack of the bound stays far below a cell: finite, extent in [1e-8, 1e8], not a speck far from the origin
+        const bool ok = bad == 0.f && ext >= 1e-8f && ext <= 1e8f && amax <= 1e8f && ext >= 1e-3f * amax;
+        const float h = ok ? ext / (float)g.G : 1.f;
+        uint32_t* o = g.hdr + (size_t)b * GRID_HDR_WORDS;
+        o[0] = __float_as_uint(ok ? lo[0] : 0.f);
+        o[1] = __float_as_uint(ok ? lo[1] : 0.f);
+        o[2] = __float_as_uint(ok ? lo[2] : 0.f);
+        o[3] = __float_as_uint(h);
+        o[4] = __float_as_uint(1.f / h);
+        o[5] = __float_as_uint(ok ? amax : 0.f);
+        o[6] = ok ? 0u : 1u;
+        // o[7] (rmax bits) stays at the 0 of the caller's clear; k_p2m_grid_count raises it
+    }
+}
+
+__device__ __forceinline__ void grid_load_tri(const float* __restrict__ vts, const int32_t* __restrict__ faces, int b, int V, int f,
+                                              f3& a0, f3& a1, f3& a2) {
+    const float* q0 = vts + ((size_t)b * V + faces[(size_t)f * 3]) * 3;
+    const float* q1 = vts + ((size_t)b * V + faces[(size_t)f * 3 + 1]) * 3;
+    const float* q2 = vts + ((size_t)b * V + faces[(size_t)f * 3 + 2]) * 3;
+    a0 = {q0[0], q0[1], q0[2]}; a1 = {q1[0], q1[1], q1[2]}; a2 = {q2[0], q2[1], q2[2]};
+}
+
+__global__ __launch_bounds__(LOSS_BLOCK) void k_p2m_grid_count(const float* __restrict__ vts, const int32_t* __restrict__ faces, int V,
+                                                                int F, P2MGrid g) {
+    const int b = blockIdx.y, f = blockIdx.x * LOSS_BLOCK + threadIdx.x;
+    uint32_t* hdr = g.hdr + (size_t)b * GRID_HDR_WORDS;
+    const int G = g.G, NC = G * G * G;
+    float r_binned = 0.f;
+    if (f < F) {
+        const f3 lo = {__uint_as_float(hdr[0]), __uint_as_float(hdr[1]), __uint_as_float(hdr[2])};
+        const float h = __uint_as_float(hdr[3]), inv_h = __uint_as_float(hdr[4]);
+        int cell = NC;
+        if (hdr[6] == 0u) {
+            f3 a0, a1, a2;
+            grid_load_tri(vts, faces, b, V, f, a0, a1, a2);
+            const f3 s = a0 + a1 + a2;
+            const f3 c = {s.x * (1.f / 3.f), s.y * (1.f / 3.f), s.z * (1.f / 3.f)};
+            const f3 e0 = a0 - c, e1 = a1 - c, e2 = a2 - c;
+            const float r = sqrtf(fmaxf(dot(e0, e0), fmaxf(dot(e1, e1), dot(e2, e2))));
+            if (r <= 2.f * h) {                                            // false for NaN: cannot happen in mode 0, harmless if it did
+                float t;
+                const int cx = grid_cell(c.x, lo.x, inv_h, G, t), cy = grid_cell(c.y, lo.y, inv_h, G, t),
+                          cz = grid_cell(c.z, lo.z, inv_h, G, t);
+                cell = (cz * G + cy) * G + cx;
+                r_binned = r;
+            }
+        }
+        g.tcell[(size_t)b * g.t_stride + f] = cell;
+        atomicAdd(g.e + (size_t)b * g.e_stride + cell + 1, 1);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) r_binned = fmaxf(r_binned, __shfl_xor(r_binned, d, 64));
+    if ((threadIdx.x & 63) == 0 && r_binned > 0.f) atomicMax(hdr + 7, __float_as_uint(r_binned));   // r >= 0: bits order as values
+}
+
+// exclusive scan in place of e[1 .. n] (n = G^3 + 1 counts), one block per mesh, tiles of GRID_SCAN_BLOCK; e[0] stays 0
+__global__ __launch_bounds__(GRID_SCAN_BLOCK) void k_p2m_grid_scan(P2MGrid g) {
+    __shared__ int wsum[GRID_SCAN_BLOCK / 64];
+    int32_t* e = g.e + (size_t)blockIdx.x * g.e_stride + 1;
+    const int n = g.G * g.G * g.G + 1, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int carry = 0;
+    for (int base = 0; base < n; base += GRID_SCAN_BLOCK) {
+        const int i = base + threadIdx.x;
+        const int v = i < n ? e[i] : 0;
+        int x = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int y = __shfl_up(x, d, 64);
+            if (lane >= d) x += y;
+        }
+        if (lane == 63) wsum[w] = x;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < GRID_SCAN_BLOCK / 64; ++k) {
+            const int s = wsum[k];
+            if (k < w) before += s;
+            total += s;
+        }
+        if (i < n) e[i] = carry + before + x - v;
+        carry += total;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(LOSS_BLOCK) void k_p2m_grid_fill(const float* __restrict__ vts, const int32_t* __restrict__ faces, int V,
+                                                               int F, P2MGrid g) {
+    const int b = blockIdx.y, f = blockIdx.x * LOSS_BLOCK + threadIdx.x;
+    if (f >= F) return;
+    const int cell = g.tcell[(size_t)b * g.t_stride + f];
+    const int slot = atomicAdd(g.e + (size_t)b * g.e_stride + cell + 1, 1);
+    if (slot < 0 || slot >= F) return;                                     // cannot happen: the counts of this same tcell sum to F
+    f3 a0, a1, a2;
+    grid_load_tri(vts, faces, b, V, f, a0, a1, a2);
+    float4* o = reinterpret_cast<float4*>(g.tris + (size_t)b * g.s_stride + (size_t)slot * 12);   // 48-byte records, 16-byte aligned
+    o[0] = make_float4(a0.x, a0.y, a0.z, __int_as_float(f));
+    o[1] = make_float4(a1.x, a1.y, a1.z, 0.f);
+    o[2] = make_float4(a2.x, a2.y, a2.z, 0.f);
+}
+
+__global__ __launch_bounds__(LOSS_BLOCK) void k_p2m_grid_query(const float* __restrict__ pts, int P, int F, P2MGrid g,
+                                                                float* __restrict__ dist, int32_t* __restrict__ face,
+                                                                int32_t* __restrict__ kind) {
+    const int b = blockIdx.y, i = blockIdx.x * LOSS_BLOCK + threadIdx.x;
+    if (i >= P) return;
+    const uint32_t* hdr = g.hdr + (size_t)b * GRID_HDR_WORDS;
+    const int32_t* e = g.e + (size_t)b * g.e_stride;
+    const float* tris = g.tris + (size_t)b * g.s_stride;
+    const int G = g.G, NC = G * G * G;
+    const float* pp = pts + ((size_t)b * P + i) * 3;
+    const f3 p = {pp[0], pp[1], pp[2]};
+    float best = 3.4e38f;
+    int best_f = 0, best_k = 0;
+    auto test = [&](int s0, int s1) {
+        s0 = max(s0, 0); s1 = min(s1, F);                                  // the slots stay inside the list whatever e holds
+        for (int s = s0; s < s1; ++s) {
+            const float4* r = reinterpret_cast<const float4*>(tris + (size_t)s * 12);
+            const float4 r0 = r[0], r1 = r[1], r2 = r[2];
+            const int f = __float_as_int(r0.w);
+            int k;
+            const float d2 = tri_dist2(p, f3{r0.x, r0.y, r0.z}, f3{r1.x, r1.y, r1.z}, f3{r2.x, r2.y, r2.z}, k);
+            if (d2 < best || (d2 == best && f < best_f)) { best = d2; best_f = f; best_k = k; }
+        }
+    };
+    test(e[NC], e[NC + 1]);                                                // the always-tested list
+    if (hdr[6] == 0u) {
+        const f3 lo = {__uint_as_float(hdr[0]), __uint_as_float(hdr[1]), __uint_as_float(hdr[2])};
+        const float h = __uint_as_float(hdr[3]), inv_h = __uint_as_float(hdr[4]), amax = __uint_as_float(hdr[5]);
+        const float rmax = __uint_as_float(hdr[7]) * (1.f + 1e-5f) + 1e-6f * h;
+        float tx, ty, tz;
+        const int cx = grid_cell(p.x, lo.x, inv_h, G, tx), cy = grid_cell(p.y, lo.y, inv_h, G, ty), cz = grid_cell(p.z, lo.z, inv_h, G, tz);
+        const float pmax = fmaxf(fabsf(p.x), fmaxf(fabsf(p.y), fabsf(p.z)));
+        const bool finite = fabsf(p.x) <= 3.0e38f && fabsf(p.y) <= 3.0e38f && fabsf(p.z) <= 3.0e38f;
+        const float tslack = 1e-6f * ((float)(G + 1) + fmaxf(fabsf(tx), fmaxf(fabsf(ty), fabsf(tz))));
+        const float dslack = rmax + 4e-6f * (amax + pmax);
+        const int kmax = max(2, G / 4);
+        bool walked_out = false;
+        for (int k = 0;; ++k) {                                            // ends at k = kmax + 1 <= G at the latest
+            if (k > kmax) { walked_out = true; break; }
+            const int x0 = max(cx - k, 0), x1 = min(cx + k, G - 1), y0 = max(cy - k, 0), y1 = min(cy + k, G - 1);
+            const int z0 = max(cz - k, 0), z1 = min(cz + k, G - 1);
+            for (int z = z0; z <= z1; ++z)
+                for (int y = y0; y <= y1; ++y) {
+                    const int row = (z * G + y) * G;
+                    if (abs(z - cz) == k || abs(y - cy) == k) test(e[row + x0], e[row + x1 + 1]);
+                    else {
+                        if (cx - k >= 0) test(e[row + cx - k], e[row + cx - k + 1]);
+                        if (cx + k <= G - 1) test(e[row + cx + k], e[row + cx + k + 1]);
+                    }
+                }
+            // distance (in cells) to the nearest face of the visited block that is not on the grid border
+            float dt = 3.4e38f;
+            if (x0 > 0) dt = fminf(dt, tx - (float)x0);
+            if (x1 < G - 1) dt = fminf(dt, (float)(x1 + 1) - tx);
+            if (y0 > 0) dt = fminf(dt, ty - (float)y0);
+            if (y1 < G - 1) dt = fminf(dt, (float)(y1 + 1) - ty);
+            if (z0 > 0) dt = fminf(dt, tz - (float)z0);
+            if (z1 < G - 1) dt = fminf(dt, (float)(z1 + 1) - tz);
+            if (dt == 3.4e38f) break;                                      // every cell visited
+            const float bound = (dt - tslack) * h * (1.f - 1e-6f) - dslack;
+            if (finite && bound > 0.f && bound * bound * (1.f - 1e-5f) > best) break;
+        }
+        // not excluded after kmax shells (farther from the mesh than about a quarter of its extent, or not finite): the whole
+        // list, linearly.  Re-testing a triangle changes nothing; such lanes of a wave scan in lockstep, reading the same slots.
+        if (walked_out) test(0, F);
+    }
+    dist[(size_t)b * P + i] = best;
+    face[(size_t)b * P + i] = best_f;
+    kind[(size_t)b * P + i] = best_k;
+}
+
 }  // namespace
 
 void launch_point_to_mesh(const float* pts, const float* vts, const int32_t* faces, int B, int P, int V, int F, float* dist,
@@ -619,6 +891,62 @@ void launch_point_to_mesh_bwd(const float* pts, const float* vts, const int32_t*
     prof_mark_begin(PROF_P2M_BWD_VERTEX, 0.0, s);
     hipLaunchKernelGGL(k_point_to_mesh_bwd_vertex, dim3((V + LOSS_BLOCK - 1) / LOSS_BLOCK, B), dim3(LOSS_BLOCK), 0, s, rec, P, V, dvts);
     prof_mark_end(s);
+}
+
+// G = round(sqrt(F / 16)) in [1, 64]: about 16 triangles per occupied cell of a closed surface (which fills ~6 G^2 of the G^3
+// cells); a function of F alone and non-decreasing in it, so that the workspace size is too.
+int p2m_grid_res(int F) {
+    int G = 1;
+    while (G < 64 && (long)(2 * G + 1) * (2 * G + 1) * 4 <= (long)F) ++G;          // (G + 1/2)^2 * 16 <= F
+    return G;
+}
+
+static size_t up16(size_t bytes) { return (bytes + 15) / 16 * 16; }
+
+static size_t p2m_grid_layout(int B, int F, P2MGrid* g, void* ws, size_t* clear_bytes) {
+    const int G = p2m_grid_res(F);
+    const size_t hdr = (size_t)B * GRID_HDR_WORDS * 4, e1 = up16(((size_t)G * G * G + 2) * 4), t1 = up16((size_t)F * 4),
+                 s1 = (size_t)F * 48;
+    if (g) {
+        char* base = static_cast<char*>(ws);
+        g->G = G;
+        g->hdr = reinterpret_cast<uint32_t*>(base);
+        g->e = reinterpret_cast<int32_t*>(base + hdr);
+        g->tcell = reinterpret_cast<int32_t*>(base + hdr + B * e1);
+        g->tris = reinterpret_cast<float*>(base + hdr + B * (e1 + t1));
+        g->e_stride = e1 / 4; g->t_stride = t1 / 4; g->s_stride = s1 / 4;
+    }
+    if (clear_bytes) *clear_bytes = hdr + B * e1;                           // headers (rmax) and cell counts start at zero
+    return hdr + B * (e1 + t1 + s1);
+}
+
+size_t point_to_mesh_grid_bytes(int B, int F) { return p2m_grid_layout(B, F, nullptr, nullptr, nullptr); }
+
+hipError_t launch_point_to_mesh_grid(const float* pts, const float* vts, const int32_t* faces, int B, int P, int V, int F, float* dist,
+                                     int32_t* face, int32_t* kind, void* ws, hipStream_t s) {
+    P2MGrid g;
+    size_t clear = 0;
+    p2m_grid_layout(B, F, &g, ws, &clear);
+    const hipError_t rc = hipMemsetAsync(ws, 0, clear, s);
+    if (rc != hipSuccess) return rc;
+    const dim3 tri_grid((F + LOSS_BLOCK - 1) / LOSS_BLOCK, B);
+    prof_mark_begin(PROF_P2M_GRID_BOUNDS, 0.0, s);
+    hipLaunchKernelGGL(k_p2m_grid_bounds, dim3(B), dim3(GRID_SCAN_BLOCK), 0, s, vts, V, g);
+    prof_mark_end(s);
+    prof_mark_begin(PROF_P2M_GRID_COUNT, 0.0, s);
+    hipLaunchKernelGGL(k_p2m_grid_count, tri_grid, dim3(LOSS_BLOCK), 0, s, vts, faces, V, F, g);
+    prof_mark_end(s);
+    prof_mark_begin(PROF_P2M_GRID_SCAN, 0.0, s);
+    hipLaunchKernelGGL(k_p2m_grid_scan, dim3(B), dim3(GRID_SCAN_BLOCK), 0, s, g);
+    prof_mark_end(s);
+    prof_mark_begin(PROF_P2M_GRID_FILL, 0.0, s);
+    hipLaunchKernelGGL(k_p2m_grid_fill, tri_grid, dim3(LOSS_BLOCK), 0, s, vts, faces, V, F, g);
+    prof_mark_end(s);
+    prof_mark_begin(PROF_P2M_GRID_QUERY, 0.0, s);
+    hipLaunchKernelGGL(k_p2m_grid_query, dim3((P + LOSS_BLOCK - 1) / LOSS_BLOCK, B), dim3(LOSS_BLOCK), 0, s, pts, P, F, g, dist, face,
+                       kind);
+    prof_mark_end(s);
+    return hipSuccess;
 }
 
 }  // namespace icn

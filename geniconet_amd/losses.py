@@ -225,11 +225,20 @@ class Point2Mesh_Loss(torch.nn.Module):
     point plus P * V integer compares per mesh.  Measured on an MI355X at I5 / batch 36 (10 242 points against 20 480 triangles
     per mesh, HIP events, median of 10, profiles/point_to_mesh_bwd.txt): k_point_to_mesh 15.1 ms, the two backward kernels
     1.05 ms together, the whole term forward + backward 16.5 ms, beside a training step of 6.3 ms (python bench.py, same
-    batch) -- 2.6 training steps' worth per evaluation, nearly all of it the forward search."""
+    batch) -- 2.6 training steps' worth per evaluation, nearly all of it the forward search.
+    search='grid' replaces that search by an exact grid-accelerated one (icn_point_to_mesh_grid; same value and gradients bit for
+    bit).  Same machine and sizes, both searches alternating in one process (profiles/point_to_mesh_grid.txt): with the output
+    near its target (rms distance 0.01) the forward takes 0.46 ms (index build 0.14 + query 0.33) against 14.6 ms and the whole
+    term 1.8 ms against 15.9 ms, a third of a training step; against a different shape (rms 0.06) 2.3 ms against 15.4 ms, the term
+    3.7 ms.  Far from the surface (Gaussian cloud, rms 0.75) it is 1.8 x SLOWER than 'brute' (28.2 against 15.5 ms): an untrained
+    network's output may be such a cloud, so start with 'brute' or a point-to-point term if the output is nowhere near the surface."""
 
-    def __init__(self, subdivisions):
+    def __init__(self, subdivisions, search='brute'):
         super().__init__()
+        from .metrics import _check_search
+        _check_search(search)
         self.subdivisions = subdivisions
+        self.search = search
         self.last_loss_total = 0
 
     def forward(self, inputs, ref_vertices, ref_faces):
@@ -237,7 +246,8 @@ class Point2Mesh_Loss(torch.nn.Module):
         n = 2 ** self.subdivisions
         if inputs.dim() != 4 or tuple(inputs.shape[1:]) != (3, 5 * n, 2 * n):
             raise ValueError('Point2Mesh_Loss: expected inputs (B, 3, %d, %d), got %s' % (5 * n, 2 * n, tuple(inputs.shape)))
-        dist, _, _ = point_to_mesh_distance(grid_to_vertices(inputs, self.subdivisions), ref_vertices, ref_faces)
+        dist, _, _ = point_to_mesh_distance(grid_to_vertices(inputs, self.subdivisions), ref_vertices, ref_faces,
+                                            search=self.search)
         loss = dist.mean()
         self.last_loss_total = loss.detach()
         return loss

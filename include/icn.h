@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ICN_ABI_VERSION 8
+#define ICN_ABI_VERSION 9
 
 #define ICN_CORNER_ZEROS 0
 #define ICN_CORNER_AVERAGE 1
@@ -224,6 +224,22 @@ int icn_point_to_mesh_bwd(const float* points, const float* vertices, const int3
                           const float* ddist, int B, int P, int V, int F, float* dpoints, float* dvertices, void* ws, size_t ws_bytes,
                           void* stream);
 
+/* icn_point_to_mesh through a spatial index (ABI 9): the same three outputs, bit for bit (the same point-triangle routine and the
+ * same lowest-face tie rule), so icn_point_to_mesh_bwd takes them unchanged.  Per mesh the triangles are binned once by centroid into
+ * a uniform grid of G^3 cells over the bounding cube (G = round(sqrt(F / 16)) in [1, 64], a function of F alone); a point visits
+ * shells of cells around its own until a conservative fp32 bound excludes everything not yet visited.  Near the surface that is
+ * ~100 instead of F triangle tests per point; a point farther away than about a quarter of the mesh's extent, or a NaN / infinite one, gives up after max(2, G / 4) shells and tests all F,
+ * a mesh with non-finite vertices or zero extent is searched linearly, and an over-long triangle is tested for every point rather
+ * than binned.  Prefer icn_point_to_mesh when most points are farther from the mesh than about its extent.
+ * ws: icn_point_to_mesh_grid_workspace_bytes(B, P, V, F) bytes (host-only query; 0 for sizes the call would reject; depends on B and
+ * F only, 64 + 4 (G^3 + 2) + 52 F bytes per mesh rounded up to 16s), 16-byte aligned, owned by the caller; contents need not survive
+ * the call.  The library allocates nothing and never synchronises: one hipMemsetAsync and five launches on `stream`, legal inside
+ * a stream capture.  Integer atomics only; outputs are bit-identical run to run.  B <= 65535 per call.  0 on success, negative
+ * with icn_last_error() otherwise (arguments are checked before any device call). */
+size_t icn_point_to_mesh_grid_workspace_bytes(int B, int P, int V, int F);
+int icn_point_to_mesh_grid(const float* points, const float* vertices, const int32_t* faces, int B, int P, int V, int F, float* dist2,
+                           int32_t* face, int32_t* kind, void* ws, size_t ws_bytes, void* stream);
+
 /* Adam step (reference run.py:253 `optimizer.step()` on the optimiser of run.py:446, torch.optim.Adam without amsgrad /
  * maximize) over `count` fp32 tensors, one launch per 96 tensors that share a step count (normally: one launch).  The four pointer arrays and numel / step_size / bc2_sqrt
  * are HOST arrays of length count; the pointers in them are device pointers (param, grad, exp_avg, exp_avg_sq of tensor i,
@@ -279,7 +295,7 @@ long icn_table_upconv_bwd(int r_in, int corner_mode, int32_t* idx, float* coef, 
  * does not exist for this (r_in, stride): P_out % 16 != 0 or a union that does not fit. */
 long icn_table_wgrad7(int r_in, int stride, int corner_mode, int32_t* rows, size_t cap_rows, uint16_t* pos, size_t cap_pos, int* meta);
 
-/* Optional diagnostics: HIP-event timing of every MFMA kernel launch (and, ABI 8, of k_point_to_mesh and its two backward kernels,
+/* Optional diagnostics: HIP-event timing of every MFMA kernel launch (and, ABI 8, of k_point_to_mesh and its two backward kernels, ABI 9, of the five k_p2m_grid_* kernels,
  * with total_flops 0) between start and stop, on the launch stream.  `stop` synchronises the device and returns the number of entries written (one per kernel that ran).
  * total_flops counts what a launch multiplies: 2*7*Cin*Cout*B*P_out per pass of an ordinary convolution (= its algorithmic
  * FLOPs; the small virtual-row launch of a stride-1 bwd-data adds time, not FLOPs); the composite icn_upconv_* launches execute
