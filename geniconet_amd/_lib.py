@@ -58,6 +58,10 @@ SIGNATURES = {
     'icn_p2p_loss_fwd': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_float] * 3 + [ctypes.c_int] + [_c_float_p] * 2 + [ctypes.c_void_p]),
     'icn_p2p_loss_bwd_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 2),
     'icn_p2p_loss_bwd': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_float] * 3 + [ctypes.c_int] + [_c_float_p] * 2 + [ctypes.c_void_p]),
+    'icn_mesh_reg_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 2),
+    'icn_mesh_reg_fwd': (ctypes.c_int, [_c_float_p] + [ctypes.c_int] * 2 + [ctypes.c_float] * 4 + [_c_float_p] * 2 + [ctypes.c_void_p]),
+    'icn_mesh_reg_bwd_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 2),
+    'icn_mesh_reg_bwd': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_float] * 4 + [_c_float_p] * 2 + [ctypes.c_void_p]),
     'icn_kld_workspace_floats': (ctypes.c_size_t, [ctypes.c_size_t]),
     'icn_kld_fwd': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_size_t] + [_c_float_p] * 2 + [ctypes.c_void_p]),
     'icn_kld_bwd': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_size_t] + [_c_float_p] * 2 + [ctypes.c_void_p]),
@@ -85,6 +89,7 @@ SIGNATURES = {
     'icn_table_upsample': (ctypes.c_long, [ctypes.c_int] * 3 + [_i32p, _f32p, ctypes.c_size_t, _intp]),
     'icn_table_upsample_pairs': (ctypes.c_long, [ctypes.c_int, _i32p, ctypes.c_size_t]),
     'icn_table_faces': (ctypes.c_long, [ctypes.c_int, _i32p, ctypes.c_size_t]),
+    'icn_table_vertex_stencils': (ctypes.c_long, [ctypes.c_int, _i32p, ctypes.c_size_t]),
     'icn_table_upconv_bwd': (ctypes.c_long, [ctypes.c_int] * 2 + [_i32p, _f32p, ctypes.c_size_t, _intp]),
     'icn_table_upconv': (ctypes.c_long, [ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_size_t, _f32p, ctypes.c_size_t, _intp]),
 }
@@ -269,6 +274,17 @@ def table_faces(r):
     out = np.empty(n, dtype=np.int32)
     L.icn_table_faces(r, out.ctypes.data_as(_i32p), n)
     return out.reshape(-1, 3)
+
+
+def table_vertex_stencils(r):
+    """Edge stencils of the mesh regularisers (icn_table_vertex_stencils): int32 (V, 6, 3) of (p, q, x), -1 padded."""
+    L = lib()
+    n = L.icn_table_vertex_stencils(r, None, 0)
+    if n < 0:
+        check(-1, 'icn_table_vertex_stencils')
+    out = np.empty(n, dtype=np.int32)
+    L.icn_table_vertex_stencils(r, out.ctypes.data_as(_i32p), n)
+    return out.reshape(-1, 6, 3)
 
 
 def table_upsample_pairs(r_in):

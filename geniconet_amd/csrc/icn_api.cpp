@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -301,6 +302,20 @@ const int32_t* vertex_faces(int r) {
     std::vector<int32_t> vf;
     icn::build_vertex_faces(r, vf);
     return g_vf.emplace(key, upload(vf)).first->second;
+}
+
+std::map<std::pair<int, int>, int32_t*> g_vs;                  // (device, r) -> edge stencil table of the mesh regularisers
+
+const int32_t* vertex_stencils(int r) {
+    int dev = 0;
+    ICN_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto key = std::make_pair(dev, r);
+    auto it = g_vs.find(key);
+    if (it != g_vs.end()) return it->second;
+    std::vector<int32_t> vs;
+    icn::build_vertex_stencils(r, vs);
+    return g_vs.emplace(key, upload(vs)).first->second;
 }
 
 UpTables make_up_tables(int r_in, int mode) {
@@ -1255,6 +1270,53 @@ int icn_p2p_loss_bwd(const float* grid, const float* target, const float* upstre
     }
 }
 
+// ---- mesh regularisers of the surface loss ------------------------------------------------------------------------------
+namespace {
+void check_mesh_reg(const char* who, int B, int r, float edge_length) {
+    const std::string w(who);
+    if (B < 1 || r < 0 || r > 10) throw std::invalid_argument(w + ": bad B / subdivisions");
+    if ((size_t)B * (icn::pixels(r) + 2) >= (size_t)1 << 31) throw std::invalid_argument(w + ": B * vertices exceeds int32");
+    if (!(edge_length >= 0.f) || !std::isfinite(edge_length)) throw std::invalid_argument(w + ": edge_length must be finite and >= 0");
+}
+}  // namespace
+
+size_t icn_mesh_reg_workspace_floats(int B, int r) {
+    return (B < 1 || r < 0 || r > 10) ? 0 : (size_t)3 * icn::p2p_loss_blocks(B, icn::pixels(r));
+}
+
+int icn_mesh_reg_fwd(const float* grid, int B, int r, float f_edge, float f_ncons, float f_smooth, float edge_length, float* terms,
+                     float* ws, void* stream) {
+    try {
+        if (!grid || !terms || !ws) throw std::invalid_argument("icn_mesh_reg_fwd: null pointer");
+        check_mesh_reg("icn_mesh_reg_fwd", B, r, edge_length);
+        icn::launch_mesh_reg_fwd(grid, vertex_stencils(r), ws, terms, B, icn::pixels(r), 1 << r, f_edge, f_ncons, f_smooth, edge_length,
+                                 static_cast<hipStream_t>(stream));
+        ICN_HIP(hipGetLastError());
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(e.what());
+    }
+}
+
+size_t icn_mesh_reg_bwd_workspace_floats(int B, int r) {
+    return (B < 1 || r < 0 || r > 10) ? 0 : (size_t)3 * B * (icn::pixels(r) + 2);
+}
+
+int icn_mesh_reg_bwd(const float* grid, const float* upstream, int B, int r, float f_edge, float f_ncons, float f_smooth,
+                     float edge_length, float* dgrid, float* ws, void* stream) {
+    try {
+        if (!grid || !upstream || !dgrid) throw std::invalid_argument("icn_mesh_reg_bwd: null pointer");
+        check_mesh_reg("icn_mesh_reg_bwd", B, r, edge_length);
+        if (f_smooth != 0.f && !ws) throw std::invalid_argument("icn_mesh_reg_bwd: null pointer (workspace needed for the smoothness term)");
+        icn::launch_mesh_reg_bwd(grid, vertex_stencils(r), upstream, f_edge, f_ncons, f_smooth, edge_length, dgrid, ws, B, icn::pixels(r),
+                                 1 << r, static_cast<hipStream_t>(stream));
+        ICN_HIP(hipGetLastError());
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(e.what());
+    }
+}
+
 // ---- KL term and reparameterisation of the VAE -----------------------------------------------------------------------
 size_t icn_kld_workspace_floats(size_t n) { return n < 1 ? 0 : (size_t)icn::kld_blocks(n); }
 
@@ -1730,6 +1792,17 @@ long icn_table_faces(int r, int32_t* out, size_t cap) {
     try {
         std::vector<int32_t> v;
         icn::build_faces(r, v);
+        if (out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(int32_t));
+        return (long)v.size();
+    } catch (const std::exception& e) {
+        return fail(e.what());
+    }
+}
+
+long icn_table_vertex_stencils(int r, int32_t* out, size_t cap) {
+    try {
+        std::vector<int32_t> v;
+        icn::build_vertex_stencils(r, v);
         if (out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(int32_t));
         return (long)v.size();
     } catch (const std::exception& e) {

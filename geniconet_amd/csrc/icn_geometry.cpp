@@ -611,4 +611,31 @@ void build_vertex_faces(int r, std::vector<int32_t>& vf) {
         }
 }
 
+void build_vertex_stencils(int r, std::vector<int32_t>& vs) {
+    std::vector<int32_t> vf;
+    build_vertex_faces(r, vf);
+    const int V = pixels(r) + 2;
+    vs.assign((size_t)V * 18, -1);
+    // q of the incident face of vertex i whose p is `p` (the face holding the directed edge i -> p); -1 if there is none
+    auto across = [&](int i, int p) {
+        for (int f = 0; f < 6; ++f)
+            if (vf[((size_t)i * 6 + f) * 2] == p) return vf[((size_t)i * 6 + f) * 2 + 1];
+        return (int32_t)-1;
+    };
+    for (int i = 0; i < V; ++i) {
+        int k = 0;
+        while (k < 6 && vf[((size_t)i * 6 + k) * 2] >= 0) ++k;
+        int32_t p = vf[(size_t)i * 12];                                    // start at the vertex's first face in face order
+        for (int f = 0; f < k; ++f) {
+            const int32_t q = across(i, p);
+            const int32_t x = q >= 0 ? across(q, p) : -1;                  // (q, p, x) holds the directed edge q -> p
+            if (q < 0 || x < 0) throw std::logic_error("build_vertex_stencils: the mesh is not closed");
+            int32_t* o = &vs[((size_t)i * 6 + f) * 3];
+            o[0] = p; o[1] = q; o[2] = x;
+            p = q;
+        }
+        if (p != vf[(size_t)i * 12]) throw std::logic_error("build_vertex_stencils: the faces of a vertex do not form one cycle");
+    }
+}
+
 }  // namespace icn

@@ -154,4 +154,10 @@ void build_faces(int r, std::vector<int32_t>& faces);
 // vertices have 5 faces).  On the closed mesh the p entries of a vertex are exactly its one-ring, each neighbour once.
 void build_vertex_faces(int r, std::vector<int32_t>& vf);
 
+// Edge stencils of every vertex, for the mesh regularisers (icn_mesh_reg_*): vs[(i * 6 + f) * 3 + {0, 1, 2}] = (p, q, x), -1 padded
+// for the missing sixth slot of the 12 five-valent vertices.  (i, p, q) is a face in its orientation rotated so that i comes first
+// (as in build_vertex_faces); the slots are in CYCLIC order around i: q of slot f is p of slot f + 1, wrapping at the valence, so the
+// two faces at edge (i, p_f) are slots f and f - 1.  x is the vertex opposite i across edge (p, q): (q, p, x) is a face.
+void build_vertex_stencils(int r, std::vector<int32_t>& vs);
+
 }  // namespace icn

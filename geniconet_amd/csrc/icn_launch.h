@@ -201,6 +201,12 @@ void launch_p2p_loss_bwd_pos(const float* grid, const float* target, const float
 // all three terms (aux = 6 * B * (P + 2) floats; unused, may be null, when f_nor = f_lap = 0)
 void launch_p2p_loss_bwd(const float* grid, const float* target, const int32_t* vf, const float* upstream, float f_pos, float f_nor,
                          float f_lap, int lap_mode, float* dgrid, float* aux, int B, int P, int n, hipStream_t s);
+// ---- mesh regularisers (icn_loss.hip): terms[4] = {edge, normal consistency, smoothness, weighted total}; vs = edge stencil table;
+// partial = 3 * p2p_loss_blocks floats; aux = 3 * B * (P + 2) floats, only touched when f_smooth != 0
+void launch_mesh_reg_fwd(const float* grid, const int32_t* vs, float* partial, float* terms, int B, int P, int n, float f_edge,
+                         float f_ncons, float f_smooth, float edge_length, hipStream_t s);
+void launch_mesh_reg_bwd(const float* grid, const int32_t* vs, const float* upstream, float f_edge, float f_ncons, float f_smooth,
+                         float edge_length, float* dgrid, float* aux, int B, int P, int n, hipStream_t s);
 
 // ---- KL term + reparameterisation of the VAE (icn_loss.hip); partial = kld_blocks(n) floats
 int kld_blocks(size_t n);

@@ -128,8 +128,9 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_p2p_fwd(const float* __restrict_
 }
 
 // terms from the per-block partials: one block, lanes stride over the partials in double, fixed tree
-__global__ __launch_bounds__(LOSS_BLOCK) void k_p2p_finalize(const float* __restrict__ partial, int nblocks, double count_vec,
-                                                              double count_vtx, float f_pos, float f_nor, float f_lap,
+// (also the finalize of the mesh regularisers below: count0 / count1 / count2 divide the three sums)
+__global__ __launch_bounds__(LOSS_BLOCK) void k_p2p_finalize(const float* __restrict__ partial, int nblocks, double count0,
+                                                              double count1, double count2, float f_pos, float f_nor, float f_lap,
                                                               float* __restrict__ terms) {
     __shared__ double red[3][LOSS_BLOCK];
     double s[3] = {0.0, 0.0, 0.0};
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_p2p_finalize(const float* __rest
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        const float l_pos = (float)(red[0][0] / count_vec), l_nor = (float)(red[1][0] / count_vtx), l_lap = (float)(red[2][0] / count_vec);
+        const float l_pos = (float)(red[0][0] / count0), l_nor = (float)(red[1][0] / count1), l_lap = (float)(red[2][0] / count2);
         terms[0] = l_pos;
         terms[1] = l_nor;
         terms[2] = l_lap;
@@ -280,7 +281,8 @@ void launch_p2p_loss_fwd(const float* grid, const float* target, const int32_t* 
     const int nb = p2p_loss_blocks(B, P);
     hipLaunchKernelGGL(k_p2p_fwd, dim3(nb), dim3(LOSS_BLOCK), 0, s, grid, target, vf, partial, B, P, n, lap_mode);
     const double nv = (double)B * (P + 2);
-    hipLaunchKernelGGL(k_p2p_finalize, dim3(1), dim3(LOSS_BLOCK), 0, s, partial, nb, nv * 3.0, nv, f_pos, f_nor, f_lap, terms);
+    hipLaunchKernelGGL(k_p2p_finalize, dim3(1), dim3(LOSS_BLOCK), 0, s, partial, nb, nv * 3.0, nv, nv * 3.0, f_pos, f_nor,
+                       f_lap, terms);
 }
 
 void launch_p2p_loss_bwd_pos(const float* grid, const float* target, const float* upstream, float f_pos, float* dgrid, int B, int P,
@@ -300,6 +302,227 @@ void launch_p2p_loss_bwd(const float* grid, const float* target, const int32_t* 
                        B, P, n, lap_mode);
     hipLaunchKernelGGL(k_p2p_bwd, dim3((unsigned)((tp + LOSS_BLOCK - 1) / LOSS_BLOCK)), dim3(LOSS_BLOCK), 0, s, grid, target, vf, aux,
                        upstream, (float)(2.0 * f_pos / (3.0 * nv)), (float)(2.0 * f_lap / (3.0 * nv)), (float)(f_nor / nv), dgrid, B, P, n);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Mesh regularisers of the surface loss (not in the reference): edge length, normal consistency between adjacent faces, uniform
+// Laplacian smoothness, on the static icosahedral topology.  Same input as the point-to-point loss above (grid (B, P, 3), V = P + 2
+// vertices through vertex()); E = 3 P undirected edges.  Topology: the edge stencil table of icn_geometry.h, vs[(i * 6 + f) * 3] =
+// (p, q, x) in cyclic order around i -- the kernels read p and x, q of slot f is p of slot f + 1.
+//   terms[0] = T_e = 1 / (B E)   sum_b sum_edges (|v_i - v_j| - L)^2          (L = 0: |v_i - v_j|^2, no square root)
+//   terms[1] = T_n = 1 / (B E)   sum_b sum_edges 1/2 |n^_F0 - n^_F1|^2        n_F = (v_b - v_a) x (v_c - v_a), n^ = n / max(|n|, 1e-12)
+//   terms[2] = T_s = 1 / (3 B V) sum_b sum_i |mean(ring_i) - v_i|^2           terms[3] = f_edge T_e + f_ncons T_n + f_smooth T_s
+// Forward, one thread per (sample, vertex i): every edge at i is a spoke (i, p_f) with the faces of slots f and f - 1 on its sides, and
+// every edge of the mesh is a spoke of both of its ends, so each thread adds HALF of its spokes' edge and normal terms: the 1-ring is
+// all it reads.  Sums as above: fixed tree per block, then one block in double.
+//
+// Backward (d terms[3] / d grid), gather form, one thread per (sample, pixel j); with d = v_j - v_p over the ring of j:
+//   edge   : 2 f_edge / (B E) sum_p (1 - L / |d|) d;  L = 0: 2 d;  L > 0 and |d|^2 <= 1e-24: that edge adds nothing
+//   smooth : u_i = mean(ring_i) - v_i:  2 f_smooth / (3 B V) (sum_{i in ring(j)} u_i / k_i - u_j)   (ring symmetric; k = valence).
+//            u_i / k_i of a neighbour needs the neighbour's own ring, so k_mreg_bwd_prep stores it per vertex (3 floats) first.
+//   normal : S = sum_edges 1/2 |n^_F - n^_G|^2.  For a face F with neighbours G1..G3 across its edges, g_F = dS / dn^_F = sum_G (n^_F - n^_G),
+//            H_F = dS / dn_F = (g_F - (g_F . n^_F) n^_F) / |n_F|, or 0 where the clamp is active (|n_F| <= 1e-12; a clamped face still
+//            enters its neighbours' g as the constant n_F / 1e-12).  With n_F = (v_p - v_j) x (v_q - v_j), dS / dv_j = sum over the faces
+//            (j, p, q) at j of H_F x (v_q - v_p); times f_ncons / (B E).  RECOMPUTED per vertex, no workspace: the neighbours of the face in
+//            slot f are slots f - 1 and f + 1 and, across (p_f, q_f), the face (q_f, p_f, x_f) -- the 1-ring and the six x suffice.
+//   vertex -> grid as above: a pole's gradient goes to its 5 corner pixels, a fifth each.  Every element of dgrid is written once.
+// A term whose factor is 0 is skipped in the backward (no loads of x without the normal term, no prep pass without smoothness).
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr float MREG_EPS = 1e-12f;
+
+__device__ __forceinline__ f3 scaled(f3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
+
+// n / max(|n|, 1e-12); len = |n|
+__device__ __forceinline__ f3 unit_clamped(f3 nrm, float& len) {
+    len = sqrtf(dot(nrm, nrm));
+    return scaled(nrm, 1.f / fmaxf(len, MREG_EPS));
+}
+
+// v, the ring p_0 .. p_{k-1} of vertex i (slots beyond the valence hold v) and the valence
+__device__ __forceinline__ int load_ring(const float* __restrict__ g, const int32_t* __restrict__ vs, int b, int i, int P, int n, f3& v,
+                                         f3 (&pv)[6]) {
+    v = vertex(g, b, i, P, n);
+    int k = 0;
+#pragma unroll
+    for (int f = 0; f < 6; ++f) {
+        const int p = vs[((size_t)i * 6 + f) * 3];
+        pv[f] = v;
+        if (p >= 0) { pv[f] = vertex(g, b, p, P, n); ++k; }
+    }
+    return k;
+}
+
+__global__ __launch_bounds__(LOSS_BLOCK) void k_mreg_fwd(const float* __restrict__ g, const int32_t* __restrict__ vs,
+                                                          float* __restrict__ partial, int B, int P, int n, float L) {
+    const int V = P + 2;
+    const long idx = (long)blockIdx.x * LOSS_BLOCK + threadIdx.x;
+    float e_edge = 0.f, e_nc = 0.f, e_sm = 0.f;
+    if (idx < (long)B * V) {
+        const int b = (int)(idx / V), i = (int)(idx % V);
+        f3 v, pv[6], nh[6];
+        const int k = load_ring(g, vs, b, i, P, n, v, pv);
+        f3 ring = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int f = 0; f < 6; ++f) {
+            nh[f] = {0.f, 0.f, 0.f};
+            if (f >= k) continue;
+            const f3 d = pv[f] - v;
+            const float d2 = dot(d, d);
+            if (L > 0.f) { const float t = (d2 > MREG_EPS * MREG_EPS ? sqrtf(d2) : 0.f) - L; e_edge += t * t; }
+            else e_edge += d2;
+            ring = ring + pv[f];
+            const f3 q = (f + 1 < k) ? pv[(f + 1) % 6] : pv[0];
+            float len;
+            nh[f] = unit_clamped(cross(d, q - v), len);
+        }
+#pragma unroll
+        for (int f = 0; f < 6; ++f) {
+            if (f >= k) continue;
+            const f3 prev = f > 0 ? nh[(f + 5) % 6] : (k == 6 ? nh[5] : nh[4]);
+            const f3 dn = nh[f] - prev;
+            e_nc += dot(dn, dn);
+        }
+        e_edge *= 0.5f;                                                      // each edge from both of its ends
+        e_nc *= 0.25f;                                                       // ... and 1/2 |n^ - n^|^2
+        const f3 u = scaled(ring, 1.f / (float)k) - v;
+        e_sm = dot(u, u);
+    }
+    block_sum3(e_edge, e_nc, e_sm);
+    if (threadIdx.x == 0) {
+        partial[(size_t)blockIdx.x * 3 + 0] = e_edge;
+        partial[(size_t)blockIdx.x * 3 + 1] = e_nc;
+        partial[(size_t)blockIdx.x * 3 + 2] = e_sm;
+    }
+}
+
+// aux[(b V + i) * 3 ..] = (mean(ring_i) - v_i) / k_i
+__global__ __launch_bounds__(LOSS_BLOCK) void k_mreg_bwd_prep(const float* __restrict__ g, const int32_t* __restrict__ vs,
+                                                               float* __restrict__ aux, int B, int P, int n) {
+    const int V = P + 2;
+    const long idx = (long)blockIdx.x * LOSS_BLOCK + threadIdx.x;
+    if (idx >= (long)B * V) return;
+    const int b = (int)(idx / V), i = (int)(idx % V);
+    f3 v, pv[6];
+    const int k = load_ring(g, vs, b, i, P, n, v, pv);
+    f3 ring = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int f = 0; f < 6; ++f)
+        if (f < k) ring = ring + pv[f];
+    const float inv = 1.f / (float)k;
+    const f3 a = scaled(scaled(ring, inv) - v, inv);
+    float* o = aux + (size_t)idx * 3;
+    o[0] = a.x; o[1] = a.y; o[2] = a.z;
+}
+
+// gradient of the weighted sum with respect to vertex j of sample b (ce, cn, cs: the three terms' constant factors, see the launcher)
+__device__ __forceinline__ f3 mreg_vertex_grad(const float* __restrict__ g, const int32_t* __restrict__ vs,
+                                               const float* __restrict__ aux, int b, int j, int P, int n, float ce, float L, float cn,
+                                               float cs) {
+    const int V = P + 2;
+    f3 v, pv[6];
+    const int k = load_ring(g, vs, b, j, P, n, v, pv);
+    f3 out = {0.f, 0.f, 0.f};
+    if (ce != 0.f) {
+        f3 ge = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int f = 0; f < 6; ++f) {
+            if (f >= k) continue;
+            const f3 d = v - pv[f];
+            if (L > 0.f) {
+                const float d2 = dot(d, d);
+                if (d2 > MREG_EPS * MREG_EPS) ge = ge + scaled(d, 1.f - L / sqrtf(d2));
+            } else {
+                ge = ge + d;
+            }
+        }
+        out = out + scaled(ge, ce);
+    }
+    if (cs != 0.f) {
+        f3 gs = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int f = 0; f < 6; ++f) {
+            const int p = vs[((size_t)j * 6 + f) * 3];
+            if (p < 0) continue;
+            const float* a = aux + ((size_t)b * V + p) * 3;
+            gs = gs + f3{a[0], a[1], a[2]};
+        }
+        const float* a = aux + ((size_t)b * V + j) * 3;
+        const float kf = (float)k;
+        out = out + scaled(gs - f3{kf * a[0], kf * a[1], kf * a[2]}, cs);
+    }
+    if (cn != 0.f) {
+        f3 nh[6], mh[6];
+        float nl[6];
+#pragma unroll
+        for (int f = 0; f < 6; ++f) {
+            nh[f] = mh[f] = {0.f, 0.f, 0.f};
+            nl[f] = 0.f;
+            if (f >= k) continue;
+            const f3 q = (f + 1 < k) ? pv[(f + 1) % 6] : pv[0];
+            nh[f] = unit_clamped(cross(pv[f] - v, q - v), nl[f]);
+            const f3 xv = vertex(g, b, vs[((size_t)j * 6 + f) * 3 + 2], P, n);
+            float ml;
+            mh[f] = unit_clamped(cross(pv[f] - q, xv - q), ml);            // face (q, p, x)
+        }
+        f3 gn = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int f = 0; f < 6; ++f) {
+            if (f >= k || !(nl[f] > MREG_EPS)) continue;
+            const f3 prev = f > 0 ? nh[(f + 5) % 6] : (k == 6 ? nh[5] : nh[4]);
+            const f3 next = (f + 1 < k) ? nh[(f + 1) % 6] : nh[0];
+            const f3 q = (f + 1 < k) ? pv[(f + 1) % 6] : pv[0];
+            const f3 gf = scaled(nh[f], 3.f) - prev - next - mh[f];
+            const f3 H = scaled(gf - scaled(nh[f], dot(gf, nh[f])), 1.f / nl[f]);
+            gn = gn + cross(H, q - pv[f]);
+        }
+        out = out + scaled(gn, cn);
+    }
+    return out;
+}
+
+__global__ __launch_bounds__(LOSS_BLOCK) void k_mreg_bwd(const float* __restrict__ g, const int32_t* __restrict__ vs,
+                                                          const float* __restrict__ aux, const float* __restrict__ upstream, float ce,
+                                                          float L, float cn, float cs, float* __restrict__ dg, int B, int P, int n) {
+    const long idx = (long)blockIdx.x * LOSS_BLOCK + threadIdx.x;
+    if (idx >= (long)B * P) return;
+    const int b = (int)(idx / P), j = (int)(idx % P);
+    f3 d = mreg_vertex_grad(g, vs, aux, b, j, P, n, ce, L, cn, cs);
+    const int chart = 2 * n * n;
+    int pole = -1;
+    if (j % chart == 0) pole = 0;
+    else if ((j + 1) % chart == 0) pole = 1;
+    if (pole >= 0) {
+        const f3 dp = mreg_vertex_grad(g, vs, aux, b, P + pole, P, n, ce, L, cn, cs);
+        d = d + f3{dp.x / 5.f, dp.y / 5.f, dp.z / 5.f};
+    }
+    const float up = upstream[0];
+    float* o = dg + ((size_t)b * P + j) * 3;
+    o[0] = up * d.x;
+    o[1] = up * d.y;
+    o[2] = up * d.z;
+}
+
+}  // namespace
+
+void launch_mesh_reg_fwd(const float* grid, const int32_t* vs, float* partial, float* terms, int B, int P, int n, float f_edge,
+                         float f_ncons, float f_smooth, float edge_length, hipStream_t s) {
+    const int nb = p2p_loss_blocks(B, P);
+    hipLaunchKernelGGL(k_mreg_fwd, dim3(nb), dim3(LOSS_BLOCK), 0, s, grid, vs, partial, B, P, n, edge_length);
+    const double ne = (double)B * 3.0 * P, nv = (double)B * (P + 2);
+    hipLaunchKernelGGL(k_p2p_finalize, dim3(1), dim3(LOSS_BLOCK), 0, s, partial, nb, ne, ne, nv * 3.0, f_edge, f_ncons, f_smooth, terms);
+}
+
+void launch_mesh_reg_bwd(const float* grid, const int32_t* vs, const float* upstream, float f_edge, float f_ncons, float f_smooth,
+                         float edge_length, float* dgrid, float* aux, int B, int P, int n, hipStream_t s) {
+    const double ne = (double)B * 3.0 * P, nv = (double)B * (P + 2);
+    const long tv = (long)B * (P + 2), tp = (long)B * P;
+    if (f_smooth != 0.f)
+        hipLaunchKernelGGL(k_mreg_bwd_prep, dim3((unsigned)((tv + LOSS_BLOCK - 1) / LOSS_BLOCK)), dim3(LOSS_BLOCK), 0, s, grid, vs, aux, B,
+                           P, n);
+    hipLaunchKernelGGL(k_mreg_bwd, dim3((unsigned)((tp + LOSS_BLOCK - 1) / LOSS_BLOCK)), dim3(LOSS_BLOCK), 0, s, grid, vs, aux, upstream,
+                       (float)(2.0 * f_edge / ne), edge_length, (float)(f_ncons / ne), (float)(2.0 * f_smooth / (3.0 * nv)), dgrid, B, P, n);
 }
 
 // ---------------------------------------------------------------------------------------------------------

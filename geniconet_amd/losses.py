@@ -18,7 +18,10 @@ bench.py), and it is what the HIP kernels are tested against besides the numpy o
 on icn_kld_fwd / icn_kld_bwd under the same conditions.
 
 Point2Mesh_Loss is not in the reference: the surface distance it reports at test time (ico_utils.py:26-44) as a loss term.
+Surface_Loss / SurfaceKLD_Loss (train.build_criterion: 'surface' / 'surfacekld') make a training criterion of it: the distance in
+both directions plus Mesh_Regularizer (edge length, normal consistency, Laplacian smoothness; HIP kernels icn_mesh_reg_*).
 """
+import math
 import os
 
 import torch
@@ -216,7 +219,8 @@ class Point2Mesh_Loss(torch.nn.Module):
     point_to_mesh_distance(grid_to_vertices(inputs), ref_vertices, ref_faces)[0].mean() -- the number the reference reports at
     test time (ico_utils.py:26-44, metrics.compute_distance), averaged over the batch, as a differentiable reconstruction term:
     vertices may slide along the target surface instead of being tied to target vertex i as in Point2Point_Loss.  Not in the
-    reference (it has no surface loss); a stand-alone module, not part of Trainer / build_criterion.
+    reference (it has no surface loss); a stand-alone module, not part of Trainer / build_criterion.  Surface_Loss below is the
+    criterion(output, target) form for training: both directions of the distance plus shape regularisers.
 
         forward(inputs (B, 3, 5n, 2n), ref_vertices (B, V, 3), ref_faces (F, 3)) -> scalar tensor
 
@@ -255,6 +259,211 @@ class Point2Mesh_Loss(torch.nn.Module):
     def get_last_losses(self):
         """(the loss, 0, 0, the loss): position-like term, no normal / Laplacian term, total -- the tuple of Point2Point_Loss."""
         return float(self.last_loss_total), 0, 0, float(self.last_loss_total)
+
+
+class _MeshRegFn(torch.autograd.Function):
+    """Mesh_Regularizer on the HIP path (icn_mesh_reg_* in include/icn.h): one kernel evaluates the three terms; the gradient is
+    one gather kernel, preceded by a small per-vertex pass when the smoothness term has a weight."""
+
+    @staticmethod
+    def forward(ctx, inputs, r, f_edge, f_ncons, f_smooth, edge_length):
+        L = _lib.lib()
+        B = inputs.shape[0]
+        grid = inputs.permute(0, 2, 3, 1).contiguous()            # (B, P, 3); free for channels_last
+        terms = torch.empty(4, dtype=torch.float32, device=inputs.device)
+        ws = torch.empty(max(L.icn_mesh_reg_workspace_floats(B, r), 1), dtype=torch.float32, device=inputs.device)
+        with torch.cuda.device(inputs.device):
+            rc = L.icn_mesh_reg_fwd(grid.data_ptr(), B, r, f_edge, f_ncons, f_smooth, edge_length, terms.data_ptr(), ws.data_ptr(),
+                                    torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, 'icn_mesh_reg_fwd')
+        ctx.save_for_backward(grid)
+        ctx.cfg = (B, r, f_edge, f_ncons, f_smooth, edge_length)
+        total = terms[3].clone()
+        ctx.mark_non_differentiable(terms)
+        return total, terms
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gtotal, _gterms):
+        B, r, f_edge, f_ncons, f_smooth, edge_length = ctx.cfg
+        L = _lib.lib()
+        grid, = ctx.saved_tensors
+        dgrid = torch.empty_like(grid)
+        up = gtotal.contiguous().to(torch.float32)
+        ws = None
+        if f_smooth != 0:
+            ws = torch.empty(L.icn_mesh_reg_bwd_workspace_floats(B, r), dtype=torch.float32, device=grid.device)
+        with torch.cuda.device(grid.device):
+            rc = L.icn_mesh_reg_bwd(grid.data_ptr(), up.data_ptr(), B, r, f_edge, f_ncons, f_smooth, edge_length, dgrid.data_ptr(),
+                                    ws.data_ptr() if ws is not None else None, torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, 'icn_mesh_reg_bwd')
+        return dgrid.permute(0, 3, 1, 2), None, None, None, None, None
+
+
+def _check_factors(who, **factors):
+    for name, f in factors.items():
+        if isinstance(f, bool) or not isinstance(f, (int, float)) or not math.isfinite(f):
+            raise ValueError('%s: %s must be a finite number, got %r' % (who, name, f))
+
+
+def _check_subdivisions(who, subdivisions):
+    if isinstance(subdivisions, bool) or not isinstance(subdivisions, int) or not 0 <= subdivisions <= 10:
+        raise ValueError('%s: subdivisions must be an integer in [0, 10], got %r' % (who, subdivisions))
+
+
+class Mesh_Regularizer(torch.nn.Module):
+    """Shape regularisers of the output mesh on the static icosahedral topology (V = 10 * 4^r + 2 vertices = grid pixels then the
+    two pole means, E = 30 * 4^r edges); not in the reference.
+
+        forward(inputs (B, 3, 5n, 2n)) -> factor_edge * T_e + factor_ncons * T_n + factor_smooth * T_s
+
+        T_e = 1 / (B E)   sum_b sum_{(i,j) in E} (|v_i - v_j| - edge_length)^2     edge_length = 0: |v_i - v_j|^2 without a square root;
+                          edge_length > 0: an edge with |v_i - v_j| <= 1e-12 contributes edge_length^2 and a zero gradient
+        T_n = 1 / (B E)   sum_b sum_edges 1/2 |n^_F0 - n^_F1|^2 over the two faces of each edge, n_F = (v_b - v_a) x (v_c - v_a),
+                          n^ = n / max(|n|, 1e-12): 1 - cos of the dihedral angle, in the difference form (in fp32 its gradient is
+                          several times more accurate than that of 1 - n^ . n^ on smooth meshes); a face whose clamp is active
+                          passes no gradient through its normal
+        T_s = 1 / (3 B V) sum_b sum_i |mean(ring_i) - v_i|^2                        (uniform umbrella operator)
+
+    All three are evaluated and reported whatever their factors (last_edge / last_ncons / last_smooth / last_total: device tensors,
+    no .item() until get_last_losses()).  ROCm fp32 tensors of the expected shape run on icn_mesh_reg_fwd / icn_mesh_reg_bwd (gather
+    kernels over the library's edge stencil table, no atomics, bit-identical run to run); ICN_NO_HIP_LOSS=1, CPU tensors and other
+    dtypes take the torch formulation of the same definitions over the same table (_lib.table_vertex_stencils)."""
+
+    def __init__(self, subdivisions, factor_edge, factor_ncons, factor_smooth, edge_length=0.0):
+        super().__init__()
+        _check_subdivisions('Mesh_Regularizer', subdivisions)
+        _check_factors('Mesh_Regularizer', factor_edge=factor_edge, factor_ncons=factor_ncons, factor_smooth=factor_smooth,
+                       edge_length=edge_length)
+        if edge_length < 0:
+            raise ValueError('Mesh_Regularizer: edge_length must be >= 0, got %r' % (edge_length,))
+        self.subdivisions = subdivisions
+        self.factor_edge, self.factor_ncons, self.factor_smooth = factor_edge, factor_ncons, factor_smooth
+        self.edge_length = float(edge_length)
+        vs = torch.from_numpy(_lib.table_vertex_stencils(subdivisions)).long()           # (V, 6, 3) of (p, q, x)
+        p, valid = vs[:, :, 0], vs[:, :, 0] >= 0
+        k = valid.sum(1, keepdim=True)
+        slot = torch.arange(6)[None, :].expand_as(p)
+        p_prev = torch.gather(p, 1, (slot - 1) % k)                                      # p of slot f - 1, wrapping at the valence
+        i = torch.arange(p.shape[0])[:, None].expand_as(p)
+        once = valid & (i < p)                                                            # every undirected edge from its lower end
+        # edge (i, p) and the third vertices of its two faces: slot f = (i, p, q), slot f - 1 = (i, p_prev, p)
+        self.register_buffer('edge_idx', torch.stack((i[once], p[once], vs[:, :, 1][once], p_prev[once]), dim=0))
+        self.register_buffer('nbr_idx', p.clamp_min(0))
+        self.register_buffer('nbr_w', valid.double() / k.double())                       # cast to the input's dtype at use
+        self.last_edge = self.last_ncons = self.last_smooth = self.last_total = 0
+
+    def _hip_path(self, inputs):
+        return not _NO_HIP_LOSS and inputs.is_cuda and inputs.dtype == torch.float32
+
+    @staticmethod
+    def _unit(nrm):
+        """n / max(|n|, 1e-12); where the clamp is active the value is kept and no gradient passes."""
+        d2 = (nrm * nrm).sum(-1, keepdim=True)
+        ok = d2.sqrt() > 1e-12
+        return torch.where(ok, nrm / torch.where(ok, d2, torch.ones_like(d2)).sqrt(), nrm.detach() / 1e-12)
+
+    def terms(self, v):
+        """(T_e, T_n, T_s) of vertices v (B, V, 3) in torch; a term whose factor is 0 records no backward graph."""
+        grad = torch.is_grad_enabled()
+        vi, vp, vq, vm = (torch.index_select(v, 1, self.edge_idx[c]) for c in range(4))
+        with torch.set_grad_enabled(grad and self.factor_edge != 0):
+            d2 = ((vi - vp) ** 2).sum(-1)
+            if self.edge_length > 0:
+                ok = d2 > 1e-24
+                length = torch.where(ok, d2, torch.ones_like(d2)).sqrt()
+                t_e = torch.where(ok, (length - self.edge_length) ** 2, torch.full_like(d2, self.edge_length ** 2)).mean()
+            else:
+                t_e = d2.mean()
+        with torch.set_grad_enabled(grad and self.factor_ncons != 0):
+            n0 = self._unit(torch.cross(vp - vi, vq - vi, dim=2))
+            n1 = self._unit(torch.cross(vm - vi, vp - vi, dim=2))
+            t_n = 0.5 * ((n0 - n1) ** 2).sum(-1).mean()
+        with torch.set_grad_enabled(grad and self.factor_smooth != 0):
+            ring = torch.index_select(v, 1, self.nbr_idx.reshape(-1)).view(v.shape[0], -1, 6, 3)
+            u = (ring * self.nbr_w.to(v.dtype)[None, :, :, None]).sum(2) - v
+            t_s = (u ** 2).mean()
+        return t_e, t_n, t_s
+
+    def forward(self, inputs):
+        n = 2 ** self.subdivisions
+        if inputs.dim() != 4 or tuple(inputs.shape[1:]) != (3, 5 * n, 2 * n) or inputs.shape[0] < 1:
+            raise ValueError('Mesh_Regularizer: expected inputs (B, 3, %d, %d), got %s' % (5 * n, 2 * n, tuple(inputs.shape)))
+        if self._hip_path(inputs):
+            loss, terms = _MeshRegFn.apply(inputs, self.subdivisions, float(self.factor_edge), float(self.factor_ncons),
+                                           float(self.factor_smooth), self.edge_length)
+            self.last_edge, self.last_ncons, self.last_smooth, self.last_total = terms[0], terms[1], terms[2], terms[3]
+            return loss
+        t_e, t_n, t_s = self.terms(grid_to_vertices(inputs, self.subdivisions))
+        loss = self.factor_edge * t_e + self.factor_ncons * t_n + self.factor_smooth * t_s
+        self.last_edge, self.last_ncons, self.last_smooth = t_e.detach(), t_n.detach(), t_s.detach()
+        self.last_total = loss.detach()
+        return loss
+
+    def get_last_losses(self):
+        """(edge, normal consistency, smoothness, weighted total) as floats."""
+        return float(self.last_edge), float(self.last_ncons), float(self.last_smooth), float(self.last_total)
+
+
+class Surface_Loss(torch.nn.Module):
+    """Surface training criterion, criterion(output (B, 3, 5n, 2n), target (B, 9, V)) as Trainer.step calls it; not in the reference.
+
+        out = grid_to_vertices(output);  ref = target[:, 0:3] as (B, V, 3)              (the target mesh shares the ico faces)
+        loss = factor_p2m * mean(p2m(out, ref, ico_faces)) + factor_m2p * mean(p2m(ref, out, ico_faces)) + Mesh_Regularizer(output)
+
+    with p2m = metrics.point_to_mesh_distance.  The first term alone (Point2Mesh_Loss) is zero for an output bunched on one patch of the
+    target; the second, the reference's vertices against the OUTPUT surface (differentiable in the output through the mesh-vertex
+    gradient of icn_point_to_mesh_bwd), pulls the output surface over all of the target; the regularisers keep a mesh that may slide
+    along the surface from folding.  A term with factor 0 is still evaluated for reporting, without a backward graph.  The face
+    list is an int32 buffer validated at construction, so forward + backward never synchronise the host (the public
+    point_to_mesh_distance reads faces.min() back on every call).  search: 'brute' / 'grid' as in point_to_mesh_distance (same
+    values bit for bit; see Point2Mesh_Loss for when 'grid' pays).
+    Cost on an MI355X at I5 / batch 36: NOT MEASURED yet -- `python tools/time_mesh_regularizer.py 10` records the regulariser kernels
+    beside icn_p2p_loss_fwd / _bwd, the torch formulation on the device and this whole term for both searches into
+    profiles/mesh_regularizer.txt; whether the HIP regulariser beats the torch formulation on the device is therefore not known."""
+
+    def __init__(self, subdivisions, factor_p2m=1.0, factor_m2p=1.0, factor_edge=0.0, factor_ncons=0.0, factor_smooth=0.0,
+                 edge_length=0.0, search='brute'):
+        super().__init__()
+        from .metrics import _check_search
+        _check_search(search)
+        _check_subdivisions('Surface_Loss', subdivisions)
+        _check_factors('Surface_Loss', factor_p2m=factor_p2m, factor_m2p=factor_m2p)
+        self.subdivisions, self.search = subdivisions, search
+        self.factor_p2m, self.factor_m2p = factor_p2m, factor_m2p
+        self.regularizer = Mesh_Regularizer(subdivisions, factor_edge, factor_ncons, factor_smooth, edge_length)
+        faces = geometry.get_ico_faces(subdivisions)
+        nv = geometry.num_vertices(subdivisions)
+        if faces.ndim != 2 or faces.shape[1] != 3 or faces.min() < 0 or faces.max() >= nv:
+            raise ValueError('Surface_Loss: the face table does not index %d vertices' % nv)
+        self.register_buffer('ico_faces', torch.from_numpy(faces).to(torch.int32))
+        self.last_p2m = self.last_m2p = self.last_reg = self.last_loss_total = 0
+
+    def forward(self, output, target):
+        from .metrics import _point_to_mesh_unchecked
+        n = 2 ** self.subdivisions
+        if output.dim() != 4 or tuple(output.shape[1:]) != (3, 5 * n, 2 * n) or output.shape[0] < 1:
+            raise ValueError('Surface_Loss: expected output (B, 3, %d, %d), got %s' % (5 * n, 2 * n, tuple(output.shape)))
+        if tuple(target.shape) != (output.shape[0], 9, 10 * n * n + 2):
+            raise ValueError('Surface_Loss: expected target (%d, 9, %d), got %s'
+                             % (output.shape[0], 10 * n * n + 2, tuple(target.shape)))
+        grad = torch.is_grad_enabled()
+        out = grid_to_vertices(output, self.subdivisions)
+        ref = target[:, 0:3].transpose(1, 2).contiguous().to(out.dtype)
+        faces = self.ico_faces if self.ico_faces.device == out.device else self.ico_faces.to(out.device)
+        with torch.set_grad_enabled(grad and self.factor_p2m != 0):
+            l_p2m = _point_to_mesh_unchecked(out, ref, faces, self.search)[0].mean()
+        with torch.set_grad_enabled(grad and self.factor_m2p != 0):
+            l_m2p = _point_to_mesh_unchecked(ref, out, faces, self.search)[0].mean()
+        l_reg = self.regularizer(output)
+        loss = self.factor_p2m * l_p2m + self.factor_m2p * l_m2p + l_reg
+        self.last_p2m, self.last_m2p, self.last_reg = l_p2m.detach(), l_m2p.detach(), l_reg.detach()
+        self.last_loss_total = loss.detach()
+        return loss
+
+    def get_last_losses(self):
+        """(p2m, m2p, regulariser, 0., total) -- the five-tuple of P2P_Loss."""
+        return float(self.last_p2m), float(self.last_m2p), float(self.last_reg), 0., float(self.last_loss_total)
 
 
 class KLD_Loss(torch.nn.Module):
@@ -297,6 +506,25 @@ class P2PKLD_Loss(P2P_Loss, KLD_Loss):
     def forward(self, output, target):
         self.kld_loss = KLD_Loss.forward(self, output, target)
         self.recons_loss = P2P_Loss.forward(self, output[0], target)
+        self.loss = self.recons_loss + self.factor_kl * self.kld_loss
+        return self.loss
+
+    def get_last_losses(self):
+        return float(self.recons_loss.detach()), 0, 0, -float(self.kld_loss.detach()), float(self.loss.detach())
+
+
+class SurfaceKLD_Loss(Surface_Loss, KLD_Loss):
+    """Surface_Loss of the reconstruction + factor_kl * KLD, for (recon, mu, logvar) outputs -- as P2PKLD_Loss is to P2P_Loss."""
+
+    def __init__(self, subdivisions, factor_p2m=1.0, factor_m2p=1.0, factor_edge=0.0, factor_ncons=0.0, factor_smooth=0.0,
+                 edge_length=0.0, search='brute', factor_kl=1.0):
+        super().__init__(subdivisions, factor_p2m, factor_m2p, factor_edge, factor_ncons, factor_smooth, edge_length, search)
+        _check_factors('SurfaceKLD_Loss', factor_kl=factor_kl)
+        self.factor_kl = factor_kl
+
+    def forward(self, output, target):
+        self.kld_loss = KLD_Loss.forward(self, output, target)
+        self.recons_loss = Surface_Loss.forward(self, output[0], target)
         self.loss = self.recons_loss + self.factor_kl * self.kld_loss
         return self.loss
 

@@ -164,6 +164,18 @@ class _PointToMeshFn(torch.autograd.Function):
         return dpts, dvts, None, None
 
 
+def _point_to_mesh_unchecked(pointclouds, vertices, f32, search='brute'):
+    """point_to_mesh_distance without its argument checks, for callers that validated once (losses.Surface_Loss: the face list is
+    a buffer checked at construction): f32 is an int32 (F, 3) tensor on the points' device with indices in [0, V).  No host
+    synchronisation -- the public function's index check reads faces.min() / max() back on every call."""
+    if pointclouds.is_cuda and pointclouds.dtype == torch.float32 and vertices.dtype == torch.float32 and f32.shape[0] > 0:
+        if torch.is_grad_enabled() and (pointclouds.requires_grad or vertices.requires_grad):
+            return _PointToMeshFn.apply(pointclouds, vertices, f32, search)
+        dist, face, kind = _hip_point_to_mesh(pointclouds.contiguous(), vertices.contiguous(), f32, search)
+        return dist, face.long(), kind
+    return _torch_point_to_mesh(pointclouds, vertices, f32)
+
+
 def point_to_mesh_distance(pointclouds, vertices, faces, search='brute'):
     """See the module docstring.  `faces` may be int32 / int64, (F, 3), shared by the batch (as in kaolin 0.9.1).
     search: 'brute' (default) or 'grid', the forward's closest-triangle search on the HIP path; the outputs are identical."""
@@ -181,11 +193,8 @@ def point_to_mesh_distance(pointclouds, vertices, faces, search='brute'):
             raise IndexError('point_to_mesh_distance: face indices span [%d, %d] but there are %d vertices'
                              % (lo, hi, vertices.shape[1]))
     if pointclouds.is_cuda and pointclouds.dtype == torch.float32 and vertices.dtype == torch.float32 and faces.shape[0] > 0:
-        f32 = faces.to(device=pointclouds.device, dtype=torch.int32).contiguous()
-        if torch.is_grad_enabled() and (pointclouds.requires_grad or vertices.requires_grad):
-            return _PointToMeshFn.apply(pointclouds, vertices, f32, search)
-        dist, face, kind = _hip_point_to_mesh(pointclouds.contiguous(), vertices.contiguous(), f32, search)
-        return dist, face.long(), kind
+        return _point_to_mesh_unchecked(pointclouds, vertices, faces.to(device=pointclouds.device, dtype=torch.int32).contiguous(),
+                                        search)
     return _torch_point_to_mesh(pointclouds, vertices, faces.to(pointclouds.device))
 
 

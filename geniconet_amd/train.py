@@ -73,12 +73,20 @@ def build_model(params, device):
 def build_criterion(params, device):
     """run.py:432-444."""
     ico, loss_kind = params['ico'], params[params['model_name']]['loss']
-    args = (ico['subdivisions'], ico['factor_pos'], ico['factor_nor'], ico['factor_lap'])
     lap = ico.get('laplacian', 'mean-v')            # convention of the target's Laplacian rows (not a reference key)
-    if loss_kind == 'p2p':
-        crit = losses.P2P_Loss(*args, laplacian=lap)
-    elif loss_kind == 'p2pkld':
-        crit = losses.P2PKLD_Loss(*args, 1., laplacian=lap)
+    if loss_kind in ('p2p', 'p2pkld'):
+        args = (ico['subdivisions'], ico['factor_pos'], ico['factor_nor'], ico['factor_lap'])
+        crit = losses.P2P_Loss(*args, laplacian=lap) if loss_kind == 'p2p' else losses.P2PKLD_Loss(*args, 1., laplacian=lap)
+    elif loss_kind in ('surface', 'surfacekld'):
+        # the surface criterion (losses.Surface_Loss; not a reference loss kind): its factors are optional keys of params['ico']
+        kw = dict(factor_p2m=ico.get('factor_p2m', 1.0), factor_m2p=ico.get('factor_m2p', 1.0),
+                  factor_edge=ico.get('factor_edge', 0.0), factor_ncons=ico.get('factor_ncons', 0.0),
+                  factor_smooth=ico.get('factor_smooth', 0.0), edge_length=ico.get('edge_length', 0.0),
+                  search=ico.get('p2m_search', 'brute'))
+        if loss_kind == 'surface':
+            crit = losses.Surface_Loss(ico['subdivisions'], **kw)
+        else:
+            crit = losses.SurfaceKLD_Loss(ico['subdivisions'], factor_kl=1., **kw)
     else:
         raise ValueError('loss for %s model not specified' % params['model_name'])
     return crit.to(device)

@@ -186,6 +186,28 @@ size_t icn_p2p_loss_bwd_workspace_floats(int B, int r);
 int icn_p2p_loss_bwd(const float* grid, const float* target, const float* upstream, int B, int r, float f_pos, float f_nor,
                      float f_lap, int lap_mode, float* dgrid, float* ws, void* stream);
 
+/* Mesh regularisers of the surface loss (not in the reference) on the static icosahedral topology; grid as for icn_p2p_loss_fwd,
+ * V = P + 2 vertices, E = 3 P undirected edges:
+ *   terms[0] = 1 / (B E)   sum_b sum_{(i,j) in E} (|v_i - v_j| - edge_length)^2    edge_length = 0: |v_i - v_j|^2, no square root;
+ *                          edge_length > 0: an edge with |v_i - v_j| <= 1e-12 contributes edge_length^2 and a zero gradient
+ *   terms[1] = 1 / (B E)   sum_b sum_edges 1/2 |n^_F0 - n^_F1|^2 over the two faces of each edge, n_F = (v_b - v_a) x (v_c - v_a),
+ *                          n^ = n / max(|n|, 1e-12) (1 - cos of the dihedral angle for non-degenerate faces); a face whose clamp is
+ *                          active passes no gradient through its normal
+ *   terms[2] = 1 / (3 B V) sum_b sum_i |mean(ring_i) - v_i|^2   (= terms[2] of icn_p2p_loss_fwd against all-zero Laplacian rows)
+ *   terms[3] = f_edge * [0] + f_ncons * [1] + f_smooth * [2]
+ * All three terms are always evaluated.  icn_mesh_reg_bwd: dgrid (B, P, 3) = upstream * d terms[3] / d grid (upstream: device
+ * scalar), gather form, no atomics, every element written exactly once, bit-identical run to run; a term with factor 0 costs nothing.
+ * ws: icn_mesh_reg_workspace_floats / icn_mesh_reg_bwd_workspace_floats (B, r) floats (host-only queries; 0 for sizes the calls
+ * reject); the backward reads its workspace only when f_smooth != 0 (ws may be null otherwise).  Topology: icn_table_vertex_stencils.
+ * Asynchronous on `stream`; 0 on success, negative with icn_last_error() otherwise; arguments (null pointers, B < 1, r outside
+ * [0, 10], a negative or non-finite edge_length) are checked before any device call. */
+size_t icn_mesh_reg_workspace_floats(int B, int r);
+int icn_mesh_reg_fwd(const float* grid, int B, int r, float f_edge, float f_ncons, float f_smooth, float edge_length, float* terms,
+                     float* ws, void* stream);
+size_t icn_mesh_reg_bwd_workspace_floats(int B, int r);
+int icn_mesh_reg_bwd(const float* grid, const float* upstream, int B, int r, float f_edge, float f_ncons, float f_smooth,
+                     float edge_length, float* dgrid, float* ws, void* stream);
+
 /* KL term of the VAE loss (reference losses.py:105):  out[0] = mean_b(-0.5 * mean_d(1 + logvar - mu^2 - exp(logvar)))
  * = -0.5 / n * sum over all n = B * D elements.  mu / logvar: n contiguous floats in the same element order.
  * Deterministic two-level sum; ws >= icn_kld_workspace_floats(n) floats.
@@ -267,6 +289,9 @@ long icn_table_conv_bwd(int r_in, int stride, int corner_mode, int32_t* out, siz
 long icn_table_upsample(int r_in, int corner_mode, int transpose, int32_t* idx, float* coef, size_t cap, int* width);
 long icn_table_upsample_pairs(int r_in, int32_t* out, size_t cap);                            /* [2][P_fine]   */
 long icn_table_faces(int r, int32_t* out, size_t cap);                                         /* [20*4^r][3]   */
+/* Edge stencils of the mesh regularisers: (p, q, x) per vertex and slot, -1 padded.  (i, p, q) is a face rotated so that i comes
+ * first, slots in cyclic order around i (q of slot f = p of slot f + 1, wrapping at the valence); (q, p, x) is the face across (p, q). */
+long icn_table_vertex_stencils(int r, int32_t* out, size_t cap);                               /* [10*4^r+2][6][3] */
 /* The stream-K schedule of the persistent conv GEMM for a launch of `ntiles` tiles of `nk` K-STEPS each on `grid`
  * workgroups, no piece shorter than `ku` steps: rows {workgroup, tile, k0, k1} (step ranges) in each workgroup's walk order.
  * A row with k1 < nk is a piece the workgroup parks for the workgroup that holds the tile's last steps (k0 > 0, k1 == nk).
