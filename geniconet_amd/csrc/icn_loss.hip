@@ -334,6 +334,14 @@ constexpr float MREG_EPS = 1e-12f;
 
 __device__ __forceinline__ f3 scaled(f3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
 
+// Face normal for the 1e-12 clamp: every product rounded on its own.  Contracted to fma(a.y, b.z, -(a.z * b.y)), a x a is the
+// rounding error of one product, about 6e-8 |a|^2 and far above the clamp, so a face with two coincident vertices would pass for a
+// face with a direction; with both products rounded a x a is exactly 0, as in the torch formulation.
+__device__ __forceinline__ f3 face_normal(f3 a, f3 b) {
+#pragma clang fp contract(off)
+    return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+
 // n / max(|n|, 1e-12); len = |n|
 __device__ __forceinline__ f3 unit_clamped(f3 nrm, float& len) {
     len = sqrtf(dot(nrm, nrm));
@@ -375,7 +383,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_mreg_fwd(const float* __restrict
             ring = ring + pv[f];
             const f3 q = (f + 1 < k) ? pv[(f + 1) % 6] : pv[0];
             float len;
-            nh[f] = unit_clamped(cross(d, q - v), len);
+            nh[f] = unit_clamped(face_normal(d, q - v), len);
         }
 #pragma unroll
         for (int f = 0; f < 6; ++f) {
@@ -461,10 +469,10 @@ __device__ __forceinline__ f3 mreg_vertex_grad(const float* __restrict__ g, cons
             nl[f] = 0.f;
             if (f >= k) continue;
             const f3 q = (f + 1 < k) ? pv[(f + 1) % 6] : pv[0];
-            nh[f] = unit_clamped(cross(pv[f] - v, q - v), nl[f]);
+            nh[f] = unit_clamped(face_normal(pv[f] - v, q - v), nl[f]);
             const f3 xv = vertex(g, b, vs[((size_t)j * 6 + f) * 3 + 2], P, n);
             float ml;
-            mh[f] = unit_clamped(cross(pv[f] - q, xv - q), ml);            // face (q, p, x)
+            mh[f] = unit_clamped(face_normal(pv[f] - q, xv - q), ml);      // face (q, p, x)
         }
         f3 gn = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -618,40 +626,76 @@ void launch_reparam_bwd(const float* dz, const float* logvar, const float* eps, 
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 
+// Accuracy.  The three edge functions of the region tests are taken from the normal n = ab x ac (vc = ab . (ap x n),
+// vb = -ac . (ap x n), va = |n|^2 - vb - vc) and the interior distance from the plane, (ap . n)^2 / |n|^2; d3 .. d6 follow from
+// d1, d2 and the triangle's Gram matrix.  n carries a relative error of about u / sin(angle at vertex 0), and every boundary
+// between regions and the plane inherit it once: the error of the distance grows with the FIRST power of the aspect ratio
+// (differences of products of dot products, as in the textbook form, lose its square).  Where n cannot be resolved,
+// |n|^2 2^22 <= |ab|^2 |ac|^2 (sine below 1 / 2048: every coincident or collinear triangle, and slivers of aspect ratio above
+// 2048 seen from a sharp corner), the triangle is the union of its three edge segments: the nearest of three clamped projections,
+// at most the sliver's inradius from the true distance, never kind 0.  The test depends on the triangle alone, so it is uniform
+// across a wave of the brute-force kernel.  Edge lengths are expected within about [1e-9, 3e9] (|ab|^2 |ac|^2 is an fp32 product).
+// A triangle with a non-finite vertex returns NaN (never selected), a non-finite point NaN or infinity.
+constexpr float TRI_FLAT = 4194304.f;        // 2^22
+
+// p - q for q the clamped projection of p on the segment u + t uw, given up = p - u; a zero-length segment is its point
+__device__ __forceinline__ f3 seg_diff(f3 up, f3 uw, float& t) {
+    const float den = dot(uw, uw);
+    t = den != 0.f ? dot(uw, up) / den : 0.f;
+    t = !(t > 0.f) ? 0.f : (t < 1.f ? t : 1.f);
+    return f3{up.x - uw.x * t, up.y - uw.y * t, up.z - uw.z * t};
+}
+
 __device__ __forceinline__ float tri_dist2(f3 p, f3 a, f3 b, f3 c, int& kind) {
     const f3 ab = b - a, ac = c - a, ap = p - a;
-    const float d1 = dot(ab, ap), d2 = dot(ac, ap);
-    f3 q;
-    if (d1 <= 0.f && d2 <= 0.f) { kind = 1; q = a; }
+    const float lab = dot(ab, ab), lac = dot(ac, ac);
+    const f3 n = cross(ab, ac);
+    const float nn = dot(n, n);
+    if (!(nn * TRI_FLAT > lab * lac)) {
+        kind = 0;
+        if (!(lab + lac <= 3.0e38f)) return __int_as_float(0x7fc00000);
+        // Nearest of the three clamped projections.  A projection clamped to a vertex is dropped where the other segment through
+        // that vertex projects inside itself: that one is nearer, by an amount that |p - q|^2 may be too coarse to show.
+        float t0, t1, t2;
+        const f3 e0 = seg_diff(ap, ab, t0), e1 = seg_diff(p - b, c - b, t1), e2 = seg_diff(ap, ac, t2);
+        const bool in0 = t0 > 0.f && t0 < 1.f, in1 = t1 > 0.f && t1 < 1.f, in2 = t2 > 0.f && t2 < 1.f;
+        const bool drop0 = t0 <= 0.f ? in2 : (t0 >= 1.f && in1), drop1 = t1 <= 0.f ? in0 : (t1 >= 1.f && in2),
+                   drop2 = t2 <= 0.f ? in0 : (t2 >= 1.f && in1);
+        float best = 3.4e38f;
+        const float s0 = dot(e0, e0), s1 = dot(e1, e1), s2 = dot(e2, e2);
+        if (!drop0) { best = s0; kind = t0 <= 0.f ? 1 : (t0 >= 1.f ? 2 : 4); }
+        if (!drop1 && !(s1 >= best)) { best = s1; kind = t1 <= 0.f ? 2 : (t1 >= 1.f ? 3 : 5); }
+        if (!drop2 && !(s2 >= best)) { best = s2; kind = t2 <= 0.f ? 1 : (t2 >= 1.f ? 3 : 6); }
+        return best;
+    }
+    const float g = dot(ab, ac), d1 = dot(ab, ap), d2 = dot(ac, ap);
+    f3 d;
+    if (d1 <= 0.f && d2 <= 0.f) { kind = 1; d = ap; }
     else {
-        const f3 bp = p - b;
-        const float d3 = dot(ab, bp), d4 = dot(ac, bp);
-        if (d3 >= 0.f && d4 <= d3) { kind = 2; q = b; }
+        const float d3 = d1 - lab, d4 = d2 - g;
+        if (d3 >= 0.f && d4 <= d3) { kind = 2; d = p - b; }
         else {
-            const f3 cp = p - c;
-            const float d5 = dot(ab, cp), d6 = dot(ac, cp);
-            if (d6 >= 0.f && d5 <= d6) { kind = 3; q = c; }
+            const float d5 = d1 - g, d6 = d2 - lac;
+            if (d6 >= 0.f && d5 <= d6) { kind = 3; d = p - c; }
             else {
-                const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-                if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) {
-                    const float den = d1 - d3, t = den != 0.f ? d1 / den : 0.f;
-                    kind = 4; q = a + f3{ab.x * t, ab.y * t, ab.z * t};
+                const f3 r = cross(ap, n);
+                const float vc = dot(ab, r), vb = -dot(ac, r), va = nn - vb - vc;
+                if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) {                 // 0 <= d1 <= lab, lab > 0: t in [0, 1]
+                    const float t = d1 / lab;
+                    kind = 4; d = f3{ap.x - ab.x * t, ap.y - ab.y * t, ap.z - ab.z * t};
                 } else if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) {
-                    const float den = d2 - d6, t = den != 0.f ? d2 / den : 0.f;
-                    kind = 6; q = a + f3{ac.x * t, ac.y * t, ac.z * t};
+                    const float t = d2 / lac;
+                    kind = 6; d = f3{ap.x - ac.x * t, ap.y - ac.y * t, ap.z - ac.z * t};
                 } else if (va <= 0.f && (d4 - d3) >= 0.f && (d5 - d6) >= 0.f) {
-                    const float den = (d4 - d3) + (d5 - d6), t = den != 0.f ? (d4 - d3) / den : 0.f;
-                    const f3 bc = c - b;
-                    kind = 5; q = b + f3{bc.x * t, bc.y * t, bc.z * t};
+                    float t;
+                    kind = 5; d = seg_diff(p - b, c - b, t);
                 } else {
-                    const float den = va + vb + vc, inv = den != 0.f ? 1.f / den : 0.f;
-                    const float v = vb * inv, w = vc * inv;
-                    kind = 0; q = a + f3{ab.x * v + ac.x * w, ab.y * v + ac.y * w, ab.z * v + ac.z * w};
+                    const float s = dot(ap, n) / nn;
+                    kind = 0; d = f3{n.x * s, n.y * s, n.z * s};
                 }
             }
         }
     }
-    const f3 d = p - q;
     return dot(d, d);
 }
 
@@ -698,7 +742,8 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_point_to_mesh(const float* __res
 // Backward of the distance above.  With q = wa a + wb b + wc c the closest point of p on its selected triangle (a, b, c),
 // p - q is orthogonal to the feature q lies on, so the derivative through the weights vanishes:
 //     d dist / d p = 2 (p - q)        d dist / d a = -2 wa (p - q)   (likewise b, c)
-// No second search: q and the weights are recomputed from the forward's (face, kind) with the expressions of tri_dist2.
+// No second search: p - q and the weights are recomputed from the forward's (face, kind) with the expressions of tri_dist2: an edge
+// kind is the clamped projection on that segment (a zero-length edge is its point, weight 1 on its first vertex), kind 0 the plane.
 //   k_point_to_mesh_bwd_point   one thread per point: g = 2 ddist (p - q) -> dpoints; a record (the three vertex ids, g, the three
 //                               weights; id -1 where the weight is zero by construction) -> workspace, 40 bytes per point
 //   k_point_to_mesh_bwd_vertex  one thread per vertex: the records of its sample go through LDS in tiles of 256 points and every
@@ -738,29 +783,21 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_point_to_mesh_bwd_point(const fl
         const float* pb = vts + ((size_t)bi * V + ib) * 3;
         const float* pc = vts + ((size_t)bi * V + ic) * 3;
         const f3 p = {pp[0], pp[1], pp[2]}, a = {pa[0], pa[1], pa[2]}, b = {pb[0], pb[1], pb[2]}, c = {pc[0], pc[1], pc[2]};
-        const f3 ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c;
-        const float d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp);
-        f3 q;
-        if (k == 1) { q = a; wa = 1.f; }
-        else if (k == 2) { q = b; wb = 1.f; }
-        else if (k == 3) { q = c; wc = 1.f; }
-        else if (k == 4) {
-            const float den = d1 - d3, t = den != 0.f ? d1 / den : 0.f;
-            q = a + f3{ab.x * t, ab.y * t, ab.z * t}; wa = 1.f - t; wb = t;
-        } else if (k == 6) {
-            const float den = d2 - d6, t = den != 0.f ? d2 / den : 0.f;
-            q = a + f3{ac.x * t, ac.y * t, ac.z * t}; wa = 1.f - t; wc = t;
-        } else if (k == 5) {
-            const float den = (d4 - d3) + (d5 - d6), t = den != 0.f ? (d4 - d3) / den : 0.f;
-            const f3 bc = c - b;
-            q = b + f3{bc.x * t, bc.y * t, bc.z * t}; wb = 1.f - t; wc = t;
-        } else {
-            const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-            const float den = va + vb + vc, inv = den != 0.f ? 1.f / den : 0.f;
-            const float v = vb * inv, w = vc * inv;
-            q = a + f3{ab.x * v + ac.x * w, ab.y * v + ac.y * w, ab.z * v + ac.z * w}; wa = 1.f - v - w; wb = v; wc = w;
+        const f3 ab = b - a, ac = c - a, ap = p - a;
+        f3 d;
+        float t;
+        if (k == 1) { d = ap; wa = 1.f; }
+        else if (k == 2) { d = p - b; wb = 1.f; }
+        else if (k == 3) { d = p - c; wc = 1.f; }
+        else if (k == 4) { d = seg_diff(ap, ab, t); wa = 1.f - t; wb = t; }
+        else if (k == 6) { d = seg_diff(ap, ac, t); wa = 1.f - t; wc = t; }
+        else if (k == 5) { d = seg_diff(p - b, c - b, t); wb = 1.f - t; wc = t; }
+        else {                                                             // the plane: p - q = (ap . n / |n|^2) n
+            const f3 n = cross(ab, ac), r = cross(ap, n);
+            const float nn = dot(n, n), inv = nn != 0.f ? 1.f / nn : 0.f;
+            const float v = -dot(ac, r) * inv, w = dot(ab, r) * inv, s = dot(ap, n) * inv;
+            d = f3{n.x * s, n.y * s, n.z * s}; wa = 1.f - v - w; wb = v; wc = w;
         }
-        const f3 d = p - q;
         const float up = 2.f * ddist[at];
         g = {up * d.x, up * d.y, up * d.z};
         // vertices whose weight is zero by the kind take no part in the accumulation
@@ -846,10 +883,14 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_point_to_mesh_bwd_vertex(P2MReco
 //     distance by 1e-6 (G + 1 + |t(p)|) covers that and the rounding of the subtraction five times over; h vs h' and the product
 //     are two more roundings (factor 1 - 1e-6).
 //   * r is a square root of three squares of differences, a few u relative; the mesh extent is >= 1e-8, so h >= 1e-10 and an
-//     underflowing square (r < 2e-19) is far below the absolute 1e-6 h that is added: rmax (1 + 1e-5) + 1e-6 h.
-//   * the brute-force value itself is fp32: tri_dist2 returns |p - q|^2 for a q that is a convex combination (weights from its
-//     region tests, all in [0, 1]) of the vertices up to about 8 u (amax + |p|), so it can undercut the true distance by that
-//     much.  4e-6 (amax + |p|_inf) is subtracted, and the square is compared with a factor 1 - 1e-5.
+//     underflowing square (r < 2e-19) is far below the absolute 1e-6 h that is added: rmax (1 + 1e-5) + 1e-6 h, and 1 % on top for the interior case below.
+//   * the brute-force value itself is fp32 and may undercut the true distance.  On a vertex, an edge or a flattened triangle
+//     tri_dist2 returns |p - q|^2 for a q on the triangle (a vertex, or u + t uw with t in [0, 1]) up to about 8 u (amax + |p|):
+//     4e-6 (amax + |p|_inf) is subtracted.  In the interior it returns the distance to the plane of the COMPUTED normal, which is
+//     off by an angle e <= 4 u / sin(angle at vertex 0) <= 2^13 u = 4.9e-4 (larger and the triangle is flattened), and the three
+//     edge functions place the foot with an error of about (e + 5 u) |ap|, |ap| <= distance + 2 r.  A foot accepted that far
+//     outside the triangle, on a plane tilted that much, undercuts by at most about 2 e |ap| < 1e-3 (distance + 2 r): rmax is
+//     taken 1 % larger and the square is compared with a factor 1 - 1e-2, five times that.
 // Cost bounds: a point far from the surface walks shells that are mostly empty, two dependent loads per slot range and at most
 // 2 (2k + 1)^2 ranges in shell k -- latency-bound, and measured 8 x slower than the brute-force kernel when such a walk was allowed
 // to cover the grid.  So the walk is cut after kmax = max(2, G / 4) shells (<= ~(8 / 3) kmax^3 range reads); a point that is not done
@@ -1042,7 +1083,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_p2m_grid_query(const float* __re
     if (hdr[6] == 0u) {
         const f3 lo = {__uint_as_float(hdr[0]), __uint_as_float(hdr[1]), __uint_as_float(hdr[2])};
         const float h = __uint_as_float(hdr[3]), inv_h = __uint_as_float(hdr[4]), amax = __uint_as_float(hdr[5]);
-        const float rmax = __uint_as_float(hdr[7]) * (1.f + 1e-5f) + 1e-6f * h;
+        const float rmax = __uint_as_float(hdr[7]) * (1.f + 1e-2f) + 1e-6f * h;
         float tx, ty, tz;
         const int cx = grid_cell(p.x, lo.x, inv_h, G, tx), cy = grid_cell(p.y, lo.y, inv_h, G, ty), cz = grid_cell(p.z, lo.z, inv_h, G, tz);
         const float pmax = fmaxf(fabsf(p.x), fmaxf(fabsf(p.y), fabsf(p.z)));
@@ -1074,7 +1115,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_p2m_grid_query(const float* __re
             if (z1 < G - 1) dt = fminf(dt, (float)(z1 + 1) - tz);
             if (dt == 3.4e38f) break;                                      // every cell visited
             const float bound = (dt - tslack) * h * (1.f - 1e-6f) - dslack;
-            if (finite && bound > 0.f && bound * bound * (1.f - 1e-5f) > best) break;
+            if (finite && bound > 0.f && bound * bound * (1.f - 1e-2f) > best) break;
         }
         // not excluded after kmax shells (farther from the mesh than about a quarter of its extent, or not finite): the whole
         // list, linearly.  Re-testing a triangle changes nothing; such lanes of a wave scan in lockstep, reading the same slots.

@@ -357,6 +357,15 @@ class Mesh_Regularizer(torch.nn.Module):
         return not _NO_HIP_LOSS and inputs.is_cuda and inputs.dtype == torch.float32
 
     @staticmethod
+    def _face_normal(a, b):
+        """a x b with every product rounded on its own.  torch.cross (and a contracting compiler) evaluates a component as
+        fma(a_y, b_z, -(a_z b_y)), which makes a x a the rounding error of one product: about 6e-8 |a|^2 in fp32, far above the
+        1e-12 clamp, so a face with two coincident vertices would count with a random unit normal.  Here a x a is exactly 0."""
+        ax, ay, az = a.unbind(-1)
+        bx, by, bz = b.unbind(-1)
+        return torch.stack((ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx), dim=-1)
+
+    @staticmethod
     def _unit(nrm):
         """n / max(|n|, 1e-12); where the clamp is active the value is kept and no gradient passes."""
         d2 = (nrm * nrm).sum(-1, keepdim=True)
@@ -376,8 +385,8 @@ class Mesh_Regularizer(torch.nn.Module):
             else:
                 t_e = d2.mean()
         with torch.set_grad_enabled(grad and self.factor_ncons != 0):
-            n0 = self._unit(torch.cross(vp - vi, vq - vi, dim=2))
-            n1 = self._unit(torch.cross(vm - vi, vp - vi, dim=2))
+            n0 = self._unit(self._face_normal(vp - vi, vq - vi))
+            n1 = self._unit(self._face_normal(vm - vi, vp - vi))
             t_n = 0.5 * ((n0 - n1) ** 2).sum(-1).mean()
         with torch.set_grad_enabled(grad and self.factor_smooth != 0):
             ring = torch.index_select(v, 1, self.nbr_idx.reshape(-1)).view(v.shape[0], -1, 6, 3)

@@ -6,6 +6,9 @@ upstream takes from kaolin's CUDA extension (`kaolin.metrics.trianglemesh.point_
     face  (B, P)  index of a closest triangle (the lowest index among equally close ones)
     kind  (B, P)  where on that triangle the closest point lies: 0 interior, 1 / 2 / 3 at vertex 0 / 1 / 2,
                   4 / 5 / 6 on edge (0,1) / (1,2) / (2,0)
+On every triangle, coincident and collinear vertices included, sqrt(dist2) is within 14 u scale + min(u scale kappa, h_min) of
+float64 (u = 2^-24, scale the largest |coordinate| involved, kappa = l_max / h_min the triangle's aspect ratio); a triangle without
+area never reports kind 0 (tests/test_point_to_mesh_shapes.py).
 The reference consumes `torch.mean(dist2)` (ico_utils.py:41).  ROCm fp32 tensors run on a HIP kernel (icn_point_to_mesh in
 include/icn.h: one thread per point, triangles staged through LDS); anything else on the chunked torch formulation below,
 which is also the kernel's second check in the tests (the first is the numpy oracle, oracle/metrics_ref.py).
@@ -34,39 +37,71 @@ from . import _lib
 
 def _closest_on_triangles(p, a, b, c):
     """Squared distance + region of the closest point on triangles (a, b, c) for points p; all (..., 3), broadcastable.
-    Region tests of Ericson, Real-Time Collision Detection 5.1.5 (Voronoi regions of the triangle's features)."""
+    Region tests of Ericson, Real-Time Collision Detection 5.1.5 (Voronoi regions of the triangle's features), with the three
+    edge functions taken from the normal n = ab x ac (vc = ab . (ap x n), vb = -ac . (ap x n), va = |n|^2 - vb - vc) instead of
+    differences of products of dot products, and the interior distance from the plane, (ap . n)^2 / |n|^2: the error grows with
+    the first power of the triangle's aspect ratio, not the second.  A triangle whose normal cannot be resolved,
+    |n|^2 <= 2 eps |ab|^2 |ac|^2 (the sine of the angle at vertex 0 below about 1 / 2048 in fp32; every coincident or collinear
+    triangle), is the union of its three edge segments: the nearest of three clamped projections, never kind 0.
+    The same method and region tests as tri_dist2 in csrc/icn_loss.hip, not the same arithmetic: the interior distance is
+    taken along n / |n| here and as n (ap . n / |n|^2) there, edge (1, 2) is the clamped projection while edges (0, 1) and
+    (2, 0) divide unclamped, and the device contracts to FMAs.  The two agree to rounding, never bit for bit."""
     ab, ac, ap = b - a, c - a, p - a
+    lab, lac, g = (ab * ab).sum(-1), (ac * ac).sum(-1), (ab * ac).sum(-1)
     d1, d2 = (ab * ap).sum(-1), (ac * ap).sum(-1)
-    bp = p - b
-    d3, d4 = (ab * bp).sum(-1), (ac * bp).sum(-1)
-    cp = p - c
-    d5, d6 = (ab * cp).sum(-1), (ac * cp).sum(-1)
-    vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
+    d3, d4, d5, d6 = d1 - lab, d2 - g, d1 - g, d2 - lac
+    n = torch.linalg.cross(ab, ac)
+    nn = (n * n).sum(-1)
+    r = torch.linalg.cross(ap, n)
+    vc, vb = (ab * r).sum(-1), -(ac * r).sum(-1)
+    va = nn - vb - vc
     one = torch.ones_like(d1)
     tiny = torch.finfo(p.dtype).tiny
 
     def safe(num, den):
         return num / torch.where(den.abs() > tiny, den, one)
+
+    def segment(u, uw, den, k_u, k_w, k_edge):
+        """Clamped projection of p on the segment u + t uw -> (p - q, kind)."""
+        up = p - u
+        t = safe((uw * up).sum(-1), den).clamp(0, 1)
+        k = torch.where(t <= 0, torch.full_like(t, k_u), torch.where(t >= 1, torch.full_like(t, k_w), torch.full_like(t, k_edge)))
+        return up - uw * t[..., None], k.to(torch.int32)
+    bc = c - b
+    lbc = (bc * bc).sum(-1)
+    seg_ab, seg_bc, seg_ac = segment(a, ab, lab, 1, 2, 4), segment(b, bc, lbc, 2, 3, 5), segment(a, ac, lac, 1, 3, 6)
     # interior (default), then the edge and vertex regions in increasing priority
-    den = va + vb + vc
-    v, w = safe(vb, den), safe(vc, den)
-    q = a + ab * v[..., None] + ac * w[..., None]
+    flat = ~(nn * (0.5 / torch.finfo(p.dtype).eps) > lab * lac)
+    unit = n / torch.where(flat, one, nn).sqrt()[..., None]                  # |n|, not |n|^2: its square must not underflow
+    d = unit * (ap * unit).sum(-1, keepdim=True)
     kind = torch.zeros_like(d1, dtype=torch.int32)
 
-    def put(mask, point, k):
-        nonlocal q, kind
-        q = torch.where(mask[..., None], point, q)
-        kind = torch.where(mask, torch.full_like(kind, k), kind)
-    t = safe(d4 - d3, (d4 - d3) + (d5 - d6))
-    put((va <= 0) & ((d4 - d3) >= 0) & ((d5 - d6) >= 0), b + (c - b) * t[..., None], 5)          # edge (1, 2)
-    t = safe(d2, d2 - d6)
-    put((vb <= 0) & (d2 >= 0) & (d6 <= 0), a + ac * t[..., None], 6)                               # edge (2, 0)
-    t = safe(d1, d1 - d3)
-    put((vc <= 0) & (d1 >= 0) & (d3 <= 0), a + ab * t[..., None], 4)                               # edge (0, 1)
-    put((d6 >= 0) & (d5 <= d6), c.expand_as(q), 3)
-    put((d3 >= 0) & (d4 <= d3), b.expand_as(q), 2)
-    put((d1 <= 0) & (d2 <= 0), a.expand_as(q), 1)
-    return ((p - q) ** 2).sum(-1), kind
+    def put(mask, vec, k):
+        nonlocal d, kind
+        d = torch.where(mask[..., None], vec, d)
+        kind = torch.where(mask, k if torch.is_tensor(k) else torch.full_like(kind, k), kind)
+    put((va <= 0) & ((d4 - d3) >= 0) & ((d5 - d6) >= 0), *seg_bc)                                  # edge (1, 2)
+    put((vb <= 0) & (d2 >= 0) & (d6 <= 0), ap - ac * safe(d2, lac)[..., None], 6)                  # edge (2, 0)
+    put((vc <= 0) & (d1 >= 0) & (d3 <= 0), ap - ab * safe(d1, lab)[..., None], 4)                  # edge (0, 1)
+    put((d6 >= 0) & (d5 <= d6), (p - c).expand_as(d), 3)
+    put((d3 >= 0) & (d4 <= d3), (p - b).expand_as(d), 2)
+    put((d1 <= 0) & (d2 <= 0), ap.expand_as(d), 1)
+    # unresolved normal: the nearest of the three segments, the first among equals in the order (0,1), (1,2), (2,0)
+    # (a projection clamped to a vertex is dropped where the other segment through that vertex projects inside itself: that one
+    # is nearer, by an amount that the squared distance may be too coarse to show)
+    inside = [(k >= 4) for _, k in (seg_ab, seg_bc, seg_ac)]
+    ends = ((1, 2, 2, 1), (2, 0, 3, 2), (1, 0, 3, 1))          # per segment: kind at t = 0, the other segment there, at t = 1, there
+    fd = fk = fd2 = None
+    for (vec, k), (k0, o0, k1, o1) in zip((seg_ab, seg_bc, seg_ac), ends):
+        v2 = (vec * vec).sum(-1)
+        v2 = torch.where(((k == k0) & inside[o0]) | ((k == k1) & inside[o1]), torch.full_like(v2, float('inf')), v2)
+        if fd is None:
+            fd, fk, fd2 = vec, k, v2
+            continue
+        take = v2 < fd2
+        fd, fk, fd2 = torch.where(take[..., None], vec, fd), torch.where(take, k, fk), torch.where(take, v2, fd2)
+    put(flat.expand_as(kind), fd, fk)
+    return (d * d).sum(-1), kind
 
 
 def _torch_point_to_mesh(points, vertices, faces, chunk=256):

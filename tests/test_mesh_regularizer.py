@@ -299,3 +299,187 @@ def test_deterministic_fully_written_and_per_sample():
     # the terms are means over the batch: sample 1 of a batch of 3, times 3, is the batch-of-1 gradient
     one = _raw_backward(bp3[1:2].contiguous(), r, FACTORS[3], L, torch.empty_like(bp3[1:2]))
     assert rel_l2((3 * outs[0][2].permute(0, 2, 3, 1)[1:2]).cpu().numpy(), one.cpu().numpy()) <= 1e-6
+
+
+# ---- 8. the documented clamps on degenerate meshes: the cases, and the float64 torch formulation on them ---------------------------
+# "A clamped face passes no gradient", "an edge shorter than 1e-12 adds L^2 and no gradient": on meshes that are degenerate in the
+# ways a saturated or untrained network makes them.  Every case is chosen from float64 alone so that no |n| and no |d|^2 lies within
+# a factor 10 of its clamp threshold (asserted), so fp32 and float64 have no excuse to take different branches.
+DEGENERATE = ('zero', 'copied vertex', 'pole corners', 'collinear face', 'tiny', 'huge', 'saturated')
+
+
+def _pixel_faces(r):
+    """Faces (i, p, q) of the stencil table whose three vertices are grid pixels, away from the poles' corners."""
+    vs = _lib.table_vertex_stencils(r)
+    P = geometry.num_vertices(r) - 2
+    corners = set(torch.nonzero(_pole_corner_mask(r).reshape(-1)).reshape(-1).tolist())
+    return [(i, int(vs[i, 0, 0]), int(vs[i, 0, 1])) for i in range(P)
+            if max(vs[i, 0, 0], vs[i, 0, 1]) < P and not {i, int(vs[i, 0, 0]), int(vs[i, 0, 1])} & corners]
+
+
+def _degenerate_grid(r, case):
+    n, B = 2 ** r, 2
+    if case == 'zero':
+        return torch.zeros(B, 3, 5 * n, 2 * n)
+    if case == 'saturated':
+        from test_point_to_mesh_shapes import _saturated_grid
+        return _saturated_grid(B, r)
+    flat = _grid_case(r, B, 'bumpy').reshape(B, 3, -1).clone()                      # (B, 3, P): column j is vertex j
+    i, p, q = _pixel_faces(r)[len(_pixel_faces(r)) // 2]
+    if case == 'copied vertex':                                                     # a zero-length edge, two faces without area
+        flat[:, :, i] = flat[:, :, p]
+    elif case == 'pole corners':                                                    # the pole and its whole ring in one lattice point
+        corners = [(c * n) * 2 * n for c in range(5)]
+        point = torch.round(flat[:, :, corners[0]] * 256) / 256                     # 5 x and 5 x / 5 are exact in fp32
+        flat[:, :, corners] = point[:, :, None]
+    elif case == 'collinear face':                                                  # area exactly zero in fp32, edges not
+        a = torch.round(flat[:, :, i] * 64) / 64
+        step = torch.tensor([16.0, -12.0, 8.0]) / (64 * 2 ** (r - 1))
+        flat[:, :, i], flat[:, :, p], flat[:, :, q] = a, a + step, a + 2 * step
+    elif case == 'tiny':                                                            # every |n| far below the 1e-12 clamp
+        flat *= 1e-7
+    elif case == 'huge':
+        flat *= 1e6
+    return flat.reshape(B, 3, 5 * n, 2 * n).contiguous()
+
+
+def _clamp_margins(grid, r):
+    """float64 |n| of both faces of every edge and |d|^2 of every edge; none within a factor 10 of its threshold."""
+    reg = losses.Mesh_Regularizer(r, 1.0, 1.0, 1.0)
+    v = losses.grid_to_vertices(grid.double(), r)
+    vi, vp, vq, vm = (torch.index_select(v, 1, reg.edge_idx[c]) for c in range(4))
+    d2 = ((vi - vp) ** 2).sum(-1)
+    nl = torch.cat([torch.cross(vp - vi, vq - vi, dim=2).norm(dim=2), torch.cross(vm - vi, vp - vi, dim=2).norm(dim=2)], 1)
+    assert not bool(((nl > 1e-13) & (nl < 1e-11)).any()) and not bool(((d2 > 1e-25) & (d2 < 1e-23)).any())
+    return nl, d2
+
+
+@functools.lru_cache(maxsize=None)
+def _degenerate_reference(r, case, with_length):
+    grid = _degenerate_grid(r, case)
+    L = float(np.float32(max(_mean_edge_length(r, grid), 0.25 if case == 'zero' else 0.0))) if with_length else 0.0
+    g = grid.double().requires_grad_()
+    terms = losses.Mesh_Regularizer(r, 1.0, 1.0, 1.0, edge_length=L).terms(losses.grid_to_vertices(g, r))
+    per_term = [torch.autograd.grad(t, g, retain_graph=True)[0] for t in terms]
+    grads = {f: f[0] * per_term[0] + f[1] * per_term[1] + f[2] * per_term[2] for f in FACTORS}
+    return grid, L, [float(t.detach()) for t in terms], grads
+
+
+@pytest.mark.parametrize('case', DEGENERATE)
+@pytest.mark.parametrize('r', [1, 2])
+def test_degenerate_cases_keep_clear_of_the_clamp_thresholds(r, case):
+    grid = _degenerate_grid(r, case)
+    nl, d2 = _clamp_margins(grid, r)
+    flat_faces, short_edges = int((nl <= 1e-13).sum()), int((d2 <= 1e-25).sum())
+    print(r, case, 'clamped normals %d of %d, clamped edges %d of %d' % (flat_faces, nl.numel(), short_edges, d2.numel()))
+    if case in ('zero', 'tiny'):
+        assert flat_faces == nl.numel() and short_edges == (d2.numel() if case == 'zero' else 0)
+    elif case == 'huge':
+        assert flat_faces == 0 and short_edges == 0
+    elif case == 'collinear face':
+        assert flat_faces >= 2 * 3 and short_edges == 0                              # one face, seen from each of its three edges
+    else:
+        assert flat_faces >= 2 * 2 and short_edges >= 2
+    for with_length in (False, True):                                               # the float64 formulation itself is finite
+        _, _, terms, grads = _degenerate_reference(r, case, with_length)
+        assert all(math.isfinite(t) for t in terms) and all(bool(torch.isfinite(g).all()) for g in grads.values())
+
+
+def _check_against_float64_under_the_clamps(r, case, with_length, device):
+    """Mesh_Regularizer in fp32 on `device` (cuda: k_mreg_fwd / k_mreg_bwd; cpu: the torch formulation) against the float64 torch formulation at the file's 1e-4, terms and gradient, for every FACTORS.
+    Where the float64 value is 0 (a term of the all-zero grid, the normal term's gradient on a mesh whose every face is clamped)
+    the bound is 0 too: the HIP value must be exactly 0.  A face with two coincident vertices has the normal 0 exactly in both
+    precisions only because the kernels round both products of a cross product (face_normal in csrc/icn_loss.hip); contracted
+    to an FMA, v x v is about 6e-8 |v|^2, far above the 1e-12 clamp, and such a face would count with a random unit normal."""
+    grid, L, want_terms, want_grads = _degenerate_reference(r, case, with_length)
+    _clamp_margins(grid, r)
+    for f in FACTORS:
+        reg = losses.Mesh_Regularizer(r, *f, edge_length=L)
+        g = grid.clone().to(device).requires_grad_()
+        loss = reg(g)
+        assert (device == 'cuda') == isinstance(loss.grad_fn, torch.autograd.function.BackwardCFunction)       # the HIP path
+        loss.backward()
+        got_terms = reg.get_last_losses()
+        print(r, case, L, f, 'terms', got_terms[:3], want_terms)
+        assert all(math.isfinite(t) for t in got_terms) and math.isfinite(float(loss))
+        for k in range(3):
+            assert abs(got_terms[k] - want_terms[k]) <= 1e-4 * abs(want_terms[k]), (f, k, got_terms[k], want_terms[k])
+        total = sum(f[k] * want_terms[k] for k in range(3))
+        assert abs(got_terms[3] - total) <= 1e-4 * abs(total) and abs(float(loss) - total) <= 1e-4 * abs(total)
+        got, want = g.grad.cpu().double(), want_grads[f]
+        assert bool(torch.isfinite(got).all()), f
+        if not bool(want.any()):
+            assert not bool(got.any()), (f, 'gradient must be exactly zero', float(got.abs().max()))
+        else:
+            e = rel_l2(got.numpy(), want.numpy())
+            print(r, case, L, f, 'gradient rel-L2 %.3g' % e)
+            assert e <= 1e-4, (f, e)
+    if case == 'zero':                                                              # T_e = L^2 and nothing else, no gradient at all
+        assert want_terms == [L * L, 0.0, 0.0] and not any(bool(w.any()) for w in want_grads.values())
+
+
+@pytest.mark.parametrize('with_length', [False, True])
+@pytest.mark.parametrize('case', DEGENERATE)
+@pytest.mark.parametrize('r', [1, 2])
+def test_fp32_torch_formulation_matches_float64_under_the_clamps(r, case, with_length):
+    _check_against_float64_under_the_clamps(r, case, with_length, 'cpu')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('with_length', [False, True])
+@pytest.mark.parametrize('case', DEGENERATE)
+@pytest.mark.parametrize('r', [1, 2])
+def test_hip_matches_float64_under_the_clamps(r, case, with_length):
+    _check_against_float64_under_the_clamps(r, case, with_length, 'cuda')
+
+
+def _saturated_surface_case(r=2, B=2):
+    from test_point_to_mesh_shapes import _saturated_grid
+    output = _saturated_grid(B, r)
+    target = torch.zeros(B, 9, geometry.num_vertices(r))
+    target[:, 0:3] = (_bumpy_vertices(r, B, seed=7) * torch.tensor([0.9, 1.2], dtype=torch.float64)[:, None, None]).transpose(1, 2).float()
+    L = float(np.float32(_mean_edge_length(r, output)))
+    return output, target, dict(factor_p2m=1.0, factor_m2p=1.0, factor_edge=0.1, factor_ncons=0.01, factor_smooth=0.1, edge_length=L)
+
+
+@functools.lru_cache(maxsize=None)
+def _saturated_surface_reference():
+    output, target, kw = _saturated_surface_case()
+    crit = losses.Surface_Loss(2, **kw)
+    x = output.double().requires_grad_()
+    loss = crit(x, target.double())
+    loss.backward()
+    return float(loss.detach()), crit.get_last_losses(), x.grad.detach()
+
+
+def test_surface_loss_on_the_saturated_grid_is_finite_in_float64():
+    total, parts, grad = _saturated_surface_reference()
+    assert math.isfinite(total) and all(math.isfinite(t) for t in parts) and bool(torch.isfinite(grad).all())
+    assert parts[0] > 0 and parts[1] > 0 and parts[2] > 0 and bool(grad.any())
+
+
+@pytest.mark.gpu
+def test_surface_loss_on_the_saturated_grid():
+    """Both directions of the distance and the regularisers with the saturated mesh as the output: in the mesh-to-points term it is
+    the TRIANGLE mesh, four faces in five without area, and the vertex gradient flows into rings of coincident vertices and on to
+    the grid.  Against the torch fallback in float64: the loss and its three parts at 1e-4; the gradient finite and bit-identical
+    run to run and search to search.  The gradient is not compared value by value: target points with two closest points on this
+    folded mesh, and the split among coincident faces and vertices, make it a matter of choice; what is well defined of it is
+    checked with those points weighted out in tests/test_point_to_mesh_shapes.py::test_hip_gradients_on_whole_meshes."""
+    output, target, kw = _saturated_surface_case()
+    want_total, want_parts, want_grad = _saturated_surface_reference()
+    runs = []
+    for search in ('brute', 'brute', 'grid'):
+        crit = losses.Surface_Loss(2, search=search, **kw).cuda()
+        x = output.cuda().requires_grad_()
+        loss = crit(x, target.cuda())
+        loss.backward()
+        runs.append((loss.detach().clone(), x.grad.clone(), crit.get_last_losses()))
+    for other in runs[1:]:                                                          # run to run, and search to search
+        assert torch.equal(runs[0][0], other[0]) and torch.equal(runs[0][1], other[1]) and runs[0][2] == other[2]
+    got_total, got_grad, got_parts = float(runs[0][0]), runs[0][1].cpu(), runs[0][2]
+    print('Surface_Loss on the saturated grid: got', got_parts, 'float64', want_parts)
+    assert math.isfinite(got_total) and bool(torch.isfinite(got_grad).all())
+    assert abs(got_total - want_total) <= 1e-4 * abs(want_total)
+    for k in (0, 1, 2, 4):
+        assert abs(got_parts[k] - want_parts[k]) <= 1e-4 * abs(want_parts[k]), k
