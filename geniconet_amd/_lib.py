@@ -83,6 +83,10 @@ SIGNATURES = {
     'icn_point_to_mesh_grid_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
     'icn_point_to_mesh_grid': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 4 + [_c_float_p] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     'icn_point_to_mesh_bwd': (ctypes.c_int, [_c_float_p] * 6 + [ctypes.c_int] * 4 + [_c_float_p] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    'icn_mesh_sample_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
+    'icn_mesh_sample_fwd': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 4 + [_c_float_p] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    'icn_mesh_sample_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
+    'icn_mesh_sample_bwd': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 4 + [_c_float_p] + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     'icn_table_conv_fwd': (ctypes.c_long, [ctypes.c_int] * 3 + [_i32p, ctypes.c_size_t]),
     'icn_table_wgrad7': (ctypes.c_long, [ctypes.c_int] * 3 + [_i32p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint16), ctypes.c_size_t, _intp]),
     'icn_table_conv_bwd': (ctypes.c_long, [ctypes.c_int] * 3 + [_i32p, ctypes.c_size_t, _intp]),

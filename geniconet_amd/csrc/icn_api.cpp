@@ -728,7 +728,9 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_conv_b3_single_sk<128, 128, 8>", "k_conv_b3_single_sk<128, 64, 4>",
                                             "k_point_to_mesh", "k_point_to_mesh_bwd_point", "k_point_to_mesh_bwd_vertex",
                                             "k_p2m_grid_bounds", "k_p2m_grid_count", "k_p2m_grid_scan", "k_p2m_grid_fill",
-                                            "k_p2m_grid_query"};
+                                            "k_p2m_grid_query",
+                                            "k_msample_area", "k_msample_scan", "k_msample_point", "k_msample_bwd_record",
+                                            "k_msample_bwd_vertex"};
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1415,6 +1417,52 @@ int icn_point_to_mesh_grid(const float* points, const float* vertices, const int
             throw std::invalid_argument("icn_point_to_mesh_grid: workspace smaller than icn_point_to_mesh_grid_workspace_bytes");
         if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) throw std::invalid_argument("icn_point_to_mesh_grid: workspace must be 16-byte aligned");
         ICN_HIP(icn::launch_point_to_mesh_grid(points, vertices, faces, B, P, V, F, dist2, face, kind, ws, static_cast<hipStream_t>(stream)));
+        ICN_HIP(hipGetLastError());
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(e.what());
+    }
+}
+
+namespace {
+void check_mesh_sample(const char* who, int B, int S, int V, int F) {
+    if (B < 1 || B > 65535 || S < 1 || V < 1 || F < 1) throw std::invalid_argument(std::string(who) + ": bad sizes");
+}
+void check_workspace(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+    if (!ws || ws_bytes < need) throw std::invalid_argument(std::string(who) + ": workspace smaller than " + who + "'s workspace query");
+    if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) throw std::invalid_argument(std::string(who) + ": workspace must be 16-byte aligned");
+}
+}  // namespace
+
+size_t icn_mesh_sample_workspace_bytes(int B, int S, int V, int F) {
+    return (B < 1 || B > 65535 || S < 1 || V < 1 || F < 1) ? 0 : icn::mesh_sample_cdf_bytes(B, F);
+}
+
+int icn_mesh_sample_fwd(const float* vertices, const int32_t* faces, const float* u, int B, int S, int V, int F, float* points,
+                        int32_t* face, float* weights, void* ws, size_t ws_bytes, void* stream) {
+    try {
+        if (!vertices || !faces || !u || !points || !face || !weights) throw std::invalid_argument("icn_mesh_sample_fwd: null pointer");
+        check_mesh_sample("icn_mesh_sample_fwd", B, S, V, F);
+        check_workspace("icn_mesh_sample_fwd", ws, ws_bytes, icn::mesh_sample_cdf_bytes(B, F));
+        icn::launch_mesh_sample_fwd(vertices, faces, u, B, S, V, F, points, face, weights, ws, static_cast<hipStream_t>(stream));
+        ICN_HIP(hipGetLastError());
+        return 0;
+    } catch (const std::exception& e) {
+        return fail(e.what());
+    }
+}
+
+size_t icn_mesh_sample_bwd_workspace_bytes(int B, int S, int V, int F) {
+    return (B < 1 || B > 65535 || S < 1 || V < 1 || F < 1) ? 0 : icn::mesh_sample_bwd_record_bytes(B, S);
+}
+
+int icn_mesh_sample_bwd(const int32_t* faces, const int32_t* face, const float* weights, const float* dpoints, int B, int S, int V,
+                        int F, float* dvertices, void* ws, size_t ws_bytes, void* stream) {
+    try {
+        if (!faces || !face || !weights || !dpoints || !dvertices) throw std::invalid_argument("icn_mesh_sample_bwd: null pointer");
+        check_mesh_sample("icn_mesh_sample_bwd", B, S, V, F);
+        check_workspace("icn_mesh_sample_bwd", ws, ws_bytes, icn::mesh_sample_bwd_record_bytes(B, S));
+        icn::launch_mesh_sample_bwd(faces, face, weights, dpoints, B, S, V, F, dvertices, ws, static_cast<hipStream_t>(stream));
         ICN_HIP(hipGetLastError());
         return 0;
     } catch (const std::exception& e) {

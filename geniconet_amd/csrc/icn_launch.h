@@ -231,6 +231,17 @@ size_t point_to_mesh_grid_bytes(int B, int F);
 hipError_t launch_point_to_mesh_grid(const float* pts, const float* vts, const int32_t* faces, int B, int P, int V, int F, float* dist,
                                      int32_t* face, int32_t* kind, void* ws, hipStream_t s);
 
+// area-weighted surface sampling (icn_sample.hip): points / face / weights of S samples per mesh from caller-supplied uniforms
+// u (B, S, 3).  ws: mesh_sample_cdf_bytes(B, F) bytes (the per-mesh CDF in double), 16-byte aligned.  Three launches on s.
+size_t mesh_sample_cdf_bytes(int B, int F);
+void launch_mesh_sample_fwd(const float* vts, const int32_t* faces, const float* u, int B, int S, int V, int F, float* points,
+                            int32_t* face, float* weights, void* ws, hipStream_t s);
+// its backward to the vertices (face choice constant): ws mesh_sample_bwd_record_bytes(B, S) bytes, 16-byte aligned.  Fixed
+// summation order, no atomics.
+size_t mesh_sample_bwd_record_bytes(int B, int S);
+void launch_mesh_sample_bwd(const int32_t* faces, const int32_t* face, const float* weights, const float* dpoints, int B, int S, int V,
+                            int F, float* dvts, void* ws, hipStream_t s);
+
 // developer routing flags (ICN_DEBUG / icn_set_debug_flags): 16 = convs on k_gather_gemm, 32 = wgrads on k_wgrad,
 // 128 = no stream-K, 256 = fault injection: every stream-K finisher reports its partners lost (tests of the failure path),
 // 512 = masked launches walk tiles b, b + G, ... instead of the balanced tile lists, 1024 = the sparse passes of the decoder-block
@@ -241,7 +252,7 @@ int debug_flags();
 int set_debug_flags(int flags);
 
 // ---- optional per-launch HIP-event timing of the MFMA kernels (bench.py's live roofline measurement) and of the
-// point-to-mesh kernels ----------
+// point-to-mesh and surface-sampling kernels ----------
 enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA_64x64, PROF_GG_128x128, PROF_GG_128x64,
                 PROF_GG_64x128, PROF_GG_64x64, PROF_WGD_128x128, PROF_WGD_128x64, PROF_WGD_64x128, PROF_WGD_64x64, PROF_WG_128x128,
                 PROF_WG_128x64, PROF_WG_64x128, PROF_WG_64x64,
@@ -256,6 +267,7 @@ enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA
                 PROF_WG7_B3, PROF_WGD_B3, PROF_WGDENSE_B3, PROF_B3_MASKED, PROF_B3SINGLEK_128x128, PROF_B3SINGLEK_128x64,
                 PROF_P2M, PROF_P2M_BWD_POINT, PROF_P2M_BWD_VERTEX,    // point-to-mesh distance and its backward (not MFMA; flops 0)
                 PROF_P2M_GRID_BOUNDS, PROF_P2M_GRID_COUNT, PROF_P2M_GRID_SCAN, PROF_P2M_GRID_FILL, PROF_P2M_GRID_QUERY,   // grid search
+                PROF_MSAMPLE_AREA, PROF_MSAMPLE_SCAN, PROF_MSAMPLE_POINT, PROF_MSAMPLE_BWD_RECORD, PROF_MSAMPLE_BWD_VERTEX,   // surface sampling
                 PROF_KINDS };
 extern const char* const PROF_NAMES[PROF_KINDS];
 void prof_mark_begin(int kind, double flops, hipStream_t s);   // no-ops unless profiling is on

@@ -429,15 +429,37 @@ class Surface_Loss(torch.nn.Module):
     values bit for bit; see Point2Mesh_Loss for when 'grid' pays).
     Cost on an MI355X at I5 / batch 36: NOT MEASURED yet -- `python tools/time_mesh_regularizer.py 10` records the regulariser kernels
     beside icn_p2p_loss_fwd / _bwd, the torch formulation on the device and this whole term for both searches into
-    profiles/mesh_regularizer.txt; whether the HIP regulariser beats the torch formulation on the device is therefore not known."""
+    profiles/mesh_regularizer.txt; whether the HIP regulariser beats the torch formulation on the device is therefore not known.
+
+    samples = S > 0 measures surfaces instead of vertices: with samples = 0 (the default: vertices only) the interior of a
+    face is never tested, so a surface that cuts a corner or bulges between its vertices goes unseen.  With S > 0 every forward draws
+    u = torch.rand((2, B, S, 3), generator=g, device=output.device) once, g a torch.Generator made on the first forward's device and
+    seeded with sample_seed (this draw order is the contract: a caller can rebuild the uniforms), and
+        l_p2m = mean p2m(sample_points(out mesh, u[0]), ref mesh)     gradient to the output through icn_mesh_sample_bwd
+        l_m2p = mean p2m(sample_points(ref mesh, u[1]), out mesh)     gradient through the mesh-vertex gradient of icn_point_to_mesh_bwd
+    with sampling.sample_points (area-weighted, HIP kernels icn_mesh_sample_*).  The regularisers, the reporting, the zero-factor rule
+    and the absence of host synchronisation are unchanged.  The loss is then a stochastic estimate: two forwards differ.  The
+    generator is a plain attribute: its state is not in state_dict, so a resumed run starts again from sample_seed.
+    Cost of samples > 0 on an MI355X at I5 / batch 36 with S = 10 242 (HIP events, median of 10, profiles/surface_samples.txt, from
+    `python tools/time_surface_samples.py 10`): the three forward kernels 0.07 ms together (area 0.008, scan 0.033, search + point
+    0.028), the backward 1.04 ms, nearly all of it k_msample_bwd_vertex (S V integer compares per mesh).  The torch formulation on the
+    device takes 0.36 ms forward and 1.04 ms forward + backward against 0.09 / 1.24 ms on the HIP path: the HIP forward is 4 x
+    faster, the fixed-order HIP backward is what buys run-to-run identity and is no faster than torch's atomic index_put.  This whole
+    term, forward + backward: samples = 0 33.2 ms ('brute') / 2.8 ms ('grid'); samples = S 38.4 / 4.2 ms, beside a training step of
+    6.6 ms."""
 
     def __init__(self, subdivisions, factor_p2m=1.0, factor_m2p=1.0, factor_edge=0.0, factor_ncons=0.0, factor_smooth=0.0,
-                 edge_length=0.0, search='brute'):
+                 edge_length=0.0, search='brute', samples=0, sample_seed=0):
         super().__init__()
         from .metrics import _check_search
         _check_search(search)
         _check_subdivisions('Surface_Loss', subdivisions)
         _check_factors('Surface_Loss', factor_p2m=factor_p2m, factor_m2p=factor_m2p)
+        if isinstance(samples, bool) or not isinstance(samples, int) or samples < 0:
+            raise ValueError('%s: samples must be a non-negative integer, got %r' % (type(self).__name__, samples))
+        if isinstance(sample_seed, bool) or not isinstance(sample_seed, int):
+            raise ValueError('%s: sample_seed must be an integer, got %r' % (type(self).__name__, sample_seed))
+        self.samples, self.sample_seed, self._sample_generator = samples, sample_seed, None
         self.subdivisions, self.search = subdivisions, search
         self.factor_p2m, self.factor_m2p = factor_p2m, factor_m2p
         self.regularizer = Mesh_Regularizer(subdivisions, factor_edge, factor_ncons, factor_smooth, edge_length)
@@ -448,8 +470,16 @@ class Surface_Loss(torch.nn.Module):
         self.register_buffer('ico_faces', torch.from_numpy(faces).to(torch.int32))
         self.last_p2m = self.last_m2p = self.last_reg = self.last_loss_total = 0
 
+    def _draw_uniforms(self, B, device):
+        """The (2, B, S, 3) uniforms of one forward, from the generator seeded with sample_seed on the first forward's device."""
+        if self._sample_generator is None or self._sample_generator.device != device:
+            self._sample_generator = torch.Generator(device=device)
+            self._sample_generator.manual_seed(self.sample_seed)
+        return torch.rand((2, B, self.samples, 3), generator=self._sample_generator, device=device)
+
     def forward(self, output, target):
         from .metrics import _point_to_mesh_unchecked
+        from .sampling import _sample_points_unchecked
         n = 2 ** self.subdivisions
         if output.dim() != 4 or tuple(output.shape[1:]) != (3, 5 * n, 2 * n) or output.shape[0] < 1:
             raise ValueError('Surface_Loss: expected output (B, 3, %d, %d), got %s' % (5 * n, 2 * n, tuple(output.shape)))
@@ -460,10 +490,16 @@ class Surface_Loss(torch.nn.Module):
         out = grid_to_vertices(output, self.subdivisions)
         ref = target[:, 0:3].transpose(1, 2).contiguous().to(out.dtype)
         faces = self.ico_faces if self.ico_faces.device == out.device else self.ico_faces.to(out.device)
+        p_out, p_ref = out, ref                                               # the points measured against the other surface
+        u = self._draw_uniforms(out.shape[0], out.device) if self.samples else None
         with torch.set_grad_enabled(grad and self.factor_p2m != 0):
-            l_p2m = _point_to_mesh_unchecked(out, ref, faces, self.search)[0].mean()
+            if u is not None:
+                p_out = _sample_points_unchecked(out, faces, u[0])[0]
+            l_p2m = _point_to_mesh_unchecked(p_out, ref, faces, self.search)[0].mean()
         with torch.set_grad_enabled(grad and self.factor_m2p != 0):
-            l_m2p = _point_to_mesh_unchecked(ref, out, faces, self.search)[0].mean()
+            if u is not None:
+                p_ref = _sample_points_unchecked(ref, faces, u[1])[0]
+            l_m2p = _point_to_mesh_unchecked(p_ref, out, faces, self.search)[0].mean()
         l_reg = self.regularizer(output)
         loss = self.factor_p2m * l_p2m + self.factor_m2p * l_m2p + l_reg
         self.last_p2m, self.last_m2p, self.last_reg = l_p2m.detach(), l_m2p.detach(), l_reg.detach()
@@ -526,8 +562,9 @@ class SurfaceKLD_Loss(Surface_Loss, KLD_Loss):
     """Surface_Loss of the reconstruction + factor_kl * KLD, for (recon, mu, logvar) outputs -- as P2PKLD_Loss is to P2P_Loss."""
 
     def __init__(self, subdivisions, factor_p2m=1.0, factor_m2p=1.0, factor_edge=0.0, factor_ncons=0.0, factor_smooth=0.0,
-                 edge_length=0.0, search='brute', factor_kl=1.0):
-        super().__init__(subdivisions, factor_p2m, factor_m2p, factor_edge, factor_ncons, factor_smooth, edge_length, search)
+                 edge_length=0.0, search='brute', factor_kl=1.0, samples=0, sample_seed=0):
+        super().__init__(subdivisions, factor_p2m, factor_m2p, factor_edge, factor_ncons, factor_smooth, edge_length, search,
+                         samples=samples, sample_seed=sample_seed)
         _check_factors('SurfaceKLD_Loss', factor_kl=factor_kl)
         self.factor_kl = factor_kl
 

@@ -82,7 +82,8 @@ def build_criterion(params, device):
         kw = dict(factor_p2m=ico.get('factor_p2m', 1.0), factor_m2p=ico.get('factor_m2p', 1.0),
                   factor_edge=ico.get('factor_edge', 0.0), factor_ncons=ico.get('factor_ncons', 0.0),
                   factor_smooth=ico.get('factor_smooth', 0.0), edge_length=ico.get('edge_length', 0.0),
-                  search=ico.get('p2m_search', 'brute'))
+                  search=ico.get('p2m_search', 'brute'), samples=ico.get('surface_samples', 0),
+                  sample_seed=ico.get('surface_sample_seed', 0))
         if loss_kind == 'surface':
             crit = losses.Surface_Loss(ico['subdivisions'], **kw)
         else:
@@ -107,6 +108,8 @@ class Trainer:
             self.model = self.model.to(memory_format=torch.channels_last)
         self.criterion = criterion if criterion is not None else build_criterion(params, self.device)
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        if self.world > 1 and getattr(self.criterion, 'samples', 0):
+            self.criterion.sample_seed += dist.get_rank()           # every rank draws its own surface samples (before the first forward)
         self.net = self.model
         if force_ddp is None:
             force_ddp = force_ddp_requested()

@@ -262,6 +262,39 @@ size_t icn_point_to_mesh_grid_workspace_bytes(int B, int P, int V, int F);
 int icn_point_to_mesh_grid(const float* points, const float* vertices, const int32_t* faces, int B, int P, int V, int F, float* dist2,
                            int32_t* face, int32_t* kind, void* ws, size_t ws_bytes, void* stream);
 
+/* Area-weighted surface sampling (an addition within ABI 9; what kaolin's sample_points / pytorch3d's sample_points_from_meshes
+ * compute): S points per mesh of vertices (B, V, 3) / faces (F, 3) (shared by the batch) from uniforms u (B, S, 3) in [0, 1) that the
+ * CALLER draws -- the kernels draw no random numbers, the outputs are a pure function of the inputs.  Per mesh:
+ *   A_f = 0.5 |(v1 - v0) x (v2 - v0)| in fp32 with every product of the cross product rounded on its own (a face with two coincident
+ *   vertices has area exactly 0);  c_f = A_0 + ... + A_f accumulated in double in a fixed order, T = c_{F-1};
+ *   face_s = the smallest f with c_f > (double) u[s,0] T, so a zero-area face is never chosen while T > 0 (for u[s,0] = 1, where no
+ *   such f exists, the last face of positive area); every sample takes face 0 if T is not a positive finite number.  (The parallel
+ *   scan adds neighbouring c_f in different orders; its sums are exact, and the statements above with them, while the non-zero areas of
+ *   a mesh lie within a factor 2^29 / F of each other -- beyond that they hold up to a double ulp of T);
+ *   r = sqrt(u[s,1]), weights_s = (1 - r, r (1 - u[s,2]), r u[s,2]), points_s = sum_k weights[s,k] v_k of that face.
+ * Components of u outside [0, 1] are clamped and NaN counts as 0.  A face with a vertex id outside [0, V) counts as area 0 and, if
+ * it is taken all the same (face 0 of a mesh without area), gives a zero point and zero weights; nothing is read out of bounds.
+ * points (B, S, 3), face (B, S) int32, weights (B, S, 3).  ws: icn_mesh_sample_workspace_bytes(B, S, V, F) bytes (host-only query;
+ * 0 for sizes the call would reject; 8 B F bytes rounded up to 16), 16-byte aligned, owned by the caller; contents need not survive
+ * the call.  Three launches on `stream`, no allocation, no synchronisation, no atomics: bit-identical run to run.  B <= 65535 per
+ * call (the batch index is gridDim.y).  0 on success, negative with icn_last_error() otherwise (arguments are checked before any
+ * device call). */
+size_t icn_mesh_sample_workspace_bytes(int B, int S, int V, int F);
+int icn_mesh_sample_fwd(const float* vertices, const int32_t* faces, const float* u, int B, int S, int V, int F, float* points,
+                        int32_t* face, float* weights, void* ws, size_t ws_bytes, void* stream);
+
+/* Backward of icn_mesh_sample_fwd to the vertices, through the weights with the face choice held constant (as kaolin and pytorch3d
+ * differentiate their samplers):  dvertices[b, faces[face[b,s], k]] += weights[b,s,k] dpoints[b,s].  face / weights: the forward's
+ * outputs; dpoints (B, S, 3): the upstream gradient; dvertices (B, V, 3) is written whole.  Summed in a fixed order (per vertex, by
+ * sample index, then vertex 0, 1, 2 of the face; no floating-point atomics): bit-identical run to run, and a vertex no sample
+ * touches gets an exact zero.  A sample whose face id is outside [0, F) or whose face has a vertex id outside [0, V) contributes
+ * nothing, and nothing is read out of bounds.  S V integer compares per mesh.
+ * ws: icn_mesh_sample_bwd_workspace_bytes(B, S, V, F) bytes (host-only query; 0 for sizes the call would reject; 40 B S), 16-byte
+ * aligned, owned by the caller.  Two launches on `stream`.  B <= 65535 per call.  0 on success, negative with icn_last_error(). */
+size_t icn_mesh_sample_bwd_workspace_bytes(int B, int S, int V, int F);
+int icn_mesh_sample_bwd(const int32_t* faces, const int32_t* face, const float* weights, const float* dpoints, int B, int S, int V,
+                        int F, float* dvertices, void* ws, size_t ws_bytes, void* stream);
+
 /* Adam step (reference run.py:253 `optimizer.step()` on the optimiser of run.py:446, torch.optim.Adam without amsgrad /
  * maximize) over `count` fp32 tensors, one launch per 96 tensors that share a step count (normally: one launch).  The four pointer arrays and numel / step_size / bc2_sqrt
  * are HOST arrays of length count; the pointers in them are device pointers (param, grad, exp_avg, exp_avg_sq of tensor i,
@@ -320,7 +353,7 @@ long icn_table_upconv_bwd(int r_in, int corner_mode, int32_t* idx, float* coef, 
  * does not exist for this (r_in, stride): P_out % 16 != 0 or a union that does not fit. */
 long icn_table_wgrad7(int r_in, int stride, int corner_mode, int32_t* rows, size_t cap_rows, uint16_t* pos, size_t cap_pos, int* meta);
 
-/* Optional diagnostics: HIP-event timing of every MFMA kernel launch (and, ABI 8, of k_point_to_mesh and its two backward kernels, ABI 9, of the five k_p2m_grid_* kernels,
+/* Optional diagnostics: HIP-event timing of every MFMA kernel launch (and, ABI 8, of k_point_to_mesh and its two backward kernels, ABI 9, of the five k_p2m_grid_* kernels and of the five k_msample_* kernels,
  * with total_flops 0) between start and stop, on the launch stream.  `stop` synchronises the device and returns the number of entries written (one per kernel that ran).
  * total_flops counts what a launch multiplies: 2*7*Cin*Cout*B*P_out per pass of an ordinary convolution (= its algorithmic
  * FLOPs; the small virtual-row launch of a stride-1 bwd-data adds time, not FLOPs); the composite icn_upconv_* launches execute
