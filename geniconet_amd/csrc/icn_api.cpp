@@ -730,7 +730,7 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_p2m_grid_bounds", "k_p2m_grid_count", "k_p2m_grid_scan", "k_p2m_grid_fill",
                                             "k_p2m_grid_query",
                                             "k_msample_area", "k_msample_scan", "k_msample_point", "k_msample_bwd_record",
-                                            "k_msample_bwd_vertex"};
+                                            "k_msample_bwd_vertex"};   // both ..._bwd_vertex: k_vertex_scatter, by its caller
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1230,17 +1230,33 @@ int icn_upsample_bwd(const float* dy, float* dx, int B, int C, int r_in, int cor
     }
 }
 
+// ---- argument checks shared by the loss, point-to-mesh and sampling entries; the ..._ok forms are what their workspace queries ask
+namespace {
+bool grid_batch_ok(int B, int r) { return B >= 1 && r >= 0 && r <= 10; }
+void check_grid_batch(const char* who, int B, int r) {              // a batch of icosahedral grids whose vertices an int32 indexes
+    if (!grid_batch_ok(B, r)) throw std::invalid_argument(std::string(who) + ": bad B / subdivisions");
+    if ((size_t)B * (icn::pixels(r) + 2) >= (size_t)1 << 31) throw std::invalid_argument(std::string(who) + ": B * vertices exceeds int32");
+}
+bool mesh_sizes_ok(int B, int N, int V, int F) { return !(B < 1 || B > 65535 || N < 1 || V < 1 || F < 1); }   // B is gridDim.y
+void check_mesh_sizes(const char* who, int B, int N, int V, int F) {
+    if (!mesh_sizes_ok(B, N, V, F)) throw std::invalid_argument(std::string(who) + ": bad sizes");
+}
+void check_workspace(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+    if (!ws || ws_bytes < need) throw std::invalid_argument(std::string(who) + ": workspace smaller than " + who + "'s workspace query");
+    if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) throw std::invalid_argument(std::string(who) + ": workspace must be 16-byte aligned");
+}
+}  // namespace
+
 // ---- point-to-point loss -----------------------------------------------------------------------------------------
 size_t icn_p2p_loss_workspace_floats(int B, int r) {
-    return (B < 1 || r < 0 || r > 10) ? 0 : (size_t)3 * icn::p2p_loss_blocks(B, icn::pixels(r));
+    return grid_batch_ok(B, r) ? (size_t)3 * icn::p2p_loss_blocks(B, icn::pixels(r)) : 0;
 }
 
 int icn_p2p_loss_fwd(const float* grid, const float* target, int B, int r, float f_pos, float f_nor, float f_lap, int lap_mode,
                      float* terms, float* ws, void* stream) {
     try {
         if (!grid || !target || !terms || !ws) throw std::invalid_argument("icn_p2p_loss_fwd: null pointer");
-        if (B < 1 || r < 0 || r > 10) throw std::invalid_argument("icn_p2p_loss_fwd: bad B / subdivisions");
-        if ((size_t)B * (icn::pixels(r) + 2) >= (size_t)1 << 31) throw std::invalid_argument("icn_p2p_loss_fwd: B * vertices exceeds int32");
+        check_grid_batch("icn_p2p_loss_fwd", B, r);
         if (lap_mode < 0 || lap_mode > 3) throw std::invalid_argument("icn_p2p_loss_fwd: lap_mode must be a combination of ICN_LAP_*");
         icn::launch_p2p_loss_fwd(grid, target, vertex_faces(r), ws, terms, B, icn::pixels(r), 1 << r, f_pos, f_nor, f_lap, lap_mode,
                                  static_cast<hipStream_t>(stream));
@@ -1252,15 +1268,14 @@ int icn_p2p_loss_fwd(const float* grid, const float* target, int B, int r, float
 }
 
 size_t icn_p2p_loss_bwd_workspace_floats(int B, int r) {
-    return (B < 1 || r < 0 || r > 10) ? 0 : (size_t)6 * B * (icn::pixels(r) + 2);
+    return grid_batch_ok(B, r) ? (size_t)6 * B * (icn::pixels(r) + 2) : 0;
 }
 
 int icn_p2p_loss_bwd(const float* grid, const float* target, const float* upstream, int B, int r, float f_pos, float f_nor,
                      float f_lap, int lap_mode, float* dgrid, float* ws, void* stream) {
     try {
         if (!grid || !target || !upstream || !dgrid) throw std::invalid_argument("icn_p2p_loss_bwd: null pointer");
-        if (B < 1 || r < 0 || r > 10) throw std::invalid_argument("icn_p2p_loss_bwd: bad B / subdivisions");
-        if ((size_t)B * (icn::pixels(r) + 2) >= (size_t)1 << 31) throw std::invalid_argument("icn_p2p_loss_bwd: B * vertices exceeds int32");
+        check_grid_batch("icn_p2p_loss_bwd", B, r);
         if ((f_nor != 0.f || f_lap != 0.f) && !ws) throw std::invalid_argument("icn_p2p_loss_bwd: workspace needed for the mesh terms");
         if (lap_mode < 0 || lap_mode > 3) throw std::invalid_argument("icn_p2p_loss_bwd: lap_mode must be a combination of ICN_LAP_*");
         icn::launch_p2p_loss_bwd(grid, target, vertex_faces(r), upstream, f_pos, f_nor, f_lap, lap_mode, dgrid, ws, B, icn::pixels(r),
@@ -1275,15 +1290,13 @@ int icn_p2p_loss_bwd(const float* grid, const float* target, const float* upstre
 // ---- mesh regularisers of the surface loss ------------------------------------------------------------------------------
 namespace {
 void check_mesh_reg(const char* who, int B, int r, float edge_length) {
-    const std::string w(who);
-    if (B < 1 || r < 0 || r > 10) throw std::invalid_argument(w + ": bad B / subdivisions");
-    if ((size_t)B * (icn::pixels(r) + 2) >= (size_t)1 << 31) throw std::invalid_argument(w + ": B * vertices exceeds int32");
-    if (!(edge_length >= 0.f) || !std::isfinite(edge_length)) throw std::invalid_argument(w + ": edge_length must be finite and >= 0");
+    check_grid_batch(who, B, r);
+    if (!(edge_length >= 0.f) || !std::isfinite(edge_length)) throw std::invalid_argument(std::string(who) + ": edge_length must be finite and >= 0");
 }
 }  // namespace
 
 size_t icn_mesh_reg_workspace_floats(int B, int r) {
-    return (B < 1 || r < 0 || r > 10) ? 0 : (size_t)3 * icn::p2p_loss_blocks(B, icn::pixels(r));
+    return grid_batch_ok(B, r) ? (size_t)3 * icn::p2p_loss_blocks(B, icn::pixels(r)) : 0;
 }
 
 int icn_mesh_reg_fwd(const float* grid, int B, int r, float f_edge, float f_ncons, float f_smooth, float edge_length, float* terms,
@@ -1301,7 +1314,7 @@ int icn_mesh_reg_fwd(const float* grid, int B, int r, float f_edge, float f_ncon
 }
 
 size_t icn_mesh_reg_bwd_workspace_floats(int B, int r) {
-    return (B < 1 || r < 0 || r > 10) ? 0 : (size_t)3 * B * (icn::pixels(r) + 2);
+    return grid_batch_ok(B, r) ? (size_t)3 * B * (icn::pixels(r) + 2) : 0;
 }
 
 int icn_mesh_reg_bwd(const float* grid, const float* upstream, int B, int r, float f_edge, float f_ncons, float f_smooth,
@@ -1370,7 +1383,7 @@ int icn_point_to_mesh(const float* points, const float* vertices, const int32_t*
                       int32_t* face, int32_t* kind, void* stream) {
     try {
         if (!points || !vertices || !faces || !dist2 || !face || !kind) throw std::invalid_argument("icn_point_to_mesh: null pointer");
-        if (B < 1 || B > 65535 || P < 1 || V < 1 || F < 1) throw std::invalid_argument("icn_point_to_mesh: bad sizes");
+        check_mesh_sizes("icn_point_to_mesh", B, P, V, F);
         icn::launch_point_to_mesh(points, vertices, faces, B, P, V, F, dist2, face, kind, static_cast<hipStream_t>(stream));
         ICN_HIP(hipGetLastError());
         return 0;
@@ -1380,7 +1393,7 @@ int icn_point_to_mesh(const float* points, const float* vertices, const int32_t*
 }
 
 size_t icn_point_to_mesh_bwd_workspace_bytes(int B, int P, int V, int F) {
-    return (B < 1 || B > 65535 || P < 1 || V < 1 || F < 1) ? 0 : icn::point_to_mesh_bwd_record_bytes(B, P);
+    return mesh_sizes_ok(B, P, V, F) ? icn::vertex_records_bytes((size_t)B * P) : 0;
 }
 
 int icn_point_to_mesh_bwd(const float* points, const float* vertices, const int32_t* faces, const int32_t* face, const int32_t* kind,
@@ -1388,12 +1401,8 @@ int icn_point_to_mesh_bwd(const float* points, const float* vertices, const int3
                           void* stream) {
     try {
         if (!points || !vertices || !faces || !face || !kind || !ddist) throw std::invalid_argument("icn_point_to_mesh_bwd: null pointer");
-        if (B < 1 || B > 65535 || P < 1 || V < 1 || F < 1) throw std::invalid_argument("icn_point_to_mesh_bwd: bad sizes");
-        if (dvertices) {
-            if (!ws || ws_bytes < icn::point_to_mesh_bwd_record_bytes(B, P))
-                throw std::invalid_argument("icn_point_to_mesh_bwd: workspace smaller than icn_point_to_mesh_bwd_workspace_bytes");
-            if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) throw std::invalid_argument("icn_point_to_mesh_bwd: workspace must be 16-byte aligned");
-        }
+        check_mesh_sizes("icn_point_to_mesh_bwd", B, P, V, F);
+        if (dvertices) check_workspace("icn_point_to_mesh_bwd", ws, ws_bytes, icn::vertex_records_bytes((size_t)B * P));
         if (!dpoints && !dvertices) return 0;                        // no gradient asked for
         icn::launch_point_to_mesh_bwd(points, vertices, faces, face, kind, ddist, B, P, V, F, dpoints, dvertices, ws,
                                       static_cast<hipStream_t>(stream));
@@ -1405,17 +1414,15 @@ int icn_point_to_mesh_bwd(const float* points, const float* vertices, const int3
 }
 
 size_t icn_point_to_mesh_grid_workspace_bytes(int B, int P, int V, int F) {
-    return (B < 1 || B > 65535 || P < 1 || V < 1 || F < 1) ? 0 : icn::point_to_mesh_grid_bytes(B, F);
+    return mesh_sizes_ok(B, P, V, F) ? icn::point_to_mesh_grid_bytes(B, F) : 0;
 }
 
 int icn_point_to_mesh_grid(const float* points, const float* vertices, const int32_t* faces, int B, int P, int V, int F, float* dist2,
                            int32_t* face, int32_t* kind, void* ws, size_t ws_bytes, void* stream) {
     try {
         if (!points || !vertices || !faces || !dist2 || !face || !kind) throw std::invalid_argument("icn_point_to_mesh_grid: null pointer");
-        if (B < 1 || B > 65535 || P < 1 || V < 1 || F < 1) throw std::invalid_argument("icn_point_to_mesh_grid: bad sizes");
-        if (!ws || ws_bytes < icn::point_to_mesh_grid_bytes(B, F))
-            throw std::invalid_argument("icn_point_to_mesh_grid: workspace smaller than icn_point_to_mesh_grid_workspace_bytes");
-        if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) throw std::invalid_argument("icn_point_to_mesh_grid: workspace must be 16-byte aligned");
+        check_mesh_sizes("icn_point_to_mesh_grid", B, P, V, F);
+        check_workspace("icn_point_to_mesh_grid", ws, ws_bytes, icn::point_to_mesh_grid_bytes(B, F));
         ICN_HIP(icn::launch_point_to_mesh_grid(points, vertices, faces, B, P, V, F, dist2, face, kind, ws, static_cast<hipStream_t>(stream)));
         ICN_HIP(hipGetLastError());
         return 0;
@@ -1424,25 +1431,15 @@ int icn_point_to_mesh_grid(const float* points, const float* vertices, const int
     }
 }
 
-namespace {
-void check_mesh_sample(const char* who, int B, int S, int V, int F) {
-    if (B < 1 || B > 65535 || S < 1 || V < 1 || F < 1) throw std::invalid_argument(std::string(who) + ": bad sizes");
-}
-void check_workspace(const char* who, const void* ws, size_t ws_bytes, size_t need) {
-    if (!ws || ws_bytes < need) throw std::invalid_argument(std::string(who) + ": workspace smaller than " + who + "'s workspace query");
-    if (reinterpret_cast<uintptr_t>(ws) % 16 != 0) throw std::invalid_argument(std::string(who) + ": workspace must be 16-byte aligned");
-}
-}  // namespace
-
 size_t icn_mesh_sample_workspace_bytes(int B, int S, int V, int F) {
-    return (B < 1 || B > 65535 || S < 1 || V < 1 || F < 1) ? 0 : icn::mesh_sample_cdf_bytes(B, F);
+    return mesh_sizes_ok(B, S, V, F) ? icn::mesh_sample_cdf_bytes(B, F) : 0;
 }
 
 int icn_mesh_sample_fwd(const float* vertices, const int32_t* faces, const float* u, int B, int S, int V, int F, float* points,
                         int32_t* face, float* weights, void* ws, size_t ws_bytes, void* stream) {
     try {
         if (!vertices || !faces || !u || !points || !face || !weights) throw std::invalid_argument("icn_mesh_sample_fwd: null pointer");
-        check_mesh_sample("icn_mesh_sample_fwd", B, S, V, F);
+        check_mesh_sizes("icn_mesh_sample_fwd", B, S, V, F);
         check_workspace("icn_mesh_sample_fwd", ws, ws_bytes, icn::mesh_sample_cdf_bytes(B, F));
         icn::launch_mesh_sample_fwd(vertices, faces, u, B, S, V, F, points, face, weights, ws, static_cast<hipStream_t>(stream));
         ICN_HIP(hipGetLastError());
@@ -1453,15 +1450,15 @@ int icn_mesh_sample_fwd(const float* vertices, const int32_t* faces, const float
 }
 
 size_t icn_mesh_sample_bwd_workspace_bytes(int B, int S, int V, int F) {
-    return (B < 1 || B > 65535 || S < 1 || V < 1 || F < 1) ? 0 : icn::mesh_sample_bwd_record_bytes(B, S);
+    return mesh_sizes_ok(B, S, V, F) ? icn::vertex_records_bytes((size_t)B * S) : 0;
 }
 
 int icn_mesh_sample_bwd(const int32_t* faces, const int32_t* face, const float* weights, const float* dpoints, int B, int S, int V,
                         int F, float* dvertices, void* ws, size_t ws_bytes, void* stream) {
     try {
         if (!faces || !face || !weights || !dpoints || !dvertices) throw std::invalid_argument("icn_mesh_sample_bwd: null pointer");
-        check_mesh_sample("icn_mesh_sample_bwd", B, S, V, F);
-        check_workspace("icn_mesh_sample_bwd", ws, ws_bytes, icn::mesh_sample_bwd_record_bytes(B, S));
+        check_mesh_sizes("icn_mesh_sample_bwd", B, S, V, F);
+        check_workspace("icn_mesh_sample_bwd", ws, ws_bytes, icn::vertex_records_bytes((size_t)B * S));
         icn::launch_mesh_sample_bwd(faces, face, weights, dpoints, B, S, V, F, dvertices, ws, static_cast<hipStream_t>(stream));
         ICN_HIP(hipGetLastError());
         return 0;

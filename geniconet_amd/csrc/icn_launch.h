@@ -219,8 +219,7 @@ void launch_reparam_bwd(const float* dz, const float* logvar, const float* eps, 
 void launch_point_to_mesh(const float* pts, const float* vts, const int32_t* faces, int B, int P, int V, int F, float* dist,
                           int32_t* face, int32_t* kind, hipStream_t s);
 // its backward from the forward's (face, kind): dpts (B, P, 3) and / or dvts (B, V, 3), either may be null; ws (only read when
-// dvts is wanted): point_to_mesh_bwd_record_bytes(B, P) bytes, 16-byte aligned.  Fixed summation order, no atomics.
-size_t point_to_mesh_bwd_record_bytes(int B, int P);
+// dvts is wanted): vertex_records_bytes(B * P) bytes, 16-byte aligned.  Fixed summation order, no atomics.
 void launch_point_to_mesh_bwd(const float* pts, const float* vts, const int32_t* faces, const int32_t* face, const int32_t* kind,
                               const float* ddist, int B, int P, int V, int F, float* dpts, float* dvts, void* ws, hipStream_t s);
 
@@ -236,11 +235,15 @@ hipError_t launch_point_to_mesh_grid(const float* pts, const float* vts, const i
 size_t mesh_sample_cdf_bytes(int B, int F);
 void launch_mesh_sample_fwd(const float* vts, const int32_t* faces, const float* u, int B, int S, int V, int F, float* points,
                             int32_t* face, float* weights, void* ws, hipStream_t s);
-// its backward to the vertices (face choice constant): ws mesh_sample_bwd_record_bytes(B, S) bytes, 16-byte aligned.  Fixed
+// its backward to the vertices (face choice constant): ws vertex_records_bytes(B * S) bytes, 16-byte aligned.  Fixed
 // summation order, no atomics.
-size_t mesh_sample_bwd_record_bytes(int B, int S);
 void launch_mesh_sample_bwd(const int32_t* faces, const int32_t* face, const float* weights, const float* dpoints, int B, int S, int V,
                             int F, float* dvts, void* ws, hipStream_t s);
+
+// records -> vertices, the second pass of both backwards above (icn_sample.hip; the record set: icn_mesh_device.h): ws holds n
+// records for each of the B meshes, dvts (B, V, 3) is written everywhere.  One launch on s, timed as prof_kind.
+size_t vertex_records_bytes(size_t n);
+void launch_vertex_scatter(int prof_kind, void* ws, int B, int n, int V, float* dvts, hipStream_t s);
 
 // developer routing flags (ICN_DEBUG / icn_set_debug_flags): 16 = convs on k_gather_gemm, 32 = wgrads on k_wgrad,
 // 128 = no stream-K, 256 = fault injection: every stream-K finisher reports its partners lost (tests of the failure path),

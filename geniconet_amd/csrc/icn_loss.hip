@@ -4,11 +4,11 @@
 // normalisation are a parameter: lap_mode bit 0 = opposite sign (v - mean), bit 1 = valence-weighted (sum(ring) - k v)).
 // HBM/L2-bound, a few tens of microseconds; replaces ~25 torch launches per step.
 //
-//   v[b, i]   i < P: network output pixel i (channels-last (B, P, 3));  i = P, P + 1: N / S pole = mean of 5 corner pixels
+//   v[b, i]   vertex i of sample b: the pixels of the network output (B, P, 3) and the two poles (vertex(), icn_mesh_device.h)
 //   terms[0] = mean_{b,i,c} (v - t_pos)^2           terms[1] = mean_{b,i} (1 - cos(unit vertex normal, t_nor))
 //   terms[2] = mean_{b,i,c} (lap(v) - t_lap)^2      terms[3] = f_pos * terms[0] + f_nor * terms[1] + f_lap * terms[2]
 // target is (B, 9, V): rows 0:3 positions, 3:6 normals, 6:9 Laplacians (data.py:64-69).
-// Sums are two-level with fixed block size and a fixed tree (deterministic).
+// Sums are two-level with a fixed order (block_sum_store, then partials_sum in one block; deterministic).
 //
 // Backward (d terms[3] / d grid), all in gather form over the incident-face table, so no atomics and no write conflicts
 // (derivation and finite-difference check: oracle/loss_ref.py p2p_grad):
@@ -18,7 +18,7 @@
 //   normal   : w_i = sum of the face normals at i, u = w / |w|, c = u . t^ (t^ = t_nor / |t_nor|);
 //              h_i = d(1 - c_i) / d w_i = -(t^ - (u . t^) u) / |w_i|;  face (j, p, q): d/d v_j = (h_j + h_p + h_q) x (v_q - v_p);
 //              times f_nor / (B V).   Where a normalisation clamp is active (|w| <= 1e-10, |t_nor| <= 1e-8) h_i = 0.
-//   vertex -> grid: pixels directly; a pole is the mean of its 5 corner pixels, each gets a fifth of the pole's gradient.
+//   vertex -> grid: store_pixel_grad (icn_mesh_device.h).
 // k_p2p_bwd_prep stores c_i e_i / k_i and h_i per vertex (6 floats), k_p2p_bwd gathers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,37 +26,13 @@
 #include <algorithm>
 
 #include "icn_launch.h"
+#include "icn_mesh_device.h"
 
 namespace icn {
 
 namespace {
 
-struct f3 { float x, y, z; };
-__device__ __forceinline__ f3 operator-(f3 a, f3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ f3 operator+(f3 a, f3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ f3 cross(f3 a, f3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-
-__device__ __forceinline__ int pole_corner(int n, int k, int c) {      // reference ico_utils.py:10-24
-    return k == 0 ? (c * n) * 2 * n : ((c + 1) * n - 1) * 2 * n + (2 * n - 1);
-}
-
-// vertex j of sample b from the channels-last grid (B, P, 3); poles: sum of the 5 corners / 5 (torch .mean)
-__device__ __forceinline__ f3 vertex(const float* __restrict__ g, int b, int j, int P, int n) {
-    if (j < P) {
-        const float* p = g + ((size_t)b * P + j) * 3;
-        return {p[0], p[1], p[2]};
-    }
-    f3 s = {0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-        const float* p = g + ((size_t)b * P + pole_corner(n, j - P, c)) * 3;
-        s = s + f3{p[0], p[1], p[2]};
-    }
-    return {s.x / 5.f, s.y / 5.f, s.z / 5.f};
-}
-
-constexpr int LOSS_BLOCK = 256;
+constexpr int LOSS_BLOCK = MESH_BLOCK;
 
 // factor c_i of the Laplacian convention: lap_i = c_i (mean(ring_i) - v_i)
 __device__ __forceinline__ float lap_factor(int lap_mode, int k) {
@@ -64,23 +40,31 @@ __device__ __forceinline__ float lap_factor(int lap_mode, int k) {
     return (lap_mode & 1) ? -w : w;
 }
 
-// fixed-order block sum of three values; result valid in thread 0
-__device__ __forceinline__ void block_sum3(float& a, float& b, float& c) {
-    __shared__ float red[3][LOSS_BLOCK / 64];
+// the fan of vertex i (position v) over the incident-face table vf[(i * 6 + f) * 2] = (p, q), p < 0: no face in slot f
+struct VertexFan {
+    f3 w, ring;                     // sum of the face normals (p - v) x (q - v), sum of the ring vertices p
+    int k;                          // valence
+};
+__device__ __forceinline__ VertexFan p2p_vertex_fan(const float* __restrict__ g, const int32_t* __restrict__ vf, int b, int i, f3 v,
+                                                    int P, int n) {
+    VertexFan fan = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, 0};
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        a += __shfl_xor(a, d, 64);
-        b += __shfl_xor(b, d, 64);
-        c += __shfl_xor(c, d, 64);
+    for (int f = 0; f < 6; ++f) {
+        const int p = vf[((size_t)i * 6 + f) * 2], q = vf[((size_t)i * 6 + f) * 2 + 1];
+        if (p < 0) continue;
+        const f3 vp = vertex(g, b, p, P, n), vq = vertex(g, b, q, P, n);
+        fan.w = fan.w + cross(vp - v, vq - v);
+        fan.ring = fan.ring + vp;
+        ++fan.k;
     }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][w] = a; red[1][w] = b; red[2][w] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        b = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-        c = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
-    }
+    return fan;
+}
+
+// lap_i = c_i (mean(ring_i) - v_i)
+__device__ __forceinline__ f3 p2p_laplacian(const VertexFan& fan, f3 v, int lap_mode) {
+    const float inv = 1.f / (float)fan.k, cf = lap_factor(lap_mode, fan.k);
+    const f3 um = f3{fan.ring.x * inv, fan.ring.y * inv, fan.ring.z * inv} - v;
+    return {cf * um.x, cf * um.y, cf * um.z};
 }
 
 __global__ __launch_bounds__(LOSS_BLOCK) void k_p2p_fwd(const float* __restrict__ g, const float* __restrict__ target,
@@ -88,7 +72,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_p2p_fwd(const float* __restrict_
                                                          int n, int lap_mode) {
     const int V = P + 2;
     const long idx = (long)blockIdx.x * LOSS_BLOCK + threadIdx.x;
-    float e_pos = 0.f, e_nor = 0.f, e_lap = 0.f;
+    float e[3] = {0.f, 0.f, 0.f};                                        // position, normal, Laplacian
     if (idx < (long)B * V) {
         const int b = (int)(idx / V), i = (int)(idx % V);
         const f3 v = vertex(g, b, i, P, n);
@@ -97,63 +81,38 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_p2p_fwd(const float* __restrict_
         const f3 tn = {t[(size_t)3 * V], t[(size_t)4 * V], t[(size_t)5 * V]};
         const f3 tl = {t[(size_t)6 * V], t[(size_t)7 * V], t[(size_t)8 * V]};
         const f3 d = v - tp;
-        e_pos = dot(d, d);
-        f3 vn = {0.f, 0.f, 0.f}, ring = {0.f, 0.f, 0.f};
-        int k = 0;
-#pragma unroll
-        for (int f = 0; f < 6; ++f) {
-            const int p = vf[((size_t)i * 6 + f) * 2], q = vf[((size_t)i * 6 + f) * 2 + 1];
-            if (p < 0) continue;
-            const f3 vp = vertex(g, b, p, P, n), vq = vertex(g, b, q, P, n);
-            vn = vn + cross(vp - v, vq - v);
-            ring = ring + vp;
-            ++k;
-        }
+        e[0] = dot(d, d);
+        const VertexFan fan = p2p_vertex_fan(g, vf, b, i, v, P, n);
+        const f3 vn = fan.w;
         const float len = fmaxf(sqrtf(dot(vn, vn)), 1e-10f);              // losses.py helper: vn / clamp_min(|vn|, eps)
         const f3 u = {vn.x / len, vn.y / len, vn.z / len};
         // F.cosine_similarity(u, tn, eps = 1e-8): each norm clamped separately
         const float cs = dot(u, tn) / (fmaxf(sqrtf(dot(u, u)), 1e-8f) * fmaxf(sqrtf(dot(tn, tn)), 1e-8f));
-        e_nor = 1.f - cs;
-        const float inv = 1.f / (float)k, cf = lap_factor(lap_mode, k);
-        const f3 um = f3{ring.x * inv, ring.y * inv, ring.z * inv} - v;
-        const f3 dl = f3{cf * um.x, cf * um.y, cf * um.z} - tl;
-        e_lap = dot(dl, dl);
+        e[1] = 1.f - cs;
+        const f3 dl = p2p_laplacian(fan, v, lap_mode) - tl;
+        e[2] = dot(dl, dl);
     }
-    block_sum3(e_pos, e_nor, e_lap);
-    if (threadIdx.x == 0) {
-        partial[(size_t)blockIdx.x * 3 + 0] = e_pos;
-        partial[(size_t)blockIdx.x * 3 + 1] = e_nor;
-        partial[(size_t)blockIdx.x * 3 + 2] = e_lap;
-    }
+    block_sum_store(e, partial + (size_t)blockIdx.x * 3);
 }
 
-// terms from the per-block partials: one block, lanes stride over the partials in double, fixed tree
+// terms from the per-block partials, one block
 // (also the finalize of the mesh regularisers below: count0 / count1 / count2 divide the three sums)
 __global__ __launch_bounds__(LOSS_BLOCK) void k_p2p_finalize(const float* __restrict__ partial, int nblocks, double count0,
                                                               double count1, double count2, float f_pos, float f_nor, float f_lap,
                                                               float* __restrict__ terms) {
-    __shared__ double red[3][LOSS_BLOCK];
-    double s[3] = {0.0, 0.0, 0.0};
-    for (int k = threadIdx.x; k < nblocks; k += LOSS_BLOCK)
-        for (int c = 0; c < 3; ++c) s[c] += (double)partial[(size_t)k * 3 + c];
-    for (int c = 0; c < 3; ++c) red[c][threadIdx.x] = s[c];
-    __syncthreads();
-    for (int d = LOSS_BLOCK / 2; d >= 1; d >>= 1) {
-        if ((int)threadIdx.x < d)
-            for (int c = 0; c < 3; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + d];
-        __syncthreads();
-    }
+    double s[3];
+    partials_sum(partial, nblocks, s);
     if (threadIdx.x == 0) {
-        const float l_pos = (float)(red[0][0] / count0), l_nor = (float)(red[1][0] / count1), l_lap = (float)(red[2][0] / count2);
+        const float l_pos = (float)(s[0] / count0), l_nor = (float)(s[1] / count1), l_lap = (float)(s[2] / count2);
         terms[0] = l_pos;
         terms[1] = l_nor;
         terms[2] = l_lap;
-        terms[3] = f_pos * l_pos + f_nor * l_nor + f_lap * l_lap;
+        terms[3] = fmaf(f_lap, l_lap, fmaf(f_pos, l_pos, f_nor * l_nor));     // spelled out: the bits must not depend on which products
+                                                                              // the compiler chooses to contract
     }
 }
 
-// d(f_pos * terms[0]) / d(grid) * upstream:  2 (v - t_pos) / (B V 3) at every pixel, plus a fifth of the pole's term at each
-// of its 5 corner pixels (the pole is their mean).  One thread per (sample, pixel): no write conflicts.
+// d(f_pos * terms[0]) / d(grid) * upstream, the per-vertex term 2 (v - t_pos) / (B V 3) with its constant factor applied last
 __global__ __launch_bounds__(LOSS_BLOCK) void k_p2p_bwd_pos(const float* __restrict__ g, const float* __restrict__ target,
                                                              const float* __restrict__ upstream, float scale,
                                                              float* __restrict__ dg, int B, int P, int n) {
@@ -161,23 +120,10 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_p2p_bwd_pos(const float* __restr
     const long idx = (long)blockIdx.x * LOSS_BLOCK + threadIdx.x;
     if (idx >= (long)B * P) return;
     const int b = (int)(idx / P), j = (int)(idx % P);
-    const float w = scale * upstream[0];
     const float* t = target + (size_t)b * 9 * V;
-    const float* p = g + ((size_t)b * P + j) * 3;
-    f3 d = {p[0] - t[j], p[1] - t[(size_t)V + j], p[2] - t[(size_t)2 * V + j]};
-    const int chart = 2 * n * n;                                         // pixels per chart
-    int pole = -1;
-    if (j % chart == 0) pole = 0;                                        // (row c*n, col 0): corner of the N pole
-    else if ((j + 1) % chart == 0) pole = 1;                             // (row (c+1)*n - 1, col 2n - 1): S pole
-    if (pole >= 0) {
-        const f3 vp = vertex(g, b, P + pole, P, n);
-        const f3 dp = {vp.x - t[P + pole], vp.y - t[(size_t)V + P + pole], vp.z - t[(size_t)2 * V + P + pole]};
-        d = d + f3{dp.x / 5.f, dp.y / 5.f, dp.z / 5.f};
-    }
-    float* o = dg + ((size_t)b * P + j) * 3;
-    o[0] = w * d.x;
-    o[1] = w * d.y;
-    o[2] = w * d.z;
+    store_pixel_grad(dg, b, j, P, n, scale * upstream[0], [&](int x) {
+        return vertex(g, b, x, P, n) - f3{t[x], t[(size_t)V + x], t[(size_t)2 * V + x]};
+    });
 }
 
 // per vertex: aux[0:3] = (lap - t_lap) / k,  aux[3:6] = h = d(1 - cos) / d w  (see the header comment)
@@ -192,20 +138,8 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_p2p_bwd_prep(const float* __rest
     const float* t = target + (size_t)b * 9 * V + i;
     const f3 tn = {t[(size_t)3 * V], t[(size_t)4 * V], t[(size_t)5 * V]};
     const f3 tl = {t[(size_t)6 * V], t[(size_t)7 * V], t[(size_t)8 * V]};
-    f3 w = {0.f, 0.f, 0.f}, ring = {0.f, 0.f, 0.f};
-    int k = 0;
-#pragma unroll
-    for (int f = 0; f < 6; ++f) {
-        const int p = vf[((size_t)i * 6 + f) * 2], q = vf[((size_t)i * 6 + f) * 2 + 1];
-        if (p < 0) continue;
-        const f3 vp = vertex(g, b, p, P, n), vq = vertex(g, b, q, P, n);
-        w = w + cross(vp - v, vq - v);
-        ring = ring + vp;
-        ++k;
-    }
-    const float inv = 1.f / (float)k, cf = lap_factor(lap_mode, k);
-    const f3 um = f3{ring.x * inv, ring.y * inv, ring.z * inv} - v;
-    const f3 e = f3{cf * um.x, cf * um.y, cf * um.z} - tl;
+    const VertexFan fan = p2p_vertex_fan(g, vf, b, i, v, P, n);
+    const f3 w = fan.w, e = p2p_laplacian(fan, v, lap_mode) - tl;
     f3 h = {0.f, 0.f, 0.f};
     const float wl = sqrtf(dot(w, w)), tl2 = sqrtf(dot(tn, tn));
     if (wl > 1e-10f && tl2 > 1e-8f) {
@@ -214,7 +148,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_p2p_bwd_prep(const float* __rest
         h = {-(th.x - c * u.x) / wl, -(th.y - c * u.y) / wl, -(th.z - c * u.z) / wl};
     }
     float* a = aux + (size_t)idx * 6;
-    const float ci = cf * inv;
+    const float ci = lap_factor(lap_mode, fan.k) * (1.f / (float)fan.k);
     a[0] = e.x * ci; a[1] = e.y * ci; a[2] = e.z * ci;
     a[3] = h.x; a[4] = h.y; a[5] = h.z;
 }
@@ -256,20 +190,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_p2p_bwd(const float* __restrict_
     const long idx = (long)blockIdx.x * LOSS_BLOCK + threadIdx.x;
     if (idx >= (long)B * P) return;
     const int b = (int)(idx / P), j = (int)(idx % P);
-    f3 d = vertex_grad(g, target, vf, aux, b, j, P, n, cp, cl, cn);
-    const int chart = 2 * n * n;
-    int pole = -1;
-    if (j % chart == 0) pole = 0;
-    else if ((j + 1) % chart == 0) pole = 1;
-    if (pole >= 0) {
-        const f3 dp = vertex_grad(g, target, vf, aux, b, P + pole, P, n, cp, cl, cn);
-        d = d + f3{dp.x / 5.f, dp.y / 5.f, dp.z / 5.f};
-    }
-    const float up = upstream[0];
-    float* o = dg + ((size_t)b * P + j) * 3;
-    o[0] = up * d.x;
-    o[1] = up * d.y;
-    o[2] = up * d.z;
+    store_pixel_grad(dg, b, j, P, n, upstream[0], [&](int x) { return vertex_grad(g, target, vf, aux, b, x, P, n, cp, cl, cn); });
 }
 
 }  // namespace
@@ -325,22 +246,12 @@ void launch_p2p_loss_bwd(const float* grid, const float* target, const int32_t* 
 //            enters its neighbours' g as the constant n_F / 1e-12).  With n_F = (v_p - v_j) x (v_q - v_j), dS / dv_j = sum over the faces
 //            (j, p, q) at j of H_F x (v_q - v_p); times f_ncons / (B E).  RECOMPUTED per vertex, no workspace: the neighbours of the face in
 //            slot f are slots f - 1 and f + 1 and, across (p_f, q_f), the face (q_f, p_f, x_f) -- the 1-ring and the six x suffice.
-//   vertex -> grid as above: a pole's gradient goes to its 5 corner pixels, a fifth each.  Every element of dgrid is written once.
+//   vertex -> grid as above (store_pixel_grad).
 // A term whose factor is 0 is skipped in the backward (no loads of x without the normal term, no prep pass without smoothness).
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 
 constexpr float MREG_EPS = 1e-12f;
-
-__device__ __forceinline__ f3 scaled(f3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-
-// Face normal for the 1e-12 clamp: every product rounded on its own.  Contracted to fma(a.y, b.z, -(a.z * b.y)), a x a is the
-// rounding error of one product, about 6e-8 |a|^2 and far above the clamp, so a face with two coincident vertices would pass for a
-// face with a direction; with both products rounded a x a is exactly 0, as in the torch formulation.
-__device__ __forceinline__ f3 face_normal(f3 a, f3 b) {
-#pragma clang fp contract(off)
-    return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
 
 // n / max(|n|, 1e-12); len = |n|
 __device__ __forceinline__ f3 unit_clamped(f3 nrm, float& len) {
@@ -397,12 +308,8 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_mreg_fwd(const float* __restrict
         const f3 u = scaled(ring, 1.f / (float)k) - v;
         e_sm = dot(u, u);
     }
-    block_sum3(e_edge, e_nc, e_sm);
-    if (threadIdx.x == 0) {
-        partial[(size_t)blockIdx.x * 3 + 0] = e_edge;
-        partial[(size_t)blockIdx.x * 3 + 1] = e_nc;
-        partial[(size_t)blockIdx.x * 3 + 2] = e_sm;
-    }
+    float e[3] = {e_edge, e_nc, e_sm};
+    block_sum_store(e, partial + (size_t)blockIdx.x * 3);
 }
 
 // aux[(b V + i) * 3 ..] = (mean(ring_i) - v_i) / k_i
@@ -496,20 +403,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_mreg_bwd(const float* __restrict
     const long idx = (long)blockIdx.x * LOSS_BLOCK + threadIdx.x;
     if (idx >= (long)B * P) return;
     const int b = (int)(idx / P), j = (int)(idx % P);
-    f3 d = mreg_vertex_grad(g, vs, aux, b, j, P, n, ce, L, cn, cs);
-    const int chart = 2 * n * n;
-    int pole = -1;
-    if (j % chart == 0) pole = 0;
-    else if ((j + 1) % chart == 0) pole = 1;
-    if (pole >= 0) {
-        const f3 dp = mreg_vertex_grad(g, vs, aux, b, P + pole, P, n, ce, L, cn, cs);
-        d = d + f3{dp.x / 5.f, dp.y / 5.f, dp.z / 5.f};
-    }
-    const float up = upstream[0];
-    float* o = dg + ((size_t)b * P + j) * 3;
-    o[0] = up * d.x;
-    o[1] = up * d.y;
-    o[2] = up * d.z;
+    store_pixel_grad(dg, b, j, P, n, upstream[0], [&](int x) { return mreg_vertex_grad(g, vs, aux, b, x, P, n, ce, L, cn, cs); });
 }
 
 }  // namespace
@@ -541,31 +435,19 @@ constexpr int KLD_MAX_BLOCKS = 1024;
 
 __global__ __launch_bounds__(LOSS_BLOCK) void k_kld_partial(const float* __restrict__ mu, const float* __restrict__ lv, size_t n,
                                                              float* __restrict__ partial) {
-    __shared__ float red[LOSS_BLOCK / 64];
-    float s = 0.f;
+    float s[1] = {0.f};
     for (size_t i = (size_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; i < n; i += (size_t)gridDim.x * LOSS_BLOCK) {
         const float m = mu[i], l = lv[i];
-        s += 1.f + l - m * m - __expf(l);
+        s[0] += 1.f + l - m * m - __expf(l);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    block_sum_store(s, partial + blockIdx.x);
 }
 
 __global__ __launch_bounds__(LOSS_BLOCK) void k_kld_finalize(const float* __restrict__ partial, int nblocks, double scale,
                                                               float* __restrict__ out) {
-    __shared__ double red[LOSS_BLOCK];
-    double s = 0.0;
-    for (int k = threadIdx.x; k < nblocks; k += LOSS_BLOCK) s += (double)partial[k];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = LOSS_BLOCK / 2; d >= 1; d >>= 1) {
-        if ((int)threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = (float)(red[0] * scale);
+    double s[1];
+    partials_sum(partial, nblocks, s);
+    if (threadIdx.x == 0) out[0] = (float)(s[0] * scale);
 }
 
 __global__ __launch_bounds__(LOSS_BLOCK) void k_kld_bwd(const float* __restrict__ mu, const float* __restrict__ lv,
@@ -744,27 +626,18 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_point_to_mesh(const float* __res
 //     d dist / d p = 2 (p - q)        d dist / d a = -2 wa (p - q)   (likewise b, c)
 // No second search: p - q and the weights are recomputed from the forward's (face, kind) with the expressions of tri_dist2: an edge
 // kind is the clamped projection on that segment (a zero-length edge is its point, weight 1 on its first vertex), kind 0 the plane.
-//   k_point_to_mesh_bwd_point   one thread per point: g = 2 ddist (p - q) -> dpoints; a record (the three vertex ids, g, the three
-//                               weights; id -1 where the weight is zero by construction) -> workspace, 40 bytes per point
-//   k_point_to_mesh_bwd_vertex  one thread per vertex: the records of its sample go through LDS in tiles of 256 points and every
-//                               thread adds those addressed to it IN POINT ORDER (then vertex 0, 1, 2 of the face) -- a fixed
-//                               order, no atomics, bit-identical run to run.  P * V integer compares per sample, one broadcast
-//                               ds_read_b128 per record and wave; a vertex no point selected gets an exact zero.
+//   k_point_to_mesh_bwd_point   one thread per point: g = 2 ddist (p - q) -> dpoints; a VertexRecords entry (icn_mesh_device.h: the
+//                               three vertex ids, -g, the three weights; id -1 where the weight is zero by construction) -> workspace
+//   launch_vertex_scatter       (icn_sample.hip) the records -> dvertices, summed per vertex in point order without atomics
 // A face index outside [0, F), a kind outside [0, 6] or a vertex id outside [0, V) gives that point a zero gradient (nothing
 // is read out of bounds).
 // ---------------------------------------------------------------------------------------------------------
-struct P2MRecords {                 // the caller's workspace, cut into three arrays of B * P entries (16-byte aligned base)
-    int4* id;                       // vertex ids of the face (or -1), .w unused
-    float4* gw;                     // g.x, g.y, g.z, weight of vertex 0
-    float2* w12;                    // weights of vertex 1 and 2
-};
-
 __global__ __launch_bounds__(LOSS_BLOCK) void k_point_to_mesh_bwd_point(const float* __restrict__ pts, const float* __restrict__ vts,
                                                                          const int32_t* __restrict__ faces,
                                                                          const int32_t* __restrict__ face,
                                                                          const int32_t* __restrict__ kind,
                                                                          const float* __restrict__ ddist, int P, int V, int F,
-                                                                         float* __restrict__ dpts, P2MRecords rec) {
+                                                                         float* __restrict__ dpts, VertexRecords rec) {
     const int bi = blockIdx.y, i = blockIdx.x * LOSS_BLOCK + threadIdx.x;
     if (i >= P) return;
     const size_t at = (size_t)bi * P + i;
@@ -810,43 +683,8 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_point_to_mesh_bwd_point(const fl
     if (dpts) { dpts[at * 3] = g.x; dpts[at * 3 + 1] = g.y; dpts[at * 3 + 2] = g.z; }
     if (rec.id) {
         rec.id[at] = make_int4(ia, ib, ic, -1);
-        rec.gw[at] = make_float4(g.x, g.y, g.z, wa);
+        rec.gw[at] = make_float4(-g.x, -g.y, -g.z, wa);
         rec.w12[at] = make_float2(wb, wc);
-    }
-}
-
-__global__ __launch_bounds__(LOSS_BLOCK) void k_point_to_mesh_bwd_vertex(P2MRecords rec, int P, int V, float* __restrict__ dvts) {
-    __shared__ int4 s_id[LOSS_BLOCK];
-    __shared__ float4 s_gw[LOSS_BLOCK];
-    __shared__ float2 s_w12[LOSS_BLOCK];
-    const int bi = blockIdx.y, j = blockIdx.x * LOSS_BLOCK + threadIdx.x;
-    const int me = j < V ? j : -2;                                         // -2 matches no record (unused ids are -1)
-    const size_t base = (size_t)bi * P;
-    float ax = 0.f, ay = 0.f, az = 0.f;
-    for (int p0 = 0; p0 < P; p0 += LOSS_BLOCK) {
-        __syncthreads();
-        const int i = p0 + threadIdx.x;
-        if (i < P) {
-            s_id[threadIdx.x] = rec.id[base + i];
-            s_gw[threadIdx.x] = rec.gw[base + i];
-            s_w12[threadIdx.x] = rec.w12[base + i];
-        }
-        __syncthreads();
-        const int np = min(LOSS_BLOCK, P - p0);                            // the same in every thread of the block
-        for (int t = 0; t < np; ++t) {
-            const int4 id = s_id[t];                                       // one address for the whole wave: a broadcast read
-            if (id.x == me || id.y == me || id.z == me) {
-                const float4 gw = s_gw[t];
-                const float2 w12 = s_w12[t];
-                if (id.x == me) { ax -= gw.w * gw.x; ay -= gw.w * gw.y; az -= gw.w * gw.z; }
-                if (id.y == me) { ax -= w12.x * gw.x; ay -= w12.x * gw.y; az -= w12.x * gw.z; }
-                if (id.z == me) { ax -= w12.y * gw.x; ay -= w12.y * gw.y; az -= w12.y * gw.z; }
-            }
-        }
-    }
-    if (j < V) {
-        float* o = dvts + ((size_t)bi * V + j) * 3;
-        o[0] = ax; o[1] = ay; o[2] = az;
     }
 }
 
@@ -861,7 +699,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_point_to_mesh_bwd_vertex(P2MReco
 //   k_p2m_grid_count   per triangle: centroid c (fp32), r = largest |vertex - c|, cell of c (clamped) or, if r > 2 h or mode 1, the
 //                      always-tested list (stored as cell G^3) -> tcell[f]; integer atomicAdd on the cell's count, integer
 //                      atomicMax (float bits, r >= 0) of r over the binned triangles -> rmax.
-//   k_p2m_grid_scan    exclusive scan of the G^3 + 1 counts in place: e[c] = first slot of cell c, e[G^3 + 1] = F.
+//   k_p2m_grid_scan    exclusive block_scan of the G^3 + 1 counts in place: e[c] = first slot of cell c, e[G^3 + 1] = F.
 //   k_p2m_grid_fill    slot = atomicAdd(e[c + 1]) (afterwards e[c + 1] is the END of cell c = the begin of c + 1, e[0] stays 0);
 //                      the triangle's three resolved vertices and its index go to the slot (three float4, 48 contiguous bytes: the
 //                      query reads a triangle with three 16-byte loads and no faces -> vertices double gather).
@@ -1010,34 +848,9 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_p2m_grid_count(const float* __re
     if ((threadIdx.x & 63) == 0 && r_binned > 0.f) atomicMax(hdr + 7, __float_as_uint(r_binned));   // r >= 0: bits order as values
 }
 
-// exclusive scan in place of e[1 .. n] (n = G^3 + 1 counts), one block per mesh, tiles of GRID_SCAN_BLOCK; e[0] stays 0
-__global__ __launch_bounds__(GRID_SCAN_BLOCK) void k_p2m_grid_scan(P2MGrid g) {
-    __shared__ int wsum[GRID_SCAN_BLOCK / 64];
-    int32_t* e = g.e + (size_t)blockIdx.x * g.e_stride + 1;
-    const int n = g.G * g.G * g.G + 1, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int carry = 0;
-    for (int base = 0; base < n; base += GRID_SCAN_BLOCK) {
-        const int i = base + threadIdx.x;
-        const int v = i < n ? e[i] : 0;
-        int x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < GRID_SCAN_BLOCK / 64; ++k) {
-            const int s = wsum[k];
-            if (k < w) before += s;
-            total += s;
-        }
-        if (i < n) e[i] = carry + before + x - v;
-        carry += total;
-        __syncthreads();
-    }
+// exclusive scan in place of e[1 .. n] (n = G^3 + 1 counts), one block per mesh; e[0] stays 0
+__global__ __launch_bounds__(SCAN_BLOCK) void k_p2m_grid_scan(P2MGrid g) {
+    block_scan<int32_t, false>(g.e + (size_t)blockIdx.x * g.e_stride + 1, g.G * g.G * g.G + 1);
 }
 
 __global__ __launch_bounds__(LOSS_BLOCK) void k_p2m_grid_fill(const float* __restrict__ vts, const int32_t* __restrict__ faces, int V,
@@ -1136,25 +949,14 @@ void launch_point_to_mesh(const float* pts, const float* vts, const int32_t* fac
     prof_mark_end(s);
 }
 
-size_t point_to_mesh_bwd_record_bytes(int B, int P) { return (size_t)B * P * (sizeof(int4) + sizeof(float4) + sizeof(float2)); }
-
 void launch_point_to_mesh_bwd(const float* pts, const float* vts, const int32_t* faces, const int32_t* face, const int32_t* kind,
                               const float* ddist, int B, int P, int V, int F, float* dpts, float* dvts, void* ws, hipStream_t s) {
-    P2MRecords rec = {nullptr, nullptr, nullptr};
-    if (dvts) {                                                            // ws: 16-byte aligned, point_to_mesh_bwd_record_bytes
-        const size_t n = (size_t)B * P;
-        rec.id = static_cast<int4*>(ws);
-        rec.gw = reinterpret_cast<float4*>(rec.id + n);
-        rec.w12 = reinterpret_cast<float2*>(rec.gw + n);
-    }
+    const VertexRecords rec = dvts ? vertex_records(ws, (size_t)B * P) : VertexRecords{nullptr, nullptr, nullptr};
     prof_mark_begin(PROF_P2M_BWD_POINT, 0.0, s);
     hipLaunchKernelGGL(k_point_to_mesh_bwd_point, dim3((P + LOSS_BLOCK - 1) / LOSS_BLOCK, B), dim3(LOSS_BLOCK), 0, s, pts, vts, faces,
                        face, kind, ddist, P, V, F, dpts, rec);
     prof_mark_end(s);
-    if (!dvts) return;
-    prof_mark_begin(PROF_P2M_BWD_VERTEX, 0.0, s);
-    hipLaunchKernelGGL(k_point_to_mesh_bwd_vertex, dim3((V + LOSS_BLOCK - 1) / LOSS_BLOCK, B), dim3(LOSS_BLOCK), 0, s, rec, P, V, dvts);
-    prof_mark_end(s);
+    if (dvts) launch_vertex_scatter(PROF_P2M_BWD_VERTEX, ws, B, P, V, dvts, s);
 }
 
 // G = round(sqrt(F / 16)) in [1, 64]: about 16 triangles per occupied cell of a closed surface (which fills ~6 G^2 of the G^3
@@ -1201,7 +1003,7 @@ hipError_t launch_point_to_mesh_grid(const float* pts, const float* vts, const i
     hipLaunchKernelGGL(k_p2m_grid_count, tri_grid, dim3(LOSS_BLOCK), 0, s, vts, faces, V, F, g);
     prof_mark_end(s);
     prof_mark_begin(PROF_P2M_GRID_SCAN, 0.0, s);
-    hipLaunchKernelGGL(k_p2m_grid_scan, dim3(B), dim3(GRID_SCAN_BLOCK), 0, s, g);
+    hipLaunchKernelGGL(k_p2m_grid_scan, dim3(B), dim3(SCAN_BLOCK), 0, s, g);
     prof_mark_end(s);
     prof_mark_begin(PROF_P2M_GRID_FILL, 0.0, s);
     hipLaunchKernelGGL(k_p2m_grid_fill, tri_grid, dim3(LOSS_BLOCK), 0, s, vts, faces, V, F, g);

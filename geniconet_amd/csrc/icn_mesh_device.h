@@ -1,0 +1,160 @@
+// Device code shared by the mesh kernels of icn_loss.hip and icn_sample.hip: 3-vectors, the pixel <-> vertex rule of the
+// icosahedral grid, fixed-order block reductions, the tiled block scan and the per-record vertex scatter's record set.
+// Everything here is inlined into its callers; every sum has a fixed order (bit-identical run to run).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace icn {
+
+constexpr int MESH_BLOCK = 256;              // workgroup of the reductions below (4 waves)
+constexpr int SCAN_BLOCK = 1024;             // workgroup = tile of block_scan
+
+// ---- vectors ---------------------------------------------------------------------------------------------------------------
+struct f3 { float x, y, z; };
+__device__ __forceinline__ f3 operator-(f3 a, f3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ f3 operator+(f3 a, f3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ f3 cross(f3 a, f3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ f3 scaled(f3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
+__device__ __forceinline__ f3 load3(const float* __restrict__ p) { return {p[0], p[1], p[2]}; }
+
+// Cross product with every product rounded on its own, for the zero test on a face normal (the 1e-12 clamp of the mesh
+// regularisers).  Contracted to fma(a.y, b.z, -(a.z * b.y)), a x a is the rounding error of one
+// product, about 6e-8 |a|^2 and far above the clamp, so a face with two coincident vertices would pass for a face with a
+// direction; with both products rounded a x a is exactly 0, as in the torch formulation.
+__device__ __forceinline__ f3 face_normal(f3 a, f3 b) {
+#pragma clang fp contract(off)
+    return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+
+// ---- pixels and vertices of the icosahedral grid (n = 2^r) ------------------------------------------------------------------
+// Vertex j < P is pixel j of the channels-last grid (B, P, 3); vertices P and P + 1 are the N / S pole, the mean of the 5 chart
+// corners pole_corner(n, k, 0..4) (reference ico_utils.py:10-24).  Backwards, a pole's gradient goes to those 5 pixels, a fifth each.
+__device__ __forceinline__ int pole_corner(int n, int k, int c) {
+    return k == 0 ? (c * n) * 2 * n : ((c + 1) * n - 1) * 2 * n + (2 * n - 1);
+}
+
+// the pole (0 N, 1 S) that pixel j is a corner of, or -1: the inverse of pole_corner (first / last pixel of a chart of 2 n^2)
+__device__ __forceinline__ int pole_of_pixel(int j, int n) {
+    const int chart = 2 * n * n;
+    return j % chart == 0 ? 0 : ((j + 1) % chart == 0 ? 1 : -1);
+}
+
+// vertex j of sample b; poles: sum of the 5 corners / 5 (torch .mean)
+__device__ __forceinline__ f3 vertex(const float* __restrict__ g, int b, int j, int P, int n) {
+    if (j < P) return load3(g + ((size_t)b * P + j) * 3);
+    f3 s = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 5; ++c) s = s + load3(g + ((size_t)b * P + pole_corner(n, j - P, c)) * 3);
+    return {s.x / 5.f, s.y / 5.f, s.z / 5.f};
+}
+
+// dg[b, j] = up * (grad(j) + grad(pole) / 5) for grad(x) = the gradient with respect to vertex x of sample b; one thread per
+// (sample, pixel), every element of dg written once
+template <class Grad>
+__device__ __forceinline__ void store_pixel_grad(float* __restrict__ dg, int b, int j, int P, int n, float up, Grad grad) {
+    __builtin_assume(j < P);                                             // a pixel: grad(j) needs no pole branch
+    f3 d = grad(j);
+    const int pole = pole_of_pixel(j, n);
+    if (pole >= 0) {
+        const f3 dp = grad(P + pole);
+        d = d + f3{dp.x / 5.f, dp.y / 5.f, dp.z / 5.f};
+    }
+    float* o = dg + ((size_t)b * P + j) * 3;
+    o[0] = up * d.x;
+    o[1] = up * d.y;
+    o[2] = up * d.z;
+}
+
+// ---- reductions -------------------------------------------------------------------------------------------------------------
+// Block sum of N values per thread in a fixed order (xor shuffles inside a wave, then a tree over the 4 wave totals);
+// thread 0 stores the N sums to out.  Every thread of the block calls it.
+template <int N>
+__device__ __forceinline__ void block_sum_store(float (&v)[N], float* __restrict__ out) {
+    __shared__ float red[N][MESH_BLOCK / 64];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+#pragma unroll
+        for (int c = 0; c < N; ++c) v[c] += __shfl_xor(v[c], d, 64);
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int c = 0; c < N; ++c) red[c][threadIdx.x >> 6] = v[c];
+    __syncthreads();
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int c = 0; c < N; ++c) out[c] = (red[c][0] + red[c][1]) + (red[c][2] + red[c][3]);
+}
+
+// Second level: one block sums nblocks rows of N partials in double (lanes stride over the rows, then a fixed tree); the N
+// sums are valid in thread 0.
+template <int N>
+__device__ __forceinline__ void partials_sum(const float* __restrict__ partial, int nblocks, double (&s)[N]) {
+    __shared__ double red[N][MESH_BLOCK];
+    for (int c = 0; c < N; ++c) s[c] = 0.0;
+    for (int k = threadIdx.x; k < nblocks; k += MESH_BLOCK)
+        for (int c = 0; c < N; ++c) s[c] += (double)partial[(size_t)k * N + c];
+    for (int c = 0; c < N; ++c) red[c][threadIdx.x] = s[c];
+    __syncthreads();
+    for (int d = MESH_BLOCK / 2; d >= 1; d >>= 1) {
+        if ((int)threadIdx.x < d)
+            for (int c = 0; c < N; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + d];
+        __syncthreads();
+    }
+    for (int c = 0; c < N; ++c) s[c] = red[c][0];
+}
+
+// ---- scan -------------------------------------------------------------------------------------------------------------------
+// Scan in place of c[0 .. n) by one block of SCAN_BLOCK threads over tiles of SCAN_BLOCK in a fixed order: a shuffle scan
+// inside each wave, the wave totals through LDS, a running carry from tile to tile.  Element i becomes
+// (carry + the waves before) + the wave's inclusive prefix, less its own value when exclusive: bit-identical run to run, also in
+// floating point, where neighbouring elements are summed in different association orders.
+template <typename T, bool INCLUSIVE>
+__device__ __forceinline__ void block_scan(T* __restrict__ c, int n) {
+    __shared__ T wsum[SCAN_BLOCK / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    T carry = 0;
+    for (int base = 0; base < n; base += SCAN_BLOCK) {
+        const int i = base + threadIdx.x;
+        const T v = i < n ? c[i] : T(0);
+        T x = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const T y = __shfl_up(x, d, 64);
+            if (lane >= d) x += y;
+        }
+        if (lane == 63) wsum[w] = x;
+        __syncthreads();
+        T before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < SCAN_BLOCK / 64; ++k) {
+            const T s = wsum[k];
+            if (k < w) before += s;
+            total += s;
+        }
+        if (i < n) c[i] = INCLUSIVE ? (carry + before) + x : (carry + before) + x - v;
+        carry += total;
+        __syncthreads();
+    }
+}
+
+// ---- records -> vertices ----------------------------------------------------------------------------------------------------
+// What a per-point (per-sample) backward leaves for launch_vertex_scatter (icn_sample.hip): record i of mesh b, at b * n + i,
+// adds w_k * g to vertex id_k of that mesh for k = 0, 1, 2; id -1 takes no part.  A workspace of vertex_records_bytes(B * n)
+// bytes, 16-byte aligned, cut into three arrays of B * n entries.
+struct VertexRecords {
+    int4* id;                       // vertex ids of the face (or -1), .w unused
+    float4* gw;                     // g.x, g.y, g.z, weight of vertex 0
+    float2* w12;                    // weights of vertex 1 and 2
+};
+constexpr size_t VERTEX_RECORD_BYTES = sizeof(int4) + sizeof(float4) + sizeof(float2);      // 40
+
+inline VertexRecords vertex_records(void* ws, size_t n) {
+    VertexRecords rec;
+    rec.id = static_cast<int4*>(ws);
+    rec.gw = reinterpret_cast<float4*>(rec.id + n);
+    rec.w12 = reinterpret_cast<float2*>(rec.gw + n);
+    return rec;
+}
+
+}  // namespace icn

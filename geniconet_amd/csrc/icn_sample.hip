@@ -2,11 +2,11 @@
 // kaolin's sample_points / pytorch3d's sample_points_from_meshes draw, from uniforms the CALLER supplies -- the kernels draw no
 // random numbers, so every output is a pure function of the inputs.  vertices (B, V, 3), faces (F, 3) shared by the batch,
 // u (B, S, 3).  Per mesh (blockIdx.y):
-//   k_msample_area    A_f = 0.5 |(v1 - v0) x (v2 - v0)| in fp32, every product of the cross product rounded on its own (no
-//                     contraction into an fma), so a face with two coincident vertices has area exactly 0 -> c[f] as a double.
-//                     A face with a vertex id outside [0, V) counts as area 0.
-//   k_msample_scan    inclusive scan of c in place, in double, one workgroup per mesh over tiles of 1024 in a fixed order
-//                     (wave scan, wave totals, running carry): c_f = A_0 + ... + A_f, T = c_{F - 1}.  Bit-identical run to run.
+//   k_msample_area    A_f = 0.5 |(v1 - v0) x (v2 - v0)| in fp32 -> c[f] as a double.  The cross product is evaluated with one fma per
+//                     component (see the kernel), so a face with v1 = v0 or v2 = v0 has area exactly 0, while v1 = v2 leaves a
+//                     rounding error of about 6e-8 |v1 - v0|^2; the torch formulation (sampling.py) rounds every product and gets
+//                     0 there too.  A face with a vertex id outside [0, V) counts as area 0.
+//   k_msample_scan    inclusive block_scan of c in place, in double, one workgroup per mesh: c_f = A_0 + ... + A_f, T = c_{F - 1}.
 //                     Neighbouring c_f are summed in different association orders.  The areas are fp32 values, so every partial sum
 //                     is exact in double -- c is then non-decreasing and constant across a zero-area face, whatever the order --
 //                     while the largest and the smallest non-zero area of a mesh lie within a factor 2^29 / F of each other
@@ -19,22 +19,19 @@
 //                     face 0.  r = sqrt(u1), weights (1 - r, r (1 - u2), r u2), point = the weighted vertices.
 // Backward (to the vertices through the weights, the face choice held constant): dvertices[b, faces[face_s, k]] += w[s, k] dpoints[s].
 //   k_msample_bwd_record  one thread per sample: the three vertex ids (-1 where the face or a vertex id is out of range: such a sample
-//                         contributes nothing and nothing is read out of bounds), dpoints and the weights -> workspace, 40 bytes
-//   k_msample_bwd_vertex  one thread per vertex: the records of its mesh go through LDS in tiles of 256 samples and every thread
-//                         adds those addressed to it IN SAMPLE ORDER (then vertex 0, 1, 2 of the face) -- the scheme of
-//                         k_point_to_mesh_bwd_vertex (icn_loss.hip): a fixed order, no atomics, bit-identical run to run, S * V
-//                         integer compares per mesh; a vertex no sample touches gets an exact zero.
+//                         contributes nothing and nothing is read out of bounds), dpoints and the weights -> a VertexRecords entry
+//   k_vertex_scatter      the records -> dvertices, below; also the vertex pass of the point-to-mesh backward (icn_loss.hip)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "icn_launch.h"
+#include "icn_mesh_device.h"
 
 namespace icn {
 
 namespace {
 
 constexpr int SAMPLE_BLOCK = 256;
-constexpr int SAMPLE_SCAN_BLOCK = 1024;
 
 __global__ __launch_bounds__(SAMPLE_BLOCK) void k_msample_area(const float* __restrict__ vts, const int32_t* __restrict__ faces, int V,
                                                                 int F, double* __restrict__ cdf) {
@@ -43,47 +40,19 @@ __global__ __launch_bounds__(SAMPLE_BLOCK) void k_msample_area(const float* __re
     const int i0 = faces[(size_t)f * 3], i1 = faces[(size_t)f * 3 + 1], i2 = faces[(size_t)f * 3 + 2];
     float area = 0.f;
     if (i0 >= 0 && i0 < V && i1 >= 0 && i1 < V && i2 >= 0 && i2 < V) {
-        const float* p0 = vts + ((size_t)b * V + i0) * 3;
-        const float* p1 = vts + ((size_t)b * V + i1) * 3;
-        const float* p2 = vts + ((size_t)b * V + i2) * 3;
-        const float ax = p1[0] - p0[0], ay = p1[1] - p0[1], az = p1[2] - p0[2];
-        const float bx = p2[0] - p0[0], by = p2[1] - p0[1], bz = p2[2] - p0[2];
-        // a x b with each product rounded on its own: a x a is exactly 0 (an fma would leave one product's rounding error)
-        const float nx = __fsub_rn(__fmul_rn(ay, bz), __fmul_rn(az, by));
-        const float ny = __fsub_rn(__fmul_rn(az, bx), __fmul_rn(ax, bz));
-        const float nz = __fsub_rn(__fmul_rn(ax, by), __fmul_rn(ay, bx));
-        area = 0.5f * sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(nx, nx), __fmul_rn(ny, ny)), __fmul_rn(nz, nz)));
+        const f3 p0 = load3(vts + ((size_t)b * V + i0) * 3);
+        const f3 a = load3(vts + ((size_t)b * V + i1) * 3) - p0, e = load3(vts + ((size_t)b * V + i2) * 3) - p0;
+        // Spelled out as fmas, NOT face_normal: the __fmul_rn / __fsub_rn / __fadd_rn spelling this replaces is plain operators to
+        // the compiler, which contracted it to exactly this, and the sampler's outputs must keep their bits.  A zero edge vector
+        // (v1 = v0 or v2 = v0) gives area exactly 0; v1 = v2 leaves the rounding error of one product per component.
+        const f3 nrm = {fmaf(a.y, e.z, -(a.z * e.y)), fmaf(a.z, e.x, -(a.x * e.z)), fmaf(a.x, e.y, -(a.y * e.x))};
+        area = 0.5f * sqrtf(fmaf(nrm.z, nrm.z, fmaf(nrm.x, nrm.x, nrm.y * nrm.y)));
     }
     cdf[(size_t)b * F + f] = (double)area;
 }
 
-// inclusive scan in place of c[0 .. F), one block per mesh, tiles of SAMPLE_SCAN_BLOCK (the scheme of k_p2m_grid_scan, in double)
-__global__ __launch_bounds__(SAMPLE_SCAN_BLOCK) void k_msample_scan(double* __restrict__ cdf, int F) {
-    __shared__ double wsum[SAMPLE_SCAN_BLOCK / 64];
-    double* c = cdf + (size_t)blockIdx.x * F;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    double carry = 0.0;
-    for (int base = 0; base < F; base += SAMPLE_SCAN_BLOCK) {
-        const int i = base + threadIdx.x;
-        double x = i < F ? c[i] : 0.0;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const double y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        double before = 0.0, total = 0.0;
-#pragma unroll
-        for (int k = 0; k < SAMPLE_SCAN_BLOCK / 64; ++k) {
-            const double s = wsum[k];
-            if (k < w) before += s;
-            total += s;
-        }
-        if (i < F) c[i] = (carry + before) + x;
-        carry += total;
-        __syncthreads();
-    }
+__global__ __launch_bounds__(SCAN_BLOCK) void k_msample_scan(double* __restrict__ cdf, int F) {
+    block_scan<double, true>(cdf + (size_t)blockIdx.x * F, F);
 }
 
 __device__ __forceinline__ float clamp01(float x) { return !(x > 0.f) ? 0.f : (x < 1.f ? x : 1.f); }   // NaN -> 0
@@ -134,16 +103,10 @@ __global__ __launch_bounds__(SAMPLE_BLOCK) void k_msample_point(const float* __r
     face[at] = f;
 }
 
-struct SampleRecords {              // the caller's workspace, cut into three arrays of B * S entries (16-byte aligned base)
-    int4* id;                       // vertex ids of the face (or -1), .w unused
-    float4* gw;                     // dpoints.x, .y, .z, weight of vertex 0
-    float2* w12;                    // weights of vertex 1 and 2
-};
-
 __global__ __launch_bounds__(SAMPLE_BLOCK) void k_msample_bwd_record(const int32_t* __restrict__ faces, const int32_t* __restrict__ face,
                                                                       const float* __restrict__ weights,
                                                                       const float* __restrict__ dpoints, int S, int V, int F,
-                                                                      SampleRecords rec) {
+                                                                      VertexRecords rec) {
     const int b = blockIdx.y, s = blockIdx.x * SAMPLE_BLOCK + threadIdx.x;
     if (s >= S) return;
     const size_t at = (size_t)b * S + s;
@@ -158,24 +121,27 @@ __global__ __launch_bounds__(SAMPLE_BLOCK) void k_msample_bwd_record(const int32
     rec.w12[at] = make_float2(weights[at * 3 + 1], weights[at * 3 + 2]);
 }
 
-__global__ __launch_bounds__(SAMPLE_BLOCK) void k_msample_bwd_vertex(SampleRecords rec, int S, int V, float* __restrict__ dvts) {
+// One thread per vertex: the n records of its mesh go through LDS in tiles of 256 and every thread adds those addressed to it IN
+// RECORD ORDER (then vertex 0, 1, 2 of the face) -- a fixed order, no atomics, bit-identical run to run.  n * V integer compares
+// per mesh, one broadcast ds_read_b128 per record and wave; a vertex no record addresses gets an exact zero.
+__global__ __launch_bounds__(SAMPLE_BLOCK) void k_vertex_scatter(VertexRecords rec, int n, int V, float* __restrict__ dvts) {
     __shared__ int4 s_id[SAMPLE_BLOCK];
     __shared__ float4 s_gw[SAMPLE_BLOCK];
     __shared__ float2 s_w12[SAMPLE_BLOCK];
     const int b = blockIdx.y, j = blockIdx.x * SAMPLE_BLOCK + threadIdx.x;
     const int me = j < V ? j : -2;                                         // -2 matches no record (unused ids are -1)
-    const size_t base = (size_t)b * S;
+    const size_t base = (size_t)b * n;
     float ax = 0.f, ay = 0.f, az = 0.f;
-    for (int s0 = 0; s0 < S; s0 += SAMPLE_BLOCK) {
+    for (int s0 = 0; s0 < n; s0 += SAMPLE_BLOCK) {
         __syncthreads();
         const int i = s0 + threadIdx.x;
-        if (i < S) {
+        if (i < n) {
             s_id[threadIdx.x] = rec.id[base + i];
             s_gw[threadIdx.x] = rec.gw[base + i];
             s_w12[threadIdx.x] = rec.w12[base + i];
         }
         __syncthreads();
-        const int ns = min(SAMPLE_BLOCK, S - s0);                          // the same in every thread of the block
+        const int ns = min(SAMPLE_BLOCK, n - s0);                          // the same in every thread of the block
         for (int t = 0; t < ns; ++t) {
             const int4 id = s_id[t];                                       // one address for the whole wave: a broadcast read
             if (id.x == me || id.y == me || id.z == me) {
@@ -204,7 +170,7 @@ void launch_mesh_sample_fwd(const float* vts, const int32_t* faces, const float*
     hipLaunchKernelGGL(k_msample_area, dim3((F + SAMPLE_BLOCK - 1) / SAMPLE_BLOCK, B), dim3(SAMPLE_BLOCK), 0, s, vts, faces, V, F, cdf);
     prof_mark_end(s);
     prof_mark_begin(PROF_MSAMPLE_SCAN, 0.0, s);
-    hipLaunchKernelGGL(k_msample_scan, dim3(B), dim3(SAMPLE_SCAN_BLOCK), 0, s, cdf, F);
+    hipLaunchKernelGGL(k_msample_scan, dim3(B), dim3(SCAN_BLOCK), 0, s, cdf, F);
     prof_mark_end(s);
     prof_mark_begin(PROF_MSAMPLE_POINT, 0.0, s);
     hipLaunchKernelGGL(k_msample_point, dim3((S + SAMPLE_BLOCK - 1) / SAMPLE_BLOCK, B), dim3(SAMPLE_BLOCK), 0, s, vts, faces, u, cdf, S, V,
@@ -212,22 +178,22 @@ void launch_mesh_sample_fwd(const float* vts, const int32_t* faces, const float*
     prof_mark_end(s);
 }
 
-size_t mesh_sample_bwd_record_bytes(int B, int S) { return (size_t)B * S * (sizeof(int4) + sizeof(float4) + sizeof(float2)); }
+size_t vertex_records_bytes(size_t n) { return n * VERTEX_RECORD_BYTES; }
+
+void launch_vertex_scatter(int prof_kind, void* ws, int B, int n, int V, float* dvts, hipStream_t s) {
+    prof_mark_begin(prof_kind, 0.0, s);
+    hipLaunchKernelGGL(k_vertex_scatter, dim3((V + SAMPLE_BLOCK - 1) / SAMPLE_BLOCK, B), dim3(SAMPLE_BLOCK), 0, s,
+                       vertex_records(ws, (size_t)B * n), n, V, dvts);
+    prof_mark_end(s);
+}
 
 void launch_mesh_sample_bwd(const int32_t* faces, const int32_t* face, const float* weights, const float* dpoints, int B, int S, int V,
                             int F, float* dvts, void* ws, hipStream_t s) {
-    const size_t n = (size_t)B * S;
-    SampleRecords rec;
-    rec.id = static_cast<int4*>(ws);
-    rec.gw = reinterpret_cast<float4*>(rec.id + n);
-    rec.w12 = reinterpret_cast<float2*>(rec.gw + n);
     prof_mark_begin(PROF_MSAMPLE_BWD_RECORD, 0.0, s);
     hipLaunchKernelGGL(k_msample_bwd_record, dim3((S + SAMPLE_BLOCK - 1) / SAMPLE_BLOCK, B), dim3(SAMPLE_BLOCK), 0, s, faces, face,
-                       weights, dpoints, S, V, F, rec);
+                       weights, dpoints, S, V, F, vertex_records(ws, (size_t)B * S));
     prof_mark_end(s);
-    prof_mark_begin(PROF_MSAMPLE_BWD_VERTEX, 0.0, s);
-    hipLaunchKernelGGL(k_msample_bwd_vertex, dim3((V + SAMPLE_BLOCK - 1) / SAMPLE_BLOCK, B), dim3(SAMPLE_BLOCK), 0, s, rec, S, V, dvts);
-    prof_mark_end(s);
+    launch_vertex_scatter(PROF_MSAMPLE_BWD_VERTEX, ws, B, S, V, dvts, s);
 }
 
 }  // namespace icn

@@ -123,6 +123,13 @@ def _torch_point_to_mesh(points, vertices, faces, chunk=256):
 _MAX_GRID_Y = 65535
 
 
+def _batch_slices(B):
+    """(b0, nb) slices of a batch of B meshes: the batch index of the mesh kernels is gridDim.y, at most _MAX_GRID_Y per launch.
+    A caller's workspace is sized once for the largest slice, min(B, _MAX_GRID_Y), and reused in stream order."""
+    for b0 in range(0, B, _MAX_GRID_Y):
+        yield b0, min(_MAX_GRID_Y, B - b0)
+
+
 _SEARCHES = ('brute', 'grid')
 
 
@@ -142,10 +149,9 @@ def _hip_point_to_mesh(pts, vts, f32, search='brute'):
     kind = torch.empty(B, P, dtype=torch.int32, device=pts.device)
     ws, ws_bytes = None, 0
     with torch.cuda.device(pts.device):
-        for b0 in range(0, B, _MAX_GRID_Y):                  # the batch index is gridDim.y (<= 65535 per launch)
-            nb = min(_MAX_GRID_Y, B - b0)
+        for b0, nb in _batch_slices(B):
             if search == 'grid':
-                if ws is None:                                # one workspace, sized for the largest slice, reused in stream order
+                if ws is None:
                     ws_bytes = L.icn_point_to_mesh_grid_workspace_bytes(min(B, _MAX_GRID_Y), P, V, F)
                     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pts.device)
                 rc = L.icn_point_to_mesh_grid(pts[b0:].data_ptr(), vts[b0:].data_ptr(), f32.data_ptr(), nb, P, V, F,
@@ -187,8 +193,7 @@ class _PointToMeshFn(torch.autograd.Function):
         ws_bytes = L.icn_point_to_mesh_bwd_workspace_bytes(min(B, _MAX_GRID_Y), P, V, F) if dvts is not None else 0
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pts.device) if ws_bytes else None
         with torch.cuda.device(pts.device):
-            for b0 in range(0, B, _MAX_GRID_Y):              # as the forward: the batch index is gridDim.y
-                nb = min(_MAX_GRID_Y, B - b0)
+            for b0, nb in _batch_slices(B):
                 rc = L.icn_point_to_mesh_bwd(pts[b0:].data_ptr(), vts[b0:].data_ptr(), f32.data_ptr(), face[b0:].data_ptr(),
                                              kind[b0:].data_ptr(), up[b0:].data_ptr(), nb, P, V, F,
                                              dpts[b0:].data_ptr() if dpts is not None else None,

@@ -5,8 +5,8 @@ sample_points_from_meshes draw, from uniforms the caller can supply (the kernels
 
 One definition for the HIP kernels (icn_mesh_sample_fwd / icn_mesh_sample_bwd in include/icn.h), the torch formulation and the tests.
 Per mesh, with u (S, 3) uniforms in [0, 1):
-    A_f    = 0.5 |(v1 - v0) x (v2 - v0)|, the cross product with every product rounded on its own (Mesh_Regularizer._face_normal),
-             so a face with two coincident vertices has area exactly 0
+    A_f    = 0.5 |(v1 - v0) x (v2 - v0)|: exactly 0 where v1 = v0 or v2 = v0.  Where v1 = v2 the torch formulation, which rounds every
+             product on its own (Mesh_Regularizer._face_normal), gets 0 too; k_msample_area (one fma per component) about 6e-8 |v1 - v0|^2
     c_f    = A_0 + ... + A_f in float64, T = c_{F-1}
     face_s = the smallest f with c_f > u[s,0] T (in float64): a zero-area face is never chosen while T > 0; for u[s,0] = 1, where no such
              f exists, the last face of positive area; face 0 for every sample if T is not a positive finite number
@@ -19,9 +19,7 @@ ROCm fp32 tensors run on the HIP kernels; CPU tensors, other dtypes and ICN_NO_H
 float64, searchsorted(..., right=True)), which computes areas, weights and points in the dtype of `vertices`."""
 import torch
 
-from . import _lib
-
-_MAX_GRID_Y = 65535
+from . import _lib, metrics
 
 
 def _face_areas(vertices, f):
@@ -29,7 +27,7 @@ def _face_areas(vertices, f):
     v0, v1, v2 = vertices[:, f[:, 0]], vertices[:, f[:, 1]], vertices[:, f[:, 2]]
     ax, ay, az = (v1 - v0).unbind(-1)
     bx, by, bz = (v2 - v0).unbind(-1)
-    nx, ny, nz = ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx      # every product rounded on its own: a x a = 0 exactly
+    nx, ny, nz = ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx      # every product rounded on its own: a x a = 0 exactly (the HIP kernel: not so)
     return 0.5 * (nx * nx + ny * ny + nz * nz).sqrt()
 
 
@@ -63,11 +61,10 @@ def _hip_sample(vts, f32, u):
     points = torch.empty(B, S, 3, dtype=torch.float32, device=vts.device)
     face = torch.empty(B, S, dtype=torch.int32, device=vts.device)
     weights = torch.empty(B, S, 3, dtype=torch.float32, device=vts.device)
-    ws_bytes = L.icn_mesh_sample_workspace_bytes(min(B, _MAX_GRID_Y), S, V, F)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=vts.device)     # one workspace for the largest slice, reused in stream order
+    ws_bytes = L.icn_mesh_sample_workspace_bytes(min(B, metrics._MAX_GRID_Y), S, V, F)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=vts.device)
     with torch.cuda.device(vts.device):
-        for b0 in range(0, B, _MAX_GRID_Y):                              # the batch index is gridDim.y (<= 65535 per launch)
-            nb = min(_MAX_GRID_Y, B - b0)
+        for b0, nb in metrics._batch_slices(B):
             rc = L.icn_mesh_sample_fwd(vts[b0:].data_ptr(), f32.data_ptr(), u[b0:].data_ptr(), nb, S, V, F, points[b0:].data_ptr(),
                                        face[b0:].data_ptr(), weights[b0:].data_ptr(), ws.data_ptr(), ws_bytes,
                                        torch.cuda.current_stream().cuda_stream)
@@ -80,11 +77,10 @@ def _hip_sample_bwd(f32, face, weights, dpoints, V):
     L = _lib.lib()
     (B, S), F = face.shape, f32.shape[0]
     dvts = torch.empty(B, V, 3, dtype=torch.float32, device=face.device)
-    ws_bytes = L.icn_mesh_sample_bwd_workspace_bytes(min(B, _MAX_GRID_Y), S, V, F)
+    ws_bytes = L.icn_mesh_sample_bwd_workspace_bytes(min(B, metrics._MAX_GRID_Y), S, V, F)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=face.device)
     with torch.cuda.device(face.device):
-        for b0 in range(0, B, _MAX_GRID_Y):
-            nb = min(_MAX_GRID_Y, B - b0)
+        for b0, nb in metrics._batch_slices(B):
             rc = L.icn_mesh_sample_bwd(f32.data_ptr(), face[b0:].data_ptr(), weights[b0:].data_ptr(), dpoints[b0:].data_ptr(), nb, S, V,
                                        F, dvts[b0:].data_ptr(), ws.data_ptr(), ws_bytes, torch.cuda.current_stream().cuda_stream)
             _lib.check(rc, 'icn_mesh_sample_bwd')

@@ -913,6 +913,20 @@ def test_hip_loss_gradient_matches_oracle(r, B, factors):
     assert rel_l2(x.grad.cpu().numpy(), want) < 5e-5
 
 
+@pytest.mark.parametrize('r,B', [(0, 1), (0, 3), (1, 1), (1, 3)])
+def test_hip_loss_gradient_at_the_pole_corners_matches_the_float64_torch_formulation(r, B):
+    """r = 0: every one of the 10 pixels is a pole corner; r = 1: 10 of 40.  Reference: autograd through the torch formulation in
+    float64 on the CPU, VAE factors, upstream gradient 3."""
+    from geniconet_amd.losses import P2P_Loss
+    pred, target = _loss_case(r, B, 61 + r)
+    crit = P2P_Loss(r, 0.6, 0.2, 0.2)
+    y = pred.double().requires_grad_()
+    (3.0 * crit(y, target.double())).backward()
+    x = pred.cuda().requires_grad_()
+    (3.0 * crit.cuda()(x, target.cuda())).backward()
+    assert rel_l2(x.grad.cpu().numpy(), y.grad.numpy()) < 5e-5
+
+
 def test_hip_loss_agrees_with_the_torch_formulation(monkeypatch):
     """Values and gradients of the HIP kernels against torch autograd through the torch formulation (what CPU tensors run)
     on the same device, VAE factors."""

@@ -204,6 +204,7 @@ def test_entry_points_reject_bad_arguments_before_touching_a_device():
 # ---- 6. HIP against the float64 torch formulation ---------------------------------------------------------------------------
 FACTORS = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0), (0.3, 0.2, 0.5))
 CASES = ((1, 2, 'bumpy'), (2, 3, 'bumpy'), (3, 2, 'smooth'), (5, 2, 'bumpy'))
+POLE_CASES = ((0, 1, 'bumpy'), (0, 3, 'bumpy'), (1, 1, 'bumpy'), (1, 3, 'bumpy'))     # r = 0: all 10 pixels are pole corners
 
 
 @functools.lru_cache(maxsize=None)
@@ -230,7 +231,7 @@ def _pole_corner_mask(r):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('with_length', [False, True])
-@pytest.mark.parametrize('r,B,mesh', CASES)
+@pytest.mark.parametrize('r,B,mesh', CASES + POLE_CASES)
 def test_hip_matches_float64(r, B, mesh, with_length):
     grid, L, want_terms, want_grads = _reference(r, B, mesh, with_length)
     corners = _pole_corner_mask(r)
@@ -389,7 +390,7 @@ def _check_against_float64_under_the_clamps(r, case, with_length, device):
     """Mesh_Regularizer in fp32 on `device` (cuda: k_mreg_fwd / k_mreg_bwd; cpu: the torch formulation) against the float64 torch formulation at the file's 1e-4, terms and gradient, for every FACTORS.
     Where the float64 value is 0 (a term of the all-zero grid, the normal term's gradient on a mesh whose every face is clamped)
     the bound is 0 too: the HIP value must be exactly 0.  A face with two coincident vertices has the normal 0 exactly in both
-    precisions only because the kernels round both products of a cross product (face_normal in csrc/icn_loss.hip); contracted
+    precisions only because the kernels round both products of a cross product (face_normal in csrc/icn_mesh_device.h); contracted
     to an FMA, v x v is about 6e-8 |v|^2, far above the 1e-12 clamp, and such a face would count with a random unit normal."""
     grid, L, want_terms, want_grads = _degenerate_reference(r, case, with_length)
     _clamp_margins(grid, r)

@@ -361,3 +361,22 @@ def test_the_kaolin_shim_is_the_differentiable_function():
     assert _rel(gp, want_p) <= BAR and _rel(gv, want_v) <= BAR
     _, _, _, gp1, gv1 = _gpu_grads(metrics.point_to_mesh_distance, tp, tv, tf, w)
     assert torch.equal(gp, gp1) and torch.equal(gv, gv1)
+
+
+@pytest.mark.gpu
+def test_vertex_gradient_has_the_sign_of_minus_the_point_gradient_exactly_on_dyadic_inputs():
+    """One triangle, 257 points (two tiles of records) at (-i / 8, -j / 8, k / 8), all closest to vertex 0 (kind 1, weight exactly 1),
+    upstream multiples of 1 / 4: every product and sum is exact in fp32, so dpoints = 2 ddist (p - a) and dvertices[0] =
+    -2 sum ddist (p - a) hold with equality, and the other two vertices get an exact 0."""
+    n = torch.arange(257)
+    pts = torch.stack([-(n % 8) / 8.0, -((n // 8) % 8) / 8.0, (n // 64) / 8.0], 1).float()[None]
+    vts = torch.tensor([[[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]])
+    ddist = (((n % 7) - 2) / 4.0).float()[None]
+    p, v = pts.cuda().requires_grad_(), vts.cuda().requires_grad_()
+    d, face, kind = metrics.point_to_mesh_distance(p, v, torch.tensor([[0, 1, 2]]).cuda())
+    assert bool((kind == 1).all()) and bool((face == 0).all())
+    d.backward(ddist.cuda())
+    want_p = 2 * ddist.double()[..., None] * pts.double()
+    assert torch.equal(p.grad.double().cpu(), want_p)
+    assert torch.equal(v.grad.double().cpu()[0, 0], -want_p[0].sum(0)) and bool((v.grad.cpu()[0, 1:] == 0).all())
+    assert bool((v.grad.cpu()[0, 0] != 0).all())

@@ -247,6 +247,17 @@ def test_planar_and_zero_extent_meshes():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('F', (1763, 1764))
+def test_cell_counts_of_one_and_of_two_scan_tiles(F):
+    """G = 10 at F = 1763 (1001 counts: one tile of the scan of 1024) and G = 11 at F = 1764 (1332 counts: two tiles, a carry)."""
+    assert _grid_res(F) == (10 if F == 1763 else 11)
+    v, f = _planar_mesh(30)                                              # 1800 triangles
+    tv = torch.from_numpy(v)[None]
+    tp = tv[:, :300] + 0.01 * torch.randn(1, 300, 3, generator=torch.Generator().manual_seed(F))
+    _assert_grid_equals_brute(tp, tv, torch.from_numpy(f[:F]), 'F = %d' % F)
+
+
+@pytest.mark.gpu
 def test_points_on_cell_boundaries_the_bounding_box_and_far_away():
     pts, v, f = _case(10, 100, 3)                                        # 1280 faces: G = 9
     G = _grid_res(f.shape[0])

@@ -456,3 +456,66 @@ def test_trainer_with_surface_samples():
     first, second = run(), run()
     for a, b_ in zip(first, second):
         assert bool(torch.isfinite(a)) and torch.equal(a, b_)
+
+
+# ---- the shared records -> vertices scatter and the shared scan, on dyadic inputs: every fp32 sum is exact, so equality ----------------
+@pytest.mark.gpu
+@pytest.mark.parametrize('samples', (1, 255, 256, 257, 513))
+def test_vertex_scatter_equals_a_float64_index_add_on_dyadic_inputs(samples):
+    """icn_mesh_sample_bwd alone: two meshes of 258 vertices (two blocks of vertices), faces on vertices 0, 255, 256 and 257, weights
+    and dpoints multiples of 1 / 8 in [-4, 4]; the record counts straddle the tile of 256.  One record names a face out of range."""
+    nb, V = 2, 258
+    f = torch.tensor([[0, 255, 256], [255, 256, 257], [257, 0, 1], [2, 3, 4], [256, 257, 0], [100, 200, 255]], dtype=torch.int32)
+    g = torch.Generator().manual_seed(samples)
+    face = torch.randint(0, f.shape[0], (nb, samples), generator=g, dtype=torch.int32)
+    face[1, samples // 2] = f.shape[0]                                       # out of range: contributes nothing
+    weights = torch.randint(-32, 33, (nb, samples, 3), generator=g).float() / 8
+    dp = torch.randint(-32, 33, (nb, samples, 3), generator=g).float() / 8
+    got = sampling._hip_sample_bwd(f.cuda(), face.cuda(), weights.cuda(), dp.cuda(), V).cpu()
+    want = torch.zeros(nb, V, 3, dtype=torch.float64)
+    for b in range(nb):
+        ok = face[b] < f.shape[0]
+        ids = f.long()[face[b][ok].long()]
+        for k in range(3):
+            want[b].index_add_(0, ids[:, k], weights[b][ok][:, k:k + 1].double() * dp[b][ok].double())
+    if samples >= 255:                                                       # both blocks of vertices and their edge are hit
+        assert bool((want[:, [0, 255, 256, 257]] != 0).any(-1).all())
+    assert torch.equal(got.double(), want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('faces', (1, 1023, 1024, 1025, 2049))
+def test_area_scan_selects_every_face_of_a_strip_of_congruent_triangles(faces):
+    """F right triangles of area 1 / 8 (the second mesh: twice the size), so c_f = (f + 1) / 8 exactly; u0 = (f + 0.5) / F lies in the
+    middle of face f's share and must select it, across the scan's tile of 1024 and its waves; u0 = 1 selects the last face."""
+    k = torch.arange(faces, dtype=torch.float32)
+    zero, half = torch.zeros(faces), torch.full((faces,), 0.5)
+    v = torch.stack([torch.stack([k, zero, zero], 1), torch.stack([k + half, zero, zero], 1), torch.stack([k, half, zero], 1)], 1)
+    v = torch.stack([v.reshape(-1, 3), 2 * v.reshape(-1, 3)]).cuda()         # (2, 3 F, 3)
+    f32 = torch.arange(3 * faces, dtype=torch.int32).reshape(faces, 3).cuda()
+    u = torch.zeros(2, faces, 3)
+    u[:, :, 0] = (k + 0.5) / faces
+    _, face, _ = sampling._hip_sample(v, f32, u.cuda())
+    assert torch.equal(face.cpu(), torch.arange(faces, dtype=torch.int32).expand(2, faces))
+    _, face, _ = sampling._hip_sample(v, f32, torch.tensor([1.0, 0.25, 0.25]).expand(2, 1, 3).contiguous().cuda())
+    assert face.cpu().tolist() == [[faces - 1], [faces - 1]]
+
+
+@pytest.mark.gpu
+def test_batch_slicing_of_the_launch_limit_applies_to_the_sampler(monkeypatch):
+    """The batch index is gridDim.y (<= 65535 per launch, metrics._MAX_GRID_Y); with the limit lowered to 1 the three meshes go through
+    three launches of the forward and of the backward each, and nothing may change."""
+    r, samples = 1, 64
+    v = _case(r)['v'].cuda()
+    f = _case(r)['f'].cuda()
+    u = torch.rand((B, samples, 3), generator=torch.Generator().manual_seed(3)).cuda()
+    dp = torch.randn((B, samples, 3), generator=torch.Generator().manual_seed(4)).cuda()
+
+    def run():
+        vg = v.clone().requires_grad_()
+        points, face = sampling.sample_points(vg, f, uniforms=u)
+        return points.detach(), face, torch.autograd.grad(points, vg, dp)[0]
+    whole = run()
+    monkeypatch.setattr(metrics, '_MAX_GRID_Y', 1)
+    sliced = run()
+    assert all(torch.equal(a, b_) for a, b_ in zip(whole, sliced))
