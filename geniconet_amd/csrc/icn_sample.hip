@@ -2,10 +2,9 @@
 // kaolin's sample_points / pytorch3d's sample_points_from_meshes draw, from uniforms the CALLER supplies -- the kernels draw no
 // random numbers, so every output is a pure function of the inputs.  vertices (B, V, 3), faces (F, 3) shared by the batch,
 // u (B, S, 3).  Per mesh (blockIdx.y):
-//   k_msample_area    A_f = 0.5 |(v1 - v0) x (v2 - v0)| in fp32 -> c[f] as a double.  The cross product is evaluated with one fma per
-//                     component (see the kernel), so a face with v1 = v0 or v2 = v0 has area exactly 0, while v1 = v2 leaves a
-//                     rounding error of about 6e-8 |v1 - v0|^2; the torch formulation (sampling.py) rounds every product and gets
-//                     0 there too.  A face with a vertex id outside [0, V) counts as area 0.
+//   k_msample_area    A_f = 0.5 |(v1 - v0) x (v2 - v0)| in fp32 -> c[f] as a double.  Every product of the cross product is rounded on
+//                     its own (face_normal, icn_mesh_device.h), as in the torch formulation (sampling.py), so a face with two or
+//                     three coincident vertices has area exactly 0.  A face with a vertex id outside [0, V) counts as area 0.
 //   k_msample_scan    inclusive block_scan of c in place, in double, one workgroup per mesh: c_f = A_0 + ... + A_f, T = c_{F - 1}.
 //                     Neighbouring c_f are summed in different association orders.  The areas are fp32 values, so every partial sum
 //                     is exact in double -- c is then non-decreasing and constant across a zero-area face, whatever the order --
@@ -42,10 +41,10 @@ __global__ __launch_bounds__(SAMPLE_BLOCK) void k_msample_area(const float* __re
     if (i0 >= 0 && i0 < V && i1 >= 0 && i1 < V && i2 >= 0 && i2 < V) {
         const f3 p0 = load3(vts + ((size_t)b * V + i0) * 3);
         const f3 a = load3(vts + ((size_t)b * V + i1) * 3) - p0, e = load3(vts + ((size_t)b * V + i2) * 3) - p0;
-        // Spelled out as fmas, NOT face_normal: the __fmul_rn / __fsub_rn / __fadd_rn spelling this replaces is plain operators to
-        // the compiler, which contracted it to exactly this, and the sampler's outputs must keep their bits.  A zero edge vector
-        // (v1 = v0 or v2 = v0) gives area exactly 0; v1 = v2 leaves the rounding error of one product per component.
-        const f3 nrm = {fmaf(a.y, e.z, -(a.z * e.y)), fmaf(a.z, e.x, -(a.x * e.z)), fmaf(a.x, e.y, -(a.y * e.x))};
+        // face_normal rounds every product on its own: a zero edge vector (v1 = v0 or v2 = v0) and equal edge vectors (v1 = v2)
+        // both give a normal of exactly 0, so the area is exactly 0.  Contracted to one fma per component, v1 = v2 would leave
+        // the rounding error of one product, about 6e-8 |v1 - v0|^2, and the face could be drawn.
+        const f3 nrm = face_normal(a, e);
         area = 0.5f * sqrtf(fmaf(nrm.z, nrm.z, fmaf(nrm.x, nrm.x, nrm.y * nrm.y)));
     }
     cdf[(size_t)b * F + f] = (double)area;

@@ -5,8 +5,8 @@ sample_points_from_meshes draw, from uniforms the caller can supply (the kernels
 
 One definition for the HIP kernels (icn_mesh_sample_fwd / icn_mesh_sample_bwd in include/icn.h), the torch formulation and the tests.
 Per mesh, with u (S, 3) uniforms in [0, 1):
-    A_f    = 0.5 |(v1 - v0) x (v2 - v0)|: exactly 0 where v1 = v0 or v2 = v0.  Where v1 = v2 the torch formulation, which rounds every
-             product on its own (Mesh_Regularizer._face_normal), gets 0 too; k_msample_area (one fma per component) about 6e-8 |v1 - v0|^2
+    A_f    = 0.5 |(v1 - v0) x (v2 - v0)| with every product of the cross product rounded on its own (Mesh_Regularizer._face_normal;
+             face_normal in k_msample_area), so a face with two or three coincident vertices has area exactly 0
     c_f    = A_0 + ... + A_f in float64, T = c_{F-1}
     face_s = the smallest f with c_f > u[s,0] T (in float64): a zero-area face is never chosen while T > 0; for u[s,0] = 1, where no such
              f exists, the last face of positive area; face 0 for every sample if T is not a positive finite number
@@ -27,7 +27,7 @@ def _face_areas(vertices, f):
     v0, v1, v2 = vertices[:, f[:, 0]], vertices[:, f[:, 1]], vertices[:, f[:, 2]]
     ax, ay, az = (v1 - v0).unbind(-1)
     bx, by, bz = (v2 - v0).unbind(-1)
-    nx, ny, nz = ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx      # every product rounded on its own: a x a = 0 exactly (the HIP kernel: not so)
+    nx, ny, nz = ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx      # every product rounded on its own: a x a = 0 exactly (as the HIP kernel's face_normal)
     return 0.5 * (nx * nx + ny * ny + nz * nz).sqrt()
 
 

@@ -275,10 +275,12 @@ int icn_point_to_mesh_grid(const float* points, const float* vertices, const int
  * Components of u outside [0, 1] are clamped and NaN counts as 0.  A face with a vertex id outside [0, V) counts as area 0 and, if
  * it is taken all the same (face 0 of a mesh without area), gives a zero point and zero weights; nothing is read out of bounds.
  * points (B, S, 3), face (B, S) int32, weights (B, S, 3).  ws: icn_mesh_sample_workspace_bytes(B, S, V, F) bytes (host-only query;
- * 0 for sizes the call would reject; 8 B F bytes rounded up to 16), 16-byte aligned, owned by the caller; contents need not survive
- * the call.  Three launches on `stream`, no allocation, no synchronisation, no atomics: bit-identical run to run.  B <= 65535 per
- * call (the batch index is gridDim.y).  0 on success, negative with icn_last_error() otherwise (arguments are checked before any
- * device call). */
+ * 0 for sizes the call would reject; 8 B F bytes rounded up to 16), 16-byte aligned, owned by the caller; nothing is expected in
+ * it on entry and the library does not read it again after the call.  Once the work on `stream` is done its first 8 B F bytes
+ * hold c as (B, F) doubles, c[b * F + f] = c_f of mesh b: the CDF the face choice was searched in (the tests read it).
+ * Three launches on `stream`, no allocation, no synchronisation, no atomics: bit-identical run to run.  B <= 65535 per call (the
+ * batch index is gridDim.y).  0 on success, negative with icn_last_error() otherwise (arguments are checked before any device
+ * call). */
 size_t icn_mesh_sample_workspace_bytes(int B, int S, int V, int F);
 int icn_mesh_sample_fwd(const float* vertices, const int32_t* faces, const float* u, int B, int S, int V, int F, float* points,
                         int32_t* face, float* weights, void* ws, size_t ws_bytes, void* stream);
