@@ -5,8 +5,10 @@ the build command; if a call fails, the library's own message is raised as Runti
 """
 import ctypes
 import os
+import types
 
 import numpy as np
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ICN_LIB_PATH: developer override (tools/asan_host.sh runs the host-side tests against a sanitizer build of the library)
@@ -22,80 +24,84 @@ _i32p = ctypes.POINTER(ctypes.c_int32)
 _f32p = ctypes.POINTER(ctypes.c_float)
 _intp = ctypes.POINTER(ctypes.c_int)
 
-# name -> (restype, argtypes); mirrors include/icn.h one to one (checked by tests/test_abi.py)
+# How an entry reports failure: RC an int, 0 is success; COUNT an int / long, negative is failure and anything else the value;
+# PLAIN cannot fail (sizes, ..._supported, versions and flags).
+RC, COUNT, PLAIN = 'rc', 'count', 'plain'
+
+# name -> (restype, argtypes, reply convention); mirrors include/icn.h one to one (checked by tests/test_abi.py)
 SIGNATURES = {
-    'icn_abi_version': (ctypes.c_int, []),
-    'icn_last_error': (ctypes.c_char_p, []),
-    'icn_prepare_conv': (ctypes.c_int, [ctypes.c_int] * 3),
-    'icn_prepare_upsample': (ctypes.c_int, [ctypes.c_int] * 2),
-    'icn_conv_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 6),
-    'icn_conv_fwd': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    'icn_conv_bwd_data': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    'icn_conv_bwd_weight': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    'icn_conv_pair_supported': (ctypes.c_int, [ctypes.c_int] * 6),
-    'icn_conv_pair_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 7),
-    'icn_conv_pair_fwd': (ctypes.c_int, [_c_float_p] * 7 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    'icn_conv_pair_bwd_data': (ctypes.c_int, [_c_float_p] * 5 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    'icn_conv_pair_bwd_weight': (ctypes.c_int, [_c_float_p] * 7 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    'icn_upconv_supported': (ctypes.c_int, [ctypes.c_int] * 5),
-    'icn_upconv_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 5),
-    'icn_upconv_fwd': (ctypes.c_int, [_c_float_p] * 7 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    'icn_upconv_bwd_supported': (ctypes.c_int, [ctypes.c_int] * 6),
-    'icn_upconv_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 5),
-    'icn_upconv_bwd': (ctypes.c_int, [_c_float_p] * 10 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    'icn_upconv_bwd_streams': (ctypes.c_int, [_c_float_p] * 10 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
-    'icn_upsample_fwd': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
-    'icn_upsample_bwd': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
-    'icn_bn_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 2),
-    'icn_bn_stats2': (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int] + ([ctypes.c_float] * 2 + [_c_float_p] * 3) * 2 + [_c_float_p, ctypes.c_void_p]),
-    'icn_bn_stats': (ctypes.c_int, [_c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float] + [_c_float_p] * 4 + [ctypes.c_void_p]),
-    'icn_bn_relu_fwd': (ctypes.c_int, [_c_float_p] * 9 + [ctypes.c_int] * 2 + [ctypes.c_void_p]),
-    'icn_bn_relu_bwd': (ctypes.c_int, [_c_float_p] * 13 + [ctypes.c_int] * 2 + [_c_float_p] * 4 + [ctypes.c_void_p]),
-    'icn_head_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 2),
-    'icn_head_fwd': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
-    'icn_head_bwd': (ctypes.c_int, [_c_float_p] * 8 + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
-    'icn_p2p_loss_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 2),
-    'icn_p2p_loss_fwd': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_float] * 3 + [ctypes.c_int] + [_c_float_p] * 2 + [ctypes.c_void_p]),
-    'icn_p2p_loss_bwd_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 2),
-    'icn_p2p_loss_bwd': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_float] * 3 + [ctypes.c_int] + [_c_float_p] * 2 + [ctypes.c_void_p]),
-    'icn_mesh_reg_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 2),
-    'icn_mesh_reg_fwd': (ctypes.c_int, [_c_float_p] + [ctypes.c_int] * 2 + [ctypes.c_float] * 4 + [_c_float_p] * 2 + [ctypes.c_void_p]),
-    'icn_mesh_reg_bwd_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 2),
-    'icn_mesh_reg_bwd': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_float] * 4 + [_c_float_p] * 2 + [ctypes.c_void_p]),
-    'icn_kld_workspace_floats': (ctypes.c_size_t, [ctypes.c_size_t]),
-    'icn_kld_fwd': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_size_t] + [_c_float_p] * 2 + [ctypes.c_void_p]),
-    'icn_kld_bwd': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_size_t] + [_c_float_p] * 2 + [ctypes.c_void_p]),
-    'icn_reparam_fwd': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_size_t] + [_c_float_p] + [ctypes.c_void_p]),
-    'icn_reparam_bwd': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_size_t] + [_c_float_p] * 2 + [ctypes.c_void_p]),
-    'icn_adam_step': (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_double] * 4 + [ctypes.c_void_p]),
-    'icn_adam_step_dev': (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_double] * 4 + [ctypes.c_void_p]),
-    'icn_table_stream_k': (ctypes.c_long, [ctypes.c_int] * 4 + [_i32p, ctypes.c_size_t]),
-    'icn_table_tile_lists': (ctypes.c_long, [ctypes.c_int] * 7 + [_i32p, ctypes.c_size_t]),
-    'icn_set_debug_flags': (ctypes.c_int, [ctypes.c_int]),
-    'icn_device_status': (ctypes.c_int, [ctypes.c_int]),
-    'icn_get_arith': (ctypes.c_int, []),
-    'icn_set_arith': (ctypes.c_int, [ctypes.c_int]),
-    'icn_build_flags': (ctypes.c_uint, []),
-    'icn_host_selfcheck': (ctypes.c_long, [ctypes.c_int] * 2),
-    'icn_debug_trace': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),
-    'icn_point_to_mesh': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 4 + [_c_float_p] * 3 + [ctypes.c_void_p]),
-    'icn_point_to_mesh_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
-    'icn_point_to_mesh_grid_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
-    'icn_point_to_mesh_grid': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 4 + [_c_float_p] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    'icn_point_to_mesh_bwd': (ctypes.c_int, [_c_float_p] * 6 + [ctypes.c_int] * 4 + [_c_float_p] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    'icn_mesh_sample_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
-    'icn_mesh_sample_fwd': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 4 + [_c_float_p] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    'icn_mesh_sample_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
-    'icn_mesh_sample_bwd': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 4 + [_c_float_p] + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
-    'icn_table_conv_fwd': (ctypes.c_long, [ctypes.c_int] * 3 + [_i32p, ctypes.c_size_t]),
-    'icn_table_wgrad7': (ctypes.c_long, [ctypes.c_int] * 3 + [_i32p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint16), ctypes.c_size_t, _intp]),
-    'icn_table_conv_bwd': (ctypes.c_long, [ctypes.c_int] * 3 + [_i32p, ctypes.c_size_t, _intp]),
-    'icn_table_upsample': (ctypes.c_long, [ctypes.c_int] * 3 + [_i32p, _f32p, ctypes.c_size_t, _intp]),
-    'icn_table_upsample_pairs': (ctypes.c_long, [ctypes.c_int, _i32p, ctypes.c_size_t]),
-    'icn_table_faces': (ctypes.c_long, [ctypes.c_int, _i32p, ctypes.c_size_t]),
-    'icn_table_vertex_stencils': (ctypes.c_long, [ctypes.c_int, _i32p, ctypes.c_size_t]),
-    'icn_table_upconv_bwd': (ctypes.c_long, [ctypes.c_int] * 2 + [_i32p, _f32p, ctypes.c_size_t, _intp]),
-    'icn_table_upconv': (ctypes.c_long, [ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_size_t, _f32p, ctypes.c_size_t, _intp]),
+    'icn_abi_version': (ctypes.c_int, [], PLAIN),
+    'icn_last_error': (ctypes.c_char_p, [], PLAIN),
+    'icn_prepare_conv': (ctypes.c_int, [ctypes.c_int] * 3, RC),
+    'icn_prepare_upsample': (ctypes.c_int, [ctypes.c_int] * 2, RC),
+    'icn_conv_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 6, PLAIN),
+    'icn_conv_fwd': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+    'icn_conv_bwd_data': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+    'icn_conv_bwd_weight': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+    'icn_conv_pair_supported': (ctypes.c_int, [ctypes.c_int] * 6, PLAIN),
+    'icn_conv_pair_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 7, PLAIN),
+    'icn_conv_pair_fwd': (ctypes.c_int, [_c_float_p] * 7 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+    'icn_conv_pair_bwd_data': (ctypes.c_int, [_c_float_p] * 5 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+    'icn_conv_pair_bwd_weight': (ctypes.c_int, [_c_float_p] * 7 + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+    'icn_upconv_supported': (ctypes.c_int, [ctypes.c_int] * 5, PLAIN),
+    'icn_upconv_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 5, PLAIN),
+    'icn_upconv_fwd': (ctypes.c_int, [_c_float_p] * 7 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+    'icn_upconv_bwd_supported': (ctypes.c_int, [ctypes.c_int] * 6, PLAIN),
+    'icn_upconv_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 5, PLAIN),
+    'icn_upconv_bwd': (ctypes.c_int, [_c_float_p] * 10 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+    'icn_upconv_bwd_streams': (ctypes.c_int, [_c_float_p] * 10 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p], RC),
+    'icn_upsample_fwd': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 4 + [ctypes.c_void_p], RC),
+    'icn_upsample_bwd': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 4 + [ctypes.c_void_p], RC),
+    'icn_bn_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 2, PLAIN),
+    'icn_bn_stats2': (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int] + ([ctypes.c_float] * 2 + [_c_float_p] * 3) * 2 + [_c_float_p, ctypes.c_void_p], RC),
+    'icn_bn_stats': (ctypes.c_int, [_c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float] + [_c_float_p] * 4 + [ctypes.c_void_p], RC),
+    'icn_bn_relu_fwd': (ctypes.c_int, [_c_float_p] * 9 + [ctypes.c_int] * 2 + [ctypes.c_void_p], RC),
+    'icn_bn_relu_bwd': (ctypes.c_int, [_c_float_p] * 13 + [ctypes.c_int] * 2 + [_c_float_p] * 4 + [ctypes.c_void_p], RC),
+    'icn_head_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 2, PLAIN),
+    'icn_head_fwd': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_void_p], RC),
+    'icn_head_bwd': (ctypes.c_int, [_c_float_p] * 8 + [ctypes.c_int] * 3 + [ctypes.c_void_p], RC),
+    'icn_p2p_loss_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 2, PLAIN),
+    'icn_p2p_loss_fwd': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_float] * 3 + [ctypes.c_int] + [_c_float_p] * 2 + [ctypes.c_void_p], RC),
+    'icn_p2p_loss_bwd_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 2, PLAIN),
+    'icn_p2p_loss_bwd': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_float] * 3 + [ctypes.c_int] + [_c_float_p] * 2 + [ctypes.c_void_p], RC),
+    'icn_mesh_reg_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 2, PLAIN),
+    'icn_mesh_reg_fwd': (ctypes.c_int, [_c_float_p] + [ctypes.c_int] * 2 + [ctypes.c_float] * 4 + [_c_float_p] * 2 + [ctypes.c_void_p], RC),
+    'icn_mesh_reg_bwd_workspace_floats': (ctypes.c_size_t, [ctypes.c_int] * 2, PLAIN),
+    'icn_mesh_reg_bwd': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_float] * 4 + [_c_float_p] * 2 + [ctypes.c_void_p], RC),
+    'icn_kld_workspace_floats': (ctypes.c_size_t, [ctypes.c_size_t], PLAIN),
+    'icn_kld_fwd': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_size_t] + [_c_float_p] * 2 + [ctypes.c_void_p], RC),
+    'icn_kld_bwd': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_size_t] + [_c_float_p] * 2 + [ctypes.c_void_p], RC),
+    'icn_reparam_fwd': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_size_t] + [_c_float_p] + [ctypes.c_void_p], RC),
+    'icn_reparam_bwd': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_size_t] + [_c_float_p] * 2 + [ctypes.c_void_p], RC),
+    'icn_adam_step': (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 7 + [ctypes.c_double] * 4 + [ctypes.c_void_p], RC),
+    'icn_adam_step_dev': (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 6 + [ctypes.c_double] * 4 + [ctypes.c_void_p], RC),
+    'icn_table_stream_k': (ctypes.c_long, [ctypes.c_int] * 4 + [_i32p, ctypes.c_size_t], COUNT),
+    'icn_table_tile_lists': (ctypes.c_long, [ctypes.c_int] * 7 + [_i32p, ctypes.c_size_t], COUNT),
+    'icn_set_debug_flags': (ctypes.c_int, [ctypes.c_int], PLAIN),
+    'icn_device_status': (ctypes.c_int, [ctypes.c_int], COUNT),
+    'icn_get_arith': (ctypes.c_int, [], COUNT),
+    'icn_set_arith': (ctypes.c_int, [ctypes.c_int], COUNT),
+    'icn_build_flags': (ctypes.c_uint, [], PLAIN),
+    'icn_host_selfcheck': (ctypes.c_long, [ctypes.c_int] * 2, COUNT),
+    'icn_debug_trace': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t], RC),
+    'icn_point_to_mesh': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 4 + [_c_float_p] * 3 + [ctypes.c_void_p], RC),
+    'icn_point_to_mesh_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4, PLAIN),
+    'icn_point_to_mesh_grid_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4, PLAIN),
+    'icn_point_to_mesh_grid': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 4 + [_c_float_p] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+    'icn_point_to_mesh_bwd': (ctypes.c_int, [_c_float_p] * 6 + [ctypes.c_int] * 4 + [_c_float_p] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+    'icn_mesh_sample_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4, PLAIN),
+    'icn_mesh_sample_fwd': (ctypes.c_int, [_c_float_p] * 3 + [ctypes.c_int] * 4 + [_c_float_p] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+    'icn_mesh_sample_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4, PLAIN),
+    'icn_mesh_sample_bwd': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 4 + [_c_float_p] + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+    'icn_table_conv_fwd': (ctypes.c_long, [ctypes.c_int] * 3 + [_i32p, ctypes.c_size_t], COUNT),
+    'icn_table_wgrad7': (ctypes.c_long, [ctypes.c_int] * 3 + [_i32p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint16), ctypes.c_size_t, _intp], COUNT),
+    'icn_table_conv_bwd': (ctypes.c_long, [ctypes.c_int] * 3 + [_i32p, ctypes.c_size_t, _intp], COUNT),
+    'icn_table_upsample': (ctypes.c_long, [ctypes.c_int] * 3 + [_i32p, _f32p, ctypes.c_size_t, _intp], COUNT),
+    'icn_table_upsample_pairs': (ctypes.c_long, [ctypes.c_int, _i32p, ctypes.c_size_t], COUNT),
+    'icn_table_faces': (ctypes.c_long, [ctypes.c_int, _i32p, ctypes.c_size_t], COUNT),
+    'icn_table_vertex_stencils': (ctypes.c_long, [ctypes.c_int, _i32p, ctypes.c_size_t], COUNT),
+    'icn_table_upconv_bwd': (ctypes.c_long, [ctypes.c_int] * 2 + [_i32p, _f32p, ctypes.c_size_t, _intp], COUNT),
+    'icn_table_upconv': (ctypes.c_long, [ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_size_t, _f32p, ctypes.c_size_t, _intp], COUNT),
 }
 
 
@@ -105,16 +111,26 @@ class ProfileEntry(ctypes.Structure):
                 ('total_flops', ctypes.c_double)]
 
 
-SIGNATURES['icn_profile_start'] = (ctypes.c_int, [ctypes.c_int])
-SIGNATURES['icn_profile_stop'] = (ctypes.c_int, [ctypes.POINTER(ProfileEntry), ctypes.c_int])
-SIGNATURES['icn_profile_select'] = (ctypes.c_int, [ctypes.c_char_p])
+SIGNATURES['icn_profile_start'] = (ctypes.c_int, [ctypes.c_int], RC)
+SIGNATURES['icn_profile_stop'] = (ctypes.c_int, [ctypes.POINTER(ProfileEntry), ctypes.c_int], COUNT)
+SIGNATURES['icn_profile_select'] = (ctypes.c_int, [ctypes.c_char_p], RC)
 
-_lib = None
+_lib = _api = None
+
+
+def _raises(name, reply, last_error):
+    """ctypes errcheck of entry `name`: the library's own message as RuntimeError, the text check() gives."""
+    def errcheck(result, func, args):
+        if result < 0 or (result and reply == RC):
+            raise RuntimeError('%s failed: %s' % (name, last_error().decode()))
+        return result
+    return errcheck
 
 
 def lib():
-    """Load libicn.so once; raise with the build recipe if it is not there."""
-    global _lib
+    """Load libicn.so once; raise with the build recipe if it is not there.  The raw handle: return codes are the caller's to
+    look at (check()); the package's own calls go through api()."""
+    global _lib, _api
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(
@@ -122,15 +138,36 @@ def lib():
                 'Build it with `python -c "import __graft_entry__ as g; g.build()"` '
                 '(or `make -C geniconet_amd/csrc`).' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        checked = types.SimpleNamespace()
+        for name, (res, args, reply) in SIGNATURES.items():
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
+            fn = handle[name]            # a function object of its own (handle.name is cached, handle[name] is not)
+            fn.restype, fn.argtypes = res, args
+            if reply != PLAIN:
+                fn.errcheck = _raises(name, reply, handle.icn_last_error)
+            setattr(checked, name, fn)
         if handle.icn_abi_version() != ABI_VERSION:
             raise RuntimeError('geniconet_amd: libicn.so ABI %d != binding ABI %d; rebuild'
                                % (handle.icn_abi_version(), ABI_VERSION))
         refuse_pricing_build(handle.icn_build_flags(), LIB_PATH)
-        _lib = handle
+        _lib, _api = handle, checked
     return _lib
+
+
+def api():
+    """The checked view of the library: the same entries by name, a failing call raises RuntimeError('<entry> failed: <message>')."""
+    return _api or (lib() and _api)
+
+
+def stream():
+    """The current HIP stream of the current device, as the C ABI takes it."""
+    return torch.cuda.current_stream().cuda_stream
+
+
+def workspace(n, device, dtype=torch.uint8):
+    """Uninitialised scratch of n elements for one call, at least one (a zero-size query still gets a valid pointer)."""
+    return torch.empty(max(int(n), 1), dtype=dtype, device=device)
 
 
 def refuse_pricing_build(flags, path, allow=None):
@@ -146,7 +183,7 @@ def refuse_pricing_build(flags, path, allow=None):
 
 def build_info():
     """What was loaded: path, whether ICN_LIB_PATH overrode the in-tree library, the build switches (icn_build_flags)."""
-    f = lib().icn_build_flags()
+    f = api().icn_build_flags()
     return dict(path=LIB_PATH, overridden=bool(os.environ.get('ICN_LIB_PATH')), exp=f & 0xffff, conv_waves_default=(f >> 16) & 0xff,
                 chain_prio=(f >> 24) & 0xf)
 
@@ -155,19 +192,13 @@ ARITH_MODES = {'f32': 0, 'bf16x3': 1}
 
 
 def get_arith():
-    v = lib().icn_get_arith()
-    if v < 0:
-        check(-1, 'icn_get_arith')
-    return {0: 'f32', 1: 'bf16x3'}[v]
+    return {0: 'f32', 1: 'bf16x3'}[api().icn_get_arith()]
 
 
 def set_arith(mode):
     """Arithmetic of the channel-mixing contraction ('f32' exact MFMA, 'bf16x3' three-way bf16 split; include/icn.h); returns
     the previous mode."""
-    v = lib().icn_set_arith(ARITH_MODES[mode])
-    if v < 0:
-        check(-1, 'icn_set_arith')
-    return {0: 'f32', 1: 'bf16x3'}[v]
+    return {0: 'f32', 1: 'bf16x3'}[api().icn_set_arith(ARITH_MODES[mode])]
 
 
 def source_sha256():
@@ -194,14 +225,10 @@ STATUS_BITS = {1: "a stream-K workgroup of k_conv_dma_sk never received a partne
 
 def device_status(device=None, clear=True, synchronize=True):
     """Bits of the device's asynchronous failure word (icn_device_status): 0 = no kernel reported a failure."""
-    import torch
     with torch.cuda.device(device):
         if synchronize:
             torch.cuda.synchronize()
-        v = lib().icn_device_status(1 if clear else 0)
-    if v < 0:
-        check(-1, 'icn_device_status')
-    return v
+        return api().icn_device_status(1 if clear else 0)
 
 
 def raise_on_device_status(device=None, synchronize=True):
@@ -222,96 +249,78 @@ def corner_code(corner_mode):
 
 
 # ---- host-side table introspection (no device needed) ------------------------------------------------------
+def _table(name, ints, outs, sizes=None):
+    """The two-call idiom of the icn_table_* entries: ask for the element count with null buffers, allocate, fill.  `outs` lists
+    the C arguments after the ints: a numpy dtype is a buffer, 'cap' the capacity of the buffer before it, anything else (width /
+    meta out-parameters) is passed as it is.  Every buffer takes the returned count unless sizes(count) -- evaluated after the
+    first call, when meta is known -- says otherwise.  -> the filled buffers."""
+    fn = getattr(api(), name)
+
+    def call(bufs):
+        args, k = list(ints), -1
+        for o in outs:
+            if o == 'cap':
+                args.append(bufs[k].size if bufs else 0)
+            elif isinstance(o, type):
+                k += 1
+                args.append(bufs[k].ctypes.data_as(fn.argtypes[len(args)]) if bufs else None)
+            else:
+                args.append(o)
+        return fn(*args)
+    n = call(None)
+    dtypes = [o for o in outs if isinstance(o, type)]
+    bufs = [np.empty(m, dtype=d) for d, m in zip(dtypes, sizes(n) if sizes else [n] * len(dtypes))]
+    call(bufs)
+    return bufs
+
+
 def table_conv_fwd(r_in, stride, corner_mode):
-    L, m = lib(), corner_code(corner_mode)
-    n = L.icn_table_conv_fwd(r_in, stride, m, None, 0)
-    if n < 0:
-        check(-1, 'icn_table_conv_fwd')
-    out = np.empty(n, dtype=np.int32)
-    L.icn_table_conv_fwd(r_in, stride, m, out.ctypes.data_as(_i32p), n)
+    out, = _table('icn_table_conv_fwd', (r_in, stride, corner_code(corner_mode)), (np.int32, 'cap'))
     return out.reshape(7, -1)
 
 
 def table_wgrad7(r_in, stride, corner_mode):
     """Patch form of the forward table for the all-taps weight-gradient kernel: (rows [npatch][U], pos [npatch][16][8]) or
     None when the table does not exist for this level / stride."""
-    L, m = lib(), corner_code(corner_mode)
-    meta = (ctypes.c_int * 2)()
-    n = L.icn_table_wgrad7(r_in, stride, m, None, 0, None, 0, meta)
-    if n < 0:
-        check(-1, 'icn_table_wgrad7')
-    if n == 0:
-        return None
-    U, npatch = meta[0], meta[1]
-    rows, pos = np.empty(n, dtype=np.int32), np.empty(npatch * 16 * 8, dtype=np.uint16)
-    L.icn_table_wgrad7(r_in, stride, m, rows.ctypes.data_as(_i32p), n, pos.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), pos.size, meta)
-    return rows.reshape(npatch, U), pos.reshape(npatch, 16, 8)
+    meta = (ctypes.c_int * 2)()                                    # U, npatch
+    rows, pos = _table('icn_table_wgrad7', (r_in, stride, corner_code(corner_mode)), (np.int32, 'cap', np.uint16, 'cap', meta),
+                       lambda n: (n, meta[1] * 16 * 8))
+    return (rows.reshape(meta[1], meta[0]), pos.reshape(meta[1], 16, 8)) if rows.size else None
 
 
 def table_conv_bwd(r_in, stride, corner_mode):
-    L, m = lib(), corner_code(corner_mode)
     w = ctypes.c_int(0)
-    n = L.icn_table_conv_bwd(r_in, stride, m, None, 0, ctypes.byref(w))
-    if n < 0:
-        check(-1, 'icn_table_conv_bwd')
-    out = np.empty(n, dtype=np.int32)
-    L.icn_table_conv_bwd(r_in, stride, m, out.ctypes.data_as(_i32p), n, ctypes.byref(w))
+    out, = _table('icn_table_conv_bwd', (r_in, stride, corner_code(corner_mode)), (np.int32, 'cap', ctypes.byref(w)))
     return out.reshape(7, w.value, -1)
 
 
 def table_upsample(r_in, corner_mode, transpose=False):
-    L, m = lib(), corner_code(corner_mode)
     w = ctypes.c_int(0)
-    n = L.icn_table_upsample(r_in, m, int(transpose), None, None, 0, ctypes.byref(w))
-    if n < 0:
-        check(-1, 'icn_table_upsample')
-    idx, coef = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
-    L.icn_table_upsample(r_in, m, int(transpose), idx.ctypes.data_as(_i32p), coef.ctypes.data_as(_f32p), n, ctypes.byref(w))
+    idx, coef = _table('icn_table_upsample', (r_in, corner_code(corner_mode), int(transpose)),
+                       (np.int32, np.float32, 'cap', ctypes.byref(w)))
     return idx.reshape(-1, w.value), coef.reshape(-1, w.value)
 
 
 def table_faces(r):
-    L = lib()
-    n = L.icn_table_faces(r, None, 0)
-    if n < 0:
-        check(-1, 'icn_table_faces')
-    out = np.empty(n, dtype=np.int32)
-    L.icn_table_faces(r, out.ctypes.data_as(_i32p), n)
-    return out.reshape(-1, 3)
+    return _table('icn_table_faces', (r,), (np.int32, 'cap'))[0].reshape(-1, 3)
 
 
 def table_vertex_stencils(r):
     """Edge stencils of the mesh regularisers (icn_table_vertex_stencils): int32 (V, 6, 3) of (p, q, x), -1 padded."""
-    L = lib()
-    n = L.icn_table_vertex_stencils(r, None, 0)
-    if n < 0:
-        check(-1, 'icn_table_vertex_stencils')
-    out = np.empty(n, dtype=np.int32)
-    L.icn_table_vertex_stencils(r, out.ctypes.data_as(_i32p), n)
-    return out.reshape(-1, 6, 3)
+    return _table('icn_table_vertex_stencils', (r,), (np.int32, 'cap'))[0].reshape(-1, 6, 3)
 
 
 def table_upsample_pairs(r_in):
-    L = lib()
-    n = L.icn_table_upsample_pairs(r_in, None, 0)
-    if n < 0:
-        check(-1, 'icn_table_upsample_pairs')
-    out = np.empty(n, dtype=np.int32)
-    L.icn_table_upsample_pairs(r_in, out.ctypes.data_as(_i32p), n)
-    return out.reshape(2, -1)
+    return _table('icn_table_upsample_pairs', (r_in,), (np.int32, 'cap'))[0].reshape(2, -1)
 
 
 def table_upconv(r_in, corner_mode):
     """Composite upsample + conv table (icn_table_upconv) as a dict of numpy arrays: seg (nseg, 3) = rows per sample / first
     list position / virtual-tap mask, pix (Pf,), code (NV, Pf), alpha (NV, 7), slot_idx / slot_coef (n_slots, E)."""
-    L, m = lib(), corner_code(corner_mode)
     meta = (ctypes.c_int * 7)()
-    n = L.icn_table_upconv(r_in, m, None, 0, None, 0, meta)
-    if n < 0:
-        check(-1, 'icn_table_upconv')
-    Pf, Pc, n_slots, E, nseg, NV, nf = list(meta)
-    ints, floats = np.empty(n, dtype=np.int32), np.empty(nf, dtype=np.float32)
-    L.icn_table_upconv(r_in, m, ints.ctypes.data_as(_i32p), n, floats.ctypes.data_as(_f32p), nf, meta)
+    ints, floats = _table('icn_table_upconv', (r_in, corner_code(corner_mode)), (np.int32, 'cap', np.float32, 'cap', meta),
+                          lambda n: (n, meta[6]))
+    Pf, Pc, n_slots, E, nseg, NV, _ = list(meta)
     o = 0
     seg = ints[o:o + 3 * nseg].reshape(nseg, 3); o += 3 * nseg
     pix = ints[o:o + Pf]; o += Pf
@@ -323,51 +332,33 @@ def table_upconv(r_in, corner_mode):
 
 def table_upconv_bwd(r_in, corner_mode):
     """ELL matrix dy -> g of the aggregated upsample + conv backward: (idx, coef), each (7 * Pc, width), row s * 7 + t."""
-    L, m = lib(), corner_code(corner_mode)
     w = ctypes.c_int(0)
-    n = L.icn_table_upconv_bwd(r_in, m, None, None, 0, ctypes.byref(w))
-    if n < 0:
-        check(-1, 'icn_table_upconv_bwd')
-    idx, coef = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
-    L.icn_table_upconv_bwd(r_in, m, idx.ctypes.data_as(_i32p), coef.ctypes.data_as(_f32p), n, ctypes.byref(w))
+    idx, coef = _table('icn_table_upconv_bwd', (r_in, corner_code(corner_mode)), (np.int32, np.float32, 'cap', ctypes.byref(w)))
     return idx.reshape(-1, w.value), coef.reshape(-1, w.value)
 
 
 def table_stream_k(ntiles, grid, nk, ku=1):
     """Stream-K schedule (icn_table_stream_k) of ntiles tiles of nk K-steps, pieces >= ku steps: int32 array (n, 4) of rows
     (workgroup, tile, k0, k1) in walk order."""
-    L = lib()
-    n = L.icn_table_stream_k(ntiles, grid, nk, ku, None, 0)
-    if n < 0:
-        check(-1, 'icn_table_stream_k')
-    out = np.empty(n, dtype=np.int32)
-    L.icn_table_stream_k(ntiles, grid, nk, ku, out.ctypes.data_as(_i32p), n)
-    return out.reshape(-1, 4)
+    return _table('icn_table_stream_k', (ntiles, grid, nk, ku), (np.int32, 'cap'))[0].reshape(-1, 4)
 
 
 def table_tile_lists(r_in, B, bm, ntn, grid, corner_mode='average'):
     """Tile lists of a stride-2 data-gradient launch (icn_table_tile_lists): (offsets [grid + 1], ids)."""
-    L, m = lib(), corner_code(corner_mode)
-    n = L.icn_table_tile_lists(r_in, 2, m, B, bm, ntn, grid, None, 0)
-    if n < 0:
-        check(-1, 'icn_table_tile_lists')
-    out = np.empty(n, dtype=np.int32)
-    L.icn_table_tile_lists(r_in, 2, m, B, bm, ntn, grid, out.ctypes.data_as(_i32p), n)
+    out, = _table('icn_table_tile_lists', (r_in, 2, corner_code(corner_mode), B, bm, ntn, grid), (np.int32, 'cap'))
     return out[:grid + 1], out[grid + 1:]
 
 
 def profile_start(max_launches=4096, only=None):
     """Start timing MFMA launches (and the point-to-mesh kernels) with HIP events; only='k_conv_dma<64, 64, false>' restricts it to one kernel (an event pair
     around every launch of a step costs about 2.5 % of it)."""
-    check(lib().icn_profile_select(only.encode() if only else None), 'icn_profile_select')
-    check(lib().icn_profile_start(max_launches), 'icn_profile_start')
+    api().icn_profile_select(only.encode() if only else None)
+    api().icn_profile_start(max_launches)
 
 
 def profile_stop():
     """-> list of dicts(kernel, launches, total_ms, total_flops) for the MFMA kernels launched since profile_start."""
     buf = (ProfileEntry * 48)()
-    n = lib().icn_profile_stop(buf, 48)
-    if n < 0:
-        check(-1, 'icn_profile_stop')
+    n = api().icn_profile_stop(buf, 48)
     return [dict(kernel=buf[i].kernel.decode(), launches=buf[i].launches, total_ms=buf[i].total_ms,
                  total_flops=buf[i].total_flops) for i in range(n)]

@@ -33,6 +33,45 @@ int fail(const std::string& msg) {
         if (e_ != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// Nothing throws across the C ABI: every entry runs its body under one of these.
+//   returns<R>          the body's value; if it throws, -1 and the message for icn_last_error (the count and table entries)
+//   returns_or_zero<R>  the body's value; if it throws, 0 and no message (the size and ..._supported queries)
+//   guarded             0, or -1 and the message
+//   launched            guarded, and a body that did not throw has launched: hipGetLastError() decides.  Argument checks throw
+//                       before the first device call, so a rejected call -- and every host-only entry, which takes one of the
+//                       other three -- never touches the HIP runtime (there may be no device: the ABI tests run without one)
+template <typename R, typename F>
+R returns(F&& body) {
+    try {
+        return body();
+    } catch (const std::exception& e) {
+        return (R)fail(e.what());
+    }
+}
+template <typename R, typename F>
+R returns_or_zero(F&& body) {
+    try {
+        return body();
+    } catch (const std::exception&) {
+        return 0;
+    }
+}
+template <typename F>
+int guarded(F&& body) {
+    return returns<int>([&] { body(); return 0; });
+}
+template <typename F>
+int launched(F&& body) {
+    return returns<int>([&] { body(); ICN_HIP(hipGetLastError()); return 0; });
+}
+
+// what a table entry hands back: at most `cap` elements copied (dst may be null: size query), the element count returned
+template <typename T>
+long copy_out(T* dst, size_t cap, const std::vector<T>& v) {
+    if (dst) std::memcpy(dst, v.data(), std::min(cap, v.size()) * sizeof(T));
+    return (long)v.size();
+}
+
 // icn_host_selfcheck: build every table on the host and skip the device copy (sanitizer runs of the host code need no GPU)
 thread_local bool g_dry_run = false;
 thread_local size_t g_dry_elems = 0;
@@ -501,6 +540,21 @@ void check_conv(const void* a, const void* b, const void* c, int B, int Cin, int
     if (stride != 1 && stride != 2) throw std::invalid_argument("icn: stride must be 1 or 2");
     if ((size_t)B * icn::pixels(r_in) >= (size_t)1 << 31) throw std::invalid_argument("icn: B * pixels exceeds int32 rows");
 }
+// the convolution entries' workspace (the mesh entries have check_workspace: other wording, and an alignment rule)
+void check_conv_ws(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+    if (!ws || ws_bytes < need) throw std::invalid_argument(std::string(who) + ": workspace too small");
+}
+// host arrays of icn_adam_step / icn_adam_step_dev; no_scalars: the entry's own step scalars are missing
+void check_adam(const char* who, int count, float* const* params, const float* const* grads, float* const* exp_avg,
+                float* const* exp_avg_sq, const size_t* numel, bool no_scalars, double beta1, double beta2, double eps) {
+    const std::string w(who);
+    if (count < 0 || (count > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel)) || no_scalars)
+        throw std::invalid_argument(w + ": bad arguments");
+    for (int i = 0; i < count; ++i)
+        if (numel[i] > 0 && (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i])) throw std::invalid_argument(w + ": null tensor pointer");
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0))
+        throw std::invalid_argument(w + ": betas must lie in [0, 1), eps must not be negative");
+}
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -753,7 +807,7 @@ void prof_mark_end(hipStream_t s) {
 extern "C" {
 
 int icn_profile_start(int max_launches) {
-    try {
+    return guarded([&] {
         if (max_launches < 1) throw std::invalid_argument("icn_profile_start: max_launches must be positive");
         std::lock_guard<std::mutex> lk(g_prof_mu);
         while ((int)g_prof.size() < max_launches) {
@@ -764,10 +818,7 @@ int icn_profile_start(int max_launches) {
         }
         g_prof_used = 0;
         g_prof_on = true;
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+    });
 }
 
 int icn_profile_select(const char* kernel) {
@@ -780,7 +831,7 @@ int icn_profile_select(const char* kernel) {
 }
 
 int icn_profile_stop(icn_profile_entry* out, int cap) {
-    try {
+    return returns<int>([&] {
         {
             std::lock_guard<std::mutex> lk(g_prof_mu);
             g_prof_on = false;
@@ -799,9 +850,7 @@ int icn_profile_stop(icn_profile_entry* out, int cap) {
         for (int k = 0; k < icn::PROF_KINDS && n < cap; ++k)
             if (acc[k].launches > 0) out[n++] = acc[k];
         return n;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+    });
 }
 
 
@@ -809,162 +858,113 @@ int icn_abi_version(void) { return ICN_ABI_VERSION; }
 const char* icn_last_error(void) { return g_err.c_str(); }
 
 int icn_prepare_conv(int r_in, int stride, int corner_mode) {
-    try {
-        (void)conv_tables(r_in, stride, corner_mode);
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+    return guarded([&] { (void)conv_tables(r_in, stride, corner_mode); });
 }
 
 int icn_prepare_upsample(int r_in, int corner_mode) {
-    try {
-        (void)up_tables(r_in, corner_mode);
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+    return guarded([&] { (void)up_tables(r_in, corner_mode); });
 }
 
 size_t icn_conv_workspace_bytes(int op, int B, int Cin, int Cout, int r_in, int stride) {
-    if (!args_ok(B, Cin, Cout, r_in, stride)) return 0;
-    try {
-        return conv_ws_bytes(op, B, Cin, Cout, 0, r_in, stride);
-    } catch (const std::exception&) {
-        return 0;
-    }
+    return returns_or_zero<size_t>([&] { return args_ok(B, Cin, Cout, r_in, stride) ? conv_ws_bytes(op, B, Cin, Cout, 0, r_in, stride) : 0; });
 }
 
 int icn_conv_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int r_in,
                  int stride, int corner_mode, void* ws, size_t ws_bytes, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         check_conv(x, w, y, B, Cin, Cout, r_in, stride);
         const ConvTables& t = conv_tables(r_in, stride, corner_mode);
-        hipStream_t s = static_cast<hipStream_t>(stream);
         if (icn::gather_gemm_supported(Cin, Cout)) {
-            if (!ws || ws_bytes < conv_ws_bytes(ICN_OP_CONV_FWD, B, Cin, Cout, 0, r_in, stride))
-                throw std::invalid_argument("icn_conv_fwd: workspace too small");
+            check_conv_ws("icn_conv_fwd", ws, ws_bytes, conv_ws_bytes(ICN_OP_CONV_FWD, B, Cin, Cout, 0, r_in, stride));
             conv_fwd_impl(x, w, bias, nullptr, nullptr, y, nullptr, B, Cin, Cout, 0, r_in, stride, t, ws, s);
         } else if (icn::stem_supported(Cin, Cout)) {
             icn::launch_stem_fwd(x, w, bias, y, t.fwd, B * t.Pout, t.Pin, t.Pout, Cin, Cout, t.n_in, s);
         } else {
             icn::launch_conv_generic(x, w, bias, y, t.fwd, B, t.Pin, t.Pout, Cin, Cout, 1, t.n_in, 0, s);
         }
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+    });
 }
 
 int icn_conv_bwd_data(const float* dy, const float* w, float* dx, int B, int Cin, int Cout, int r_in, int stride,
                       int corner_mode, void* ws, size_t ws_bytes, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         check_conv(dy, w, dx, B, Cin, Cout, r_in, stride);
         const ConvTables& t = conv_tables(r_in, stride, corner_mode);
-        hipStream_t s = static_cast<hipStream_t>(stream);
         if (icn::gather_gemm_supported(Cout, Cin)) {
-            if (!ws || ws_bytes < conv_ws_bytes(ICN_OP_CONV_BWD_DATA, B, Cin, Cout, 0, r_in, stride))
-                throw std::invalid_argument("icn_conv_bwd_data: workspace too small");
+            check_conv_ws("icn_conv_bwd_data", ws, ws_bytes, conv_ws_bytes(ICN_OP_CONV_BWD_DATA, B, Cin, Cout, 0, r_in, stride));
             conv_bwd_data_impl(dy, nullptr, w, nullptr, dx, B, Cin, Cout, 0, r_in, stride, t, ws, s);
         } else {
             icn::launch_conv_generic(dy, w, nullptr, dx, t.bwd, B, t.Pout, t.Pin, Cout, Cin, t.E, t.n_out, 1, s);
         }
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+    });
 }
 
 int icn_conv_bwd_weight(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int r_in,
                         int stride, int corner_mode, void* ws, size_t ws_bytes, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         check_conv(x, dy, dw, B, Cin, Cout, r_in, stride);
         const ConvTables& t = conv_tables(r_in, stride, corner_mode);
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        if (!ws || ws_bytes < conv_ws_bytes(ICN_OP_CONV_BWD_WEIGHT, B, Cin, Cout, 0, r_in, stride))
-            throw std::invalid_argument("icn_conv_bwd_weight: workspace too small");
+        check_conv_ws("icn_conv_bwd_weight", ws, ws_bytes, conv_ws_bytes(ICN_OP_CONV_BWD_WEIGHT, B, Cin, Cout, 0, r_in, stride));
         conv_bwd_weight_impl(x, dy, nullptr, dw, dbias, nullptr, nullptr, B, Cin, Cout, 0, t, ws, s);
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+    });
 }
 
 // ---- pair forms: two convolutions of the same input (reference models.py:37-39 conv00 / conv10, 59-60) in one launch per
 // pass: forward with the output channels concatenated, bwd-data with the two dy concatenated along the GEMM's K axis
 // (one dx, no separate gradient add), bwd-weight with the shared x gathered once.
 int icn_conv_pair_supported(int B, int Cin, int Cout0, int Cout1, int r_in, int stride) {
-    try {
-        return pair_supported(B, Cin, Cout0, Cout1, r_in, stride) ? 1 : 0;
-    } catch (const std::exception&) {
-        return 0;
-    }
+    return returns_or_zero<int>([&] { return pair_supported(B, Cin, Cout0, Cout1, r_in, stride) ? 1 : 0; });
 }
 
 size_t icn_conv_pair_workspace_bytes(int op, int B, int Cin, int Cout0, int Cout1, int r_in, int stride) {
-    try {
-        if (!pair_supported(B, Cin, Cout0, Cout1, r_in, stride)) return 0;
-        return conv_ws_bytes(op, B, Cin, Cout0, Cout1, r_in, stride);
-    } catch (const std::exception&) {
-        return 0;
-    }
+    return returns_or_zero<size_t>([&] {
+        return pair_supported(B, Cin, Cout0, Cout1, r_in, stride) ? conv_ws_bytes(op, B, Cin, Cout0, Cout1, r_in, stride) : 0;
+    });
 }
 
 int icn_conv_pair_fwd(const float* x, const float* w0, const float* bias0, const float* w1, const float* bias1, float* y0, float* y1,
                       int B, int Cin, int Cout0, int Cout1, int r_in, int stride, int corner_mode, void* ws, size_t ws_bytes,
                       void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         check_conv(x, w0, y0, B, Cin, Cout0, r_in, stride);
         if (!w1 || !y1) throw std::invalid_argument("icn: null tensor pointer");
         if ((bias0 == nullptr) != (bias1 == nullptr)) throw std::invalid_argument("icn_conv_pair_fwd: both biases or none");
         if (!pair_supported(B, Cin, Cout0, Cout1, r_in, stride)) throw std::invalid_argument("icn_conv_pair_fwd: unsupported shape");
-        if (!ws || ws_bytes < conv_ws_bytes(ICN_OP_CONV_FWD, B, Cin, Cout0, Cout1, r_in, stride))
-            throw std::invalid_argument("icn_conv_pair_fwd: workspace too small");
+        check_conv_ws("icn_conv_pair_fwd", ws, ws_bytes, conv_ws_bytes(ICN_OP_CONV_FWD, B, Cin, Cout0, Cout1, r_in, stride));
         const ConvTables& t = conv_tables(r_in, stride, corner_mode);
-        conv_fwd_impl(x, w0, bias0, w1, bias1, y0, y1, B, Cin, Cout0, Cout1, r_in, stride, t, ws, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        conv_fwd_impl(x, w0, bias0, w1, bias1, y0, y1, B, Cin, Cout0, Cout1, r_in, stride, t, ws, s);
+    });
 }
 
 int icn_conv_pair_bwd_data(const float* dy0, const float* dy1, const float* w0, const float* w1, float* dx, int B, int Cin, int Cout0,
                            int Cout1, int r_in, int stride, int corner_mode, void* ws, size_t ws_bytes, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         check_conv(dy0, w0, dx, B, Cin, Cout0, r_in, stride);
         if (!dy1 || !w1) throw std::invalid_argument("icn: null tensor pointer");
         if (!pair_supported(B, Cin, Cout0, Cout1, r_in, stride)) throw std::invalid_argument("icn_conv_pair_bwd_data: unsupported shape");
-        if (!ws || ws_bytes < conv_ws_bytes(ICN_OP_CONV_BWD_DATA, B, Cin, Cout0, Cout1, r_in, stride))
-            throw std::invalid_argument("icn_conv_pair_bwd_data: workspace too small");
+        check_conv_ws("icn_conv_pair_bwd_data", ws, ws_bytes, conv_ws_bytes(ICN_OP_CONV_BWD_DATA, B, Cin, Cout0, Cout1, r_in, stride));
         const ConvTables& t = conv_tables(r_in, stride, corner_mode);
-        conv_bwd_data_impl(dy0, dy1, w0, w1, dx, B, Cin, Cout0, Cout1, r_in, stride, t, ws, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        conv_bwd_data_impl(dy0, dy1, w0, w1, dx, B, Cin, Cout0, Cout1, r_in, stride, t, ws, s);
+    });
 }
 
 int icn_conv_pair_bwd_weight(const float* x, const float* dy0, const float* dy1, float* dw0, float* dbias0, float* dw1, float* dbias1,
                              int B, int Cin, int Cout0, int Cout1, int r_in, int stride, int corner_mode, void* ws, size_t ws_bytes,
                              void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         check_conv(x, dy0, dw0, B, Cin, Cout0, r_in, stride);
         if (!dy1 || !dw1) throw std::invalid_argument("icn: null tensor pointer");
         if (!pair_supported(B, Cin, Cout0, Cout1, r_in, stride)) throw std::invalid_argument("icn_conv_pair_bwd_weight: unsupported shape");
-        if (!ws || ws_bytes < conv_ws_bytes(ICN_OP_CONV_BWD_WEIGHT, B, Cin, Cout0, Cout1, r_in, stride))
-            throw std::invalid_argument("icn_conv_pair_bwd_weight: workspace too small");
+        check_conv_ws("icn_conv_pair_bwd_weight", ws, ws_bytes, conv_ws_bytes(ICN_OP_CONV_BWD_WEIGHT, B, Cin, Cout0, Cout1, r_in, stride));
         const ConvTables& t = conv_tables(r_in, stride, corner_mode);
-        conv_bwd_weight_impl(x, dy0, dy1, dw0, dbias0, dw1, dbias1, B, Cin, Cout0, Cout1, t, ws, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        conv_bwd_weight_impl(x, dy0, dy1, dw0, dbias0, dw1, dbias1, B, Cin, Cout0, Cout1, t, ws, s);
+    });
 }
 
 // ---- composite upsample + conv (forward): y_k = conv_k(upsample(x)), k = 0 (, 1), from the COARSE tensor ------------------
@@ -1004,31 +1004,25 @@ size_t upconv_ws_bytes(int B, int Cin, int C0, int C1, int r_in) {
 }  // namespace
 
 int icn_upconv_supported(int B, int Cin, int Cout0, int Cout1, int r_in) {
-    try {
-        return upconv_supported(B, Cin, Cout0, Cout1, r_in) ? 1 : 0;
-    } catch (const std::exception&) {
-        return 0;
-    }
+    return returns_or_zero<int>([&] { return upconv_supported(B, Cin, Cout0, Cout1, r_in) ? 1 : 0; });
 }
 
 size_t icn_upconv_workspace_bytes(int B, int Cin, int Cout0, int Cout1, int r_in) {
-    try {
+    return returns_or_zero<size_t>([&] {
         return upconv_supported(B, Cin, Cout0, Cout1, r_in) ? upconv_ws_bytes(B, Cin, Cout0, Cout1, r_in) : 0;
-    } catch (const std::exception&) {
-        return 0;
-    }
+    });
 }
 
 int icn_upconv_fwd(const float* x, const float* w0, const float* bias0, const float* w1, const float* bias1, float* y0, float* y1, int B,
                    int Cin, int Cout0, int Cout1, int r_in, int corner_mode, void* ws, size_t ws_bytes, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!x || !w0 || !y0) throw std::invalid_argument("icn_upconv_fwd: null tensor pointer");
         if ((w1 == nullptr) != (Cout1 == 0) || (w1 && !y1)) throw std::invalid_argument("icn_upconv_fwd: second branch needs w1, y1 and Cout1 > 0");
         if (w1 && (bias0 == nullptr) != (bias1 == nullptr)) throw std::invalid_argument("icn_upconv_fwd: both biases or none");
         if (corner_mode != 0 && corner_mode != 1) throw std::invalid_argument("icn: corner_mode must be 0 (zeros) or 1 (average)");
         if (!upconv_supported(B, Cin, Cout0, Cout1, r_in)) throw std::invalid_argument("icn_upconv_fwd: unsupported shape");
-        if (!ws || ws_bytes < upconv_ws_bytes(B, Cin, Cout0, Cout1, r_in)) throw std::invalid_argument("icn_upconv_fwd: workspace too small");
-        hipStream_t s = static_cast<hipStream_t>(stream);
+        check_conv_ws("icn_upconv_fwd", ws, ws_bytes, upconv_ws_bytes(B, Cin, Cout0, Cout1, r_in));
         const int C = Cout0 + Cout1;
         if (upconv_use_dense(B, Cin, Cout0, Cout1, r_in)) {
             const UpconvBwdDev& d = upconv_bwd_tables(r_in, corner_mode);
@@ -1060,8 +1054,7 @@ int icn_upconv_fwd(const float* x, const float* w0, const float* bias0, const fl
                 icn::launch_upconv_scatter(z, bias, y0, y1, sc.idx, sc.coef, nullptr, B, 7 * d.Pc, d.Pf, d.Pf, Cout0, Cout1, sc.W, 0, s);
             icn::launch_upconv_scatter(z, nullptr, y0, y1, sc.ovf_idx, sc.ovf_coef, sc.ovf_rows, B, 7 * d.Pc, sc.n_ovf, d.Pf, Cout0, Cout1,
                                        sc.W_ovf, 1, s);
-            ICN_HIP(hipGetLastError());
-            return 0;
+            return;
         }
         const UpconvDev& t = upconv_tables(r_in, corner_mode);
         const size_t wbytes = align256((size_t)icn::UPCONV_TAPS * C * Cin * sizeof(float));
@@ -1084,11 +1077,7 @@ int icn_upconv_fwd(const float* x, const float* w0, const float* bias0, const fl
         for (int i = 0; i < t.nseg; ++i) taps += (double)t.seg_cnt[i] * __builtin_popcount(t.seg_mask[i]);   // ~0.68 of the 7 per row
         a.algo_flops = 2.0 * Cin * C * (double)B * taps;         // of the two operators it replaces (2 * 7 * Cin * C * B * Pf)
         icn::launch_gather_gemm_auto(a, s);
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+    });
 }
 
 // ---- backward of the same pair through the coarse-level aggregate g (csrc/icn_geometry.h build_upconv_bwd) ------------------
@@ -1116,19 +1105,13 @@ UpconvBwdWs upconv_bwd_ws(int B, int Cin, int C0, int C1, int r_in) {
 }  // namespace
 
 int icn_upconv_bwd_supported(int B, int Cin, int Cout0, int Cout1, int r_in, int corner_mode) {
-    try {
-        return upconv_bwd_supported(B, Cin, Cout0, Cout1, r_in, corner_mode) ? 1 : 0;
-    } catch (const std::exception&) {
-        return 0;
-    }
+    return returns_or_zero<int>([&] { return upconv_bwd_supported(B, Cin, Cout0, Cout1, r_in, corner_mode) ? 1 : 0; });
 }
 
 size_t icn_upconv_bwd_workspace_bytes(int B, int Cin, int Cout0, int Cout1, int r_in) {
-    try {
+    return returns_or_zero<size_t>([&] {
         return upconv_bwd_supported(B, Cin, Cout0, Cout1, r_in, ICN_CORNER_AVERAGE) ? upconv_bwd_ws(B, Cin, Cout0, Cout1, r_in).total : 0;
-    } catch (const std::exception&) {
-        return 0;
-    }
+    });
 }
 
 int icn_upconv_bwd(const float* x, const float* dy0, const float* dy1, const float* w0, const float* w1, float* dx, float* dw0,
@@ -1141,15 +1124,15 @@ int icn_upconv_bwd(const float* x, const float* dy0, const float* dy1, const flo
 int icn_upconv_bwd_streams(const float* x, const float* dy0, const float* dy1, const float* w0, const float* w1, float* dx, float* dw0,
                            float* dbias0, float* dw1, float* dbias1, int B, int Cin, int Cout0, int Cout1, int r_in, int corner_mode,
                            void* ws, size_t ws_bytes, void* stream, void* weight_stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!dy0 || (Cout1 > 0) != (dy1 != nullptr)) throw std::invalid_argument("icn_upconv_bwd: dy1 goes with Cout1 > 0");
         if (dx && (!w0 || (Cout1 > 0 && !w1))) throw std::invalid_argument("icn_upconv_bwd: dx needs the weights");
         if (dw0 && (!x || (Cout1 > 0 && !dw1))) throw std::invalid_argument("icn_upconv_bwd: dw needs x (and dw1 for a pair)");
         if (!upconv_bwd_supported(B, Cin, Cout0, Cout1, r_in, corner_mode)) throw std::invalid_argument("icn_upconv_bwd: unsupported shape / corner mode");
         const UpconvBwdWs wo = upconv_bwd_ws(B, Cin, Cout0, Cout1, r_in);
-        if (!ws || ws_bytes < wo.total) throw std::invalid_argument("icn_upconv_bwd: workspace too small");
+        check_conv_ws("icn_upconv_bwd", ws, ws_bytes, wo.total);
         const UpconvBwdDev& t = upconv_bwd_tables(r_in, corner_mode);
-        hipStream_t s = static_cast<hipStream_t>(stream);
         const int C = Cout0 + Cout1, M = B * t.Pc;
         float* g = reinterpret_cast<float*>(at(ws, wo.g));
         // 1. g[b, s, t, :] = sum_p U[nbr_t(p), s] [dy0 | dy1][b, p, :]
@@ -1199,35 +1182,25 @@ int icn_upconv_bwd_streams(const float* x, const float* dy0, const float* dy1, c
             a.algo_flops = 2.0 * 7 * Cin * C * (double)B * t.Pc;            // executed: a quarter of the fine-level bwd-weight
             icn::launch_wgrad(a, sw);
         }
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+    });
 }
 
 int icn_upsample_fwd(const float* x, float* y, int B, int C, int r_in, int corner_mode, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!x || !y || B < 1 || C < 1) throw std::invalid_argument("icn_upsample_fwd: bad arguments");
         const UpTables& t = up_tables(r_in, corner_mode);
-        icn::launch_spmm_ell(x, y, t.idx_f, t.coef_f, B, t.Pc, t.Pf, C, t.Wf, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        icn::launch_spmm_ell(x, y, t.idx_f, t.coef_f, B, t.Pc, t.Pf, C, t.Wf, s);
+    });
 }
 
 int icn_upsample_bwd(const float* dy, float* dx, int B, int C, int r_in, int corner_mode, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!dy || !dx || B < 1 || C < 1) throw std::invalid_argument("icn_upsample_bwd: bad arguments");
         const UpTables& t = up_tables(r_in, corner_mode);
-        icn::launch_spmm_ell(dy, dx, t.idx_b, t.coef_b, B, t.Pf, t.Pc, C, t.Wb, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        icn::launch_spmm_ell(dy, dx, t.idx_b, t.coef_b, B, t.Pf, t.Pc, C, t.Wb, s);
+    });
 }
 
 // ---- argument checks shared by the loss, point-to-mesh and sampling entries; the ..._ok forms are what their workspace queries ask
@@ -1254,17 +1227,13 @@ size_t icn_p2p_loss_workspace_floats(int B, int r) {
 
 int icn_p2p_loss_fwd(const float* grid, const float* target, int B, int r, float f_pos, float f_nor, float f_lap, int lap_mode,
                      float* terms, float* ws, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!grid || !target || !terms || !ws) throw std::invalid_argument("icn_p2p_loss_fwd: null pointer");
         check_grid_batch("icn_p2p_loss_fwd", B, r);
         if (lap_mode < 0 || lap_mode > 3) throw std::invalid_argument("icn_p2p_loss_fwd: lap_mode must be a combination of ICN_LAP_*");
-        icn::launch_p2p_loss_fwd(grid, target, vertex_faces(r), ws, terms, B, icn::pixels(r), 1 << r, f_pos, f_nor, f_lap, lap_mode,
-                                 static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        icn::launch_p2p_loss_fwd(grid, target, vertex_faces(r), ws, terms, B, icn::pixels(r), 1 << r, f_pos, f_nor, f_lap, lap_mode, s);
+    });
 }
 
 size_t icn_p2p_loss_bwd_workspace_floats(int B, int r) {
@@ -1273,18 +1242,15 @@ size_t icn_p2p_loss_bwd_workspace_floats(int B, int r) {
 
 int icn_p2p_loss_bwd(const float* grid, const float* target, const float* upstream, int B, int r, float f_pos, float f_nor,
                      float f_lap, int lap_mode, float* dgrid, float* ws, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!grid || !target || !upstream || !dgrid) throw std::invalid_argument("icn_p2p_loss_bwd: null pointer");
         check_grid_batch("icn_p2p_loss_bwd", B, r);
         if ((f_nor != 0.f || f_lap != 0.f) && !ws) throw std::invalid_argument("icn_p2p_loss_bwd: workspace needed for the mesh terms");
         if (lap_mode < 0 || lap_mode > 3) throw std::invalid_argument("icn_p2p_loss_bwd: lap_mode must be a combination of ICN_LAP_*");
         icn::launch_p2p_loss_bwd(grid, target, vertex_faces(r), upstream, f_pos, f_nor, f_lap, lap_mode, dgrid, ws, B, icn::pixels(r),
-                                 1 << r, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+                                 1 << r, s);
+    });
 }
 
 // ---- mesh regularisers of the surface loss ------------------------------------------------------------------------------
@@ -1301,16 +1267,12 @@ size_t icn_mesh_reg_workspace_floats(int B, int r) {
 
 int icn_mesh_reg_fwd(const float* grid, int B, int r, float f_edge, float f_ncons, float f_smooth, float edge_length, float* terms,
                      float* ws, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!grid || !terms || !ws) throw std::invalid_argument("icn_mesh_reg_fwd: null pointer");
         check_mesh_reg("icn_mesh_reg_fwd", B, r, edge_length);
-        icn::launch_mesh_reg_fwd(grid, vertex_stencils(r), ws, terms, B, icn::pixels(r), 1 << r, f_edge, f_ncons, f_smooth, edge_length,
-                                 static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        icn::launch_mesh_reg_fwd(grid, vertex_stencils(r), ws, terms, B, icn::pixels(r), 1 << r, f_edge, f_ncons, f_smooth, edge_length, s);
+    });
 }
 
 size_t icn_mesh_reg_bwd_workspace_floats(int B, int r) {
@@ -1319,77 +1281,59 @@ size_t icn_mesh_reg_bwd_workspace_floats(int B, int r) {
 
 int icn_mesh_reg_bwd(const float* grid, const float* upstream, int B, int r, float f_edge, float f_ncons, float f_smooth,
                      float edge_length, float* dgrid, float* ws, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!grid || !upstream || !dgrid) throw std::invalid_argument("icn_mesh_reg_bwd: null pointer");
         check_mesh_reg("icn_mesh_reg_bwd", B, r, edge_length);
         if (f_smooth != 0.f && !ws) throw std::invalid_argument("icn_mesh_reg_bwd: null pointer (workspace needed for the smoothness term)");
         icn::launch_mesh_reg_bwd(grid, vertex_stencils(r), upstream, f_edge, f_ncons, f_smooth, edge_length, dgrid, ws, B, icn::pixels(r),
-                                 1 << r, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+                                 1 << r, s);
+    });
 }
 
 // ---- KL term and reparameterisation of the VAE -----------------------------------------------------------------------
 size_t icn_kld_workspace_floats(size_t n) { return n < 1 ? 0 : (size_t)icn::kld_blocks(n); }
 
 int icn_kld_fwd(const float* mu, const float* logvar, size_t n, float* out, float* ws, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!mu || !logvar || !out || !ws || n < 1) throw std::invalid_argument("icn_kld_fwd: bad arguments");
-        icn::launch_kld_fwd(mu, logvar, n, out, ws, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        icn::launch_kld_fwd(mu, logvar, n, out, ws, s);
+    });
 }
 
 int icn_kld_bwd(const float* mu, const float* logvar, const float* upstream, size_t n, float* dmu, float* dlogvar, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!mu || !logvar || !upstream || !dmu || !dlogvar || n < 1) throw std::invalid_argument("icn_kld_bwd: bad arguments");
-        icn::launch_kld_bwd(mu, logvar, upstream, n, dmu, dlogvar, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        icn::launch_kld_bwd(mu, logvar, upstream, n, dmu, dlogvar, s);
+    });
 }
 
 int icn_reparam_fwd(const float* mu, const float* logvar, const float* eps, size_t n, float* z, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!mu || !logvar || !eps || !z || n < 1) throw std::invalid_argument("icn_reparam_fwd: bad arguments");
-        icn::launch_reparam_fwd(mu, logvar, eps, n, z, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        icn::launch_reparam_fwd(mu, logvar, eps, n, z, s);
+    });
 }
 
 int icn_reparam_bwd(const float* dz, const float* logvar, const float* eps, size_t n, float* dmu, float* dlogvar, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!dz || !logvar || !eps || !dmu || !dlogvar || n < 1) throw std::invalid_argument("icn_reparam_bwd: bad arguments");
-        icn::launch_reparam_bwd(dz, logvar, eps, n, dmu, dlogvar, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        icn::launch_reparam_bwd(dz, logvar, eps, n, dmu, dlogvar, s);
+    });
 }
 
 int icn_point_to_mesh(const float* points, const float* vertices, const int32_t* faces, int B, int P, int V, int F, float* dist2,
                       int32_t* face, int32_t* kind, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!points || !vertices || !faces || !dist2 || !face || !kind) throw std::invalid_argument("icn_point_to_mesh: null pointer");
         check_mesh_sizes("icn_point_to_mesh", B, P, V, F);
-        icn::launch_point_to_mesh(points, vertices, faces, B, P, V, F, dist2, face, kind, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        icn::launch_point_to_mesh(points, vertices, faces, B, P, V, F, dist2, face, kind, s);
+    });
 }
 
 size_t icn_point_to_mesh_bwd_workspace_bytes(int B, int P, int V, int F) {
@@ -1399,18 +1343,15 @@ size_t icn_point_to_mesh_bwd_workspace_bytes(int B, int P, int V, int F) {
 int icn_point_to_mesh_bwd(const float* points, const float* vertices, const int32_t* faces, const int32_t* face, const int32_t* kind,
                           const float* ddist, int B, int P, int V, int F, float* dpoints, float* dvertices, void* ws, size_t ws_bytes,
                           void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return guarded([&] {                                             // (not `launched`: the early way out touches no device)
         if (!points || !vertices || !faces || !face || !kind || !ddist) throw std::invalid_argument("icn_point_to_mesh_bwd: null pointer");
         check_mesh_sizes("icn_point_to_mesh_bwd", B, P, V, F);
         if (dvertices) check_workspace("icn_point_to_mesh_bwd", ws, ws_bytes, icn::vertex_records_bytes((size_t)B * P));
-        if (!dpoints && !dvertices) return 0;                        // no gradient asked for
-        icn::launch_point_to_mesh_bwd(points, vertices, faces, face, kind, ddist, B, P, V, F, dpoints, dvertices, ws,
-                                      static_cast<hipStream_t>(stream));
+        if (!dpoints && !dvertices) return;                          // no gradient asked for
+        icn::launch_point_to_mesh_bwd(points, vertices, faces, face, kind, ddist, B, P, V, F, dpoints, dvertices, ws, s);
         ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+    });
 }
 
 size_t icn_point_to_mesh_grid_workspace_bytes(int B, int P, int V, int F) {
@@ -1419,16 +1360,13 @@ size_t icn_point_to_mesh_grid_workspace_bytes(int B, int P, int V, int F) {
 
 int icn_point_to_mesh_grid(const float* points, const float* vertices, const int32_t* faces, int B, int P, int V, int F, float* dist2,
                            int32_t* face, int32_t* kind, void* ws, size_t ws_bytes, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!points || !vertices || !faces || !dist2 || !face || !kind) throw std::invalid_argument("icn_point_to_mesh_grid: null pointer");
         check_mesh_sizes("icn_point_to_mesh_grid", B, P, V, F);
         check_workspace("icn_point_to_mesh_grid", ws, ws_bytes, icn::point_to_mesh_grid_bytes(B, F));
-        ICN_HIP(icn::launch_point_to_mesh_grid(points, vertices, faces, B, P, V, F, dist2, face, kind, ws, static_cast<hipStream_t>(stream)));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        ICN_HIP(icn::launch_point_to_mesh_grid(points, vertices, faces, B, P, V, F, dist2, face, kind, ws, s));
+    });
 }
 
 size_t icn_mesh_sample_workspace_bytes(int B, int S, int V, int F) {
@@ -1437,16 +1375,13 @@ size_t icn_mesh_sample_workspace_bytes(int B, int S, int V, int F) {
 
 int icn_mesh_sample_fwd(const float* vertices, const int32_t* faces, const float* u, int B, int S, int V, int F, float* points,
                         int32_t* face, float* weights, void* ws, size_t ws_bytes, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!vertices || !faces || !u || !points || !face || !weights) throw std::invalid_argument("icn_mesh_sample_fwd: null pointer");
         check_mesh_sizes("icn_mesh_sample_fwd", B, S, V, F);
         check_workspace("icn_mesh_sample_fwd", ws, ws_bytes, icn::mesh_sample_cdf_bytes(B, F));
-        icn::launch_mesh_sample_fwd(vertices, faces, u, B, S, V, F, points, face, weights, ws, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        icn::launch_mesh_sample_fwd(vertices, faces, u, B, S, V, F, points, face, weights, ws, s);
+    });
 }
 
 size_t icn_mesh_sample_bwd_workspace_bytes(int B, int S, int V, int F) {
@@ -1455,63 +1390,43 @@ size_t icn_mesh_sample_bwd_workspace_bytes(int B, int S, int V, int F) {
 
 int icn_mesh_sample_bwd(const int32_t* faces, const int32_t* face, const float* weights, const float* dpoints, int B, int S, int V,
                         int F, float* dvertices, void* ws, size_t ws_bytes, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!faces || !face || !weights || !dpoints || !dvertices) throw std::invalid_argument("icn_mesh_sample_bwd: null pointer");
         check_mesh_sizes("icn_mesh_sample_bwd", B, S, V, F);
         check_workspace("icn_mesh_sample_bwd", ws, ws_bytes, icn::vertex_records_bytes((size_t)B * S));
-        icn::launch_mesh_sample_bwd(faces, face, weights, dpoints, B, S, V, F, dvertices, ws, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        icn::launch_mesh_sample_bwd(faces, face, weights, dpoints, B, S, V, F, dvertices, ws, s);
+    });
 }
 
 int icn_adam_step(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                   const size_t* numel, const float* step_size, const float* bc2_sqrt, double beta1, double beta2, double eps,
                   double weight_decay, void* stream) {
-    try {
-        if (count < 0 || (count > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel || !step_size || !bc2_sqrt)))
-            throw std::invalid_argument("icn_adam_step: bad arguments");
-        for (int i = 0; i < count; ++i)
-            if (numel[i] > 0 && (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i]))
-                throw std::invalid_argument("icn_adam_step: null tensor pointer");
-        if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0))
-            throw std::invalid_argument("icn_adam_step: betas must lie in [0, 1), eps must not be negative");
-        if (count == 0) return 0;
-        icn::launch_adam(count, params, grads, exp_avg, exp_avg_sq, numel, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay,
-                         static_cast<hipStream_t>(stream));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return guarded([&] {                                             // (not `launched`: nothing to do touches no device)
+        check_adam("icn_adam_step", count, params, grads, exp_avg, exp_avg_sq, numel, count > 0 && (!step_size || !bc2_sqrt), beta1, beta2, eps);
+        if (count == 0) return;
+        icn::launch_adam(count, params, grads, exp_avg, exp_avg_sq, numel, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay, s);
         ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+    });
 }
 
 int icn_adam_step_dev(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                       const size_t* numel, const float* scalars_dev, double beta1, double beta2, double eps, double weight_decay,
                       void* stream) {
-    try {
-        if (count < 0 || (count > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel)) || !scalars_dev)
-            throw std::invalid_argument("icn_adam_step_dev: bad arguments");
-        for (int i = 0; i < count; ++i)
-            if (numel[i] > 0 && (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i]))
-                throw std::invalid_argument("icn_adam_step_dev: null tensor pointer");
-        if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0))
-            throw std::invalid_argument("icn_adam_step_dev: betas must lie in [0, 1), eps must not be negative");
-        if (count == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return guarded([&] {
+        check_adam("icn_adam_step_dev", count, params, grads, exp_avg, exp_avg_sq, numel, !scalars_dev, beta1, beta2, eps);
+        if (count == 0) return;
         std::vector<float> same(count, 0.f);              // one step count for all tensors: one group of launches
-        icn::launch_adam(count, params, grads, exp_avg, exp_avg_sq, numel, same.data(), same.data(), beta1, beta2, eps, weight_decay,
-                         static_cast<hipStream_t>(stream), scalars_dev);
+        icn::launch_adam(count, params, grads, exp_avg, exp_avg_sq, numel, same.data(), same.data(), beta1, beta2, eps, weight_decay, s,
+                         scalars_dev);
         ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+    });
 }
 
 long icn_table_stream_k(int ntiles, int grid, int nk, int ku, int32_t* out, size_t cap) {
-    try {
+    return returns<long>([&] {
         if (ntiles < 1 || grid < 8 || grid % 8 != 0 || nk < 1 || ku < 1)
             throw std::invalid_argument("icn_table_stream_k: grid must be a positive multiple of 8, nk and ku positive");
         size_t n = 0;
@@ -1528,14 +1443,11 @@ long icn_table_stream_k(int ntiles, int grid, int nk, int ku, int32_t* out, size
             }
         }
         return (long)n;
-    } catch (const std::exception& e) {
-        fail(e.what());
-        return -1;
-    }
+    });
 }
 
 long icn_table_tile_lists(int r_in, int stride, int corner_mode, int B, int bm, int ntn, int grid, int32_t* out, size_t cap) {
-    try {
+    return returns<long>([&] {
         if (r_in < 1 || r_in > 8 || stride != 2 || B < 1 || (bm != 64 && bm != 128) || ntn < 1 || grid < 8 || grid % 256 != 0)
             throw std::invalid_argument("icn_table_tile_lists: stride-2 tables, bm 64 / 128, grid a multiple of 256");
         std::vector<int32_t> bwd, perm;
@@ -1546,32 +1458,17 @@ long icn_table_tile_lists(int r_in, int stride, int corner_mode, int B, int bm, 
         const int Pd = icn::pixels(r_in), M = B * Pd, ntiles = ((M + bm - 1) / bm) * ntn;
         std::vector<int> h;
         icn::build_tile_lists(m32.data(), M, Pd, bm, ntn, ntiles, grid, grid / 256, h);
-        if (out)
-            for (size_t i = 0; i < h.size() && i < cap; ++i) out[i] = h[i];
-        return (long)h.size();
-    } catch (const std::exception& e) {
-        fail(e.what());
-        return -1;
-    }
+        return copy_out(out, cap, h);
+    });
 }
 
 int icn_set_debug_flags(int flags) { return icn::set_debug_flags(flags); }
 
 int icn_get_arith(void) {
-    try {
-        return icn::arith_mode();
-    } catch (const std::exception& e) {
-        fail(e.what());
-        return -1;
-    }
+    return returns<int>([&] { return icn::arith_mode(); });
 }
 int icn_set_arith(int mode) {
-    try {
-        return icn::set_arith_mode(mode);
-    } catch (const std::exception& e) {
-        fail(e.what());
-        return -1;
-    }
+    return returns<int>([&] { return icn::set_arith_mode(mode); });
 }
 unsigned icn_build_flags(void) { return icn::build_flags(); }
 
@@ -1584,7 +1481,7 @@ long icn_host_selfcheck(int r, int corner_mode) {
     // Every host-side table builder and planner the device paths use at level r, with the device copies skipped: lets the
     // whole host side of the library run under ASan / UBSan on a machine without a GPU (tools/asan_host.sh).  Returns the
     // number of table elements that would have been uploaded.
-    try {
+    return returns<long>([&] {
         if (r < 0 || r > 7 || (corner_mode != 0 && corner_mode != 1)) throw std::invalid_argument("icn_host_selfcheck: r in [0, 7], corner_mode 0 / 1");
         g_dry_run = true;
         g_dry_elems = 0;
@@ -1617,17 +1514,11 @@ long icn_host_selfcheck(int r, int corner_mode) {
                     plan += icn_upconv_bwd_workspace_bytes(B, ci, co, co, r) != 0;
                 }
         return (long)(g_dry_elems + plan);
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+    });
 }
 
 int icn_device_status(int clear) {
-    try {
-        return icn::device_status(clear);
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+    return returns<int>([&] { return icn::device_status(clear); });
 }
 
 // ---- fused BatchNorm + ReLU ---------------------------------------------------------------------------------
@@ -1636,107 +1527,86 @@ size_t icn_bn_workspace_floats(int M, int C) { return (M < 1 || C < 1) ? 0 : (si
 
 int icn_bn_stats(const float* x, int M, int C, float eps, float momentum, float* running_mean, float* running_var, float* stat,
                  float* ws, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!x || !stat || !ws || M < 1) throw std::invalid_argument("icn_bn_stats: bad arguments");
         if (!icn::bn_supported(C)) throw std::invalid_argument("icn_bn_stats: unsupported channel count");
-        icn::launch_bn_stats(x, M, C, eps, momentum, running_mean, running_var, stat, ws, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        icn::launch_bn_stats(x, M, C, eps, momentum, running_mean, running_var, stat, ws, s);
+    });
 }
 
 int icn_bn_stats2(const float* a, const float* b, int M, int C, float eps_a, float momentum_a, float* running_mean_a,
                   float* running_var_a, float* stat_a, float eps_b, float momentum_b, float* running_mean_b, float* running_var_b,
                   float* stat_b, float* ws, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!a || !b || !stat_a || !stat_b || !ws || M < 1) throw std::invalid_argument("icn_bn_stats2: bad arguments");
         if ((running_mean_a == nullptr) != (running_var_a == nullptr) || (running_mean_b == nullptr) != (running_var_b == nullptr))
             throw std::invalid_argument("icn_bn_stats2: running mean and variance go together");
         if (!icn::bn_supported(C)) throw std::invalid_argument("icn_bn_stats2: unsupported channel count");
         icn::launch_bn_stats2(a, b, M, C, eps_a, momentum_a, running_mean_a, running_var_a, stat_a, eps_b, momentum_b, running_mean_b,
-                              running_var_b, stat_b, ws, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+                              running_var_b, stat_b, ws, s);
+    });
 }
 
 int icn_bn_relu_fwd(const float* a, const float* b, const float* stat_a, const float* stat_b, const float* gamma_a,
                     const float* beta_a, const float* gamma_b, const float* beta_b, float* y, int M, int C, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!a || !stat_a || !gamma_a || !beta_a || !y || M < 1) throw std::invalid_argument("icn_bn_relu_fwd: bad arguments");
         if (b && (!stat_b || !gamma_b || !beta_b)) throw std::invalid_argument("icn_bn_relu_fwd: second input needs its stats");
         if (!icn::bn_supported(C)) throw std::invalid_argument("icn_bn_relu_fwd: unsupported channel count");
-        icn::launch_bn_relu_fwd(a, b, stat_a, stat_b, gamma_a, beta_a, gamma_b, beta_b, y, M, C, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        icn::launch_bn_relu_fwd(a, b, stat_a, stat_b, gamma_a, beta_a, gamma_b, beta_b, y, M, C, s);
+    });
 }
 
 int icn_bn_relu_bwd(const float* dy, const float* a, const float* b, const float* stat_a, const float* stat_b, const float* gamma_a,
                     const float* beta_a, const float* gamma_b, const float* beta_b, float* da, float* db, float* sums, float* ws, int M,
                     int C, float* dbeta_a, float* dgamma_a, float* dbeta_b, float* dgamma_b, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!dy || !a || !stat_a || !gamma_a || !beta_a || !da || !sums || !ws || M < 1)
             throw std::invalid_argument("icn_bn_relu_bwd: bad arguments");
         if (b && (!stat_b || !gamma_b || !beta_b || !db)) throw std::invalid_argument("icn_bn_relu_bwd: second input needs its buffers");
         if (!icn::bn_supported(C)) throw std::invalid_argument("icn_bn_relu_bwd: unsupported channel count");
         icn::launch_bn_relu_bwd(dy, a, b, stat_a, stat_b, gamma_a, beta_a, gamma_b, beta_b, da, db, sums, ws, M, C, dbeta_a, dgamma_a,
-                                dbeta_b, dgamma_b, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+                                dbeta_b, dgamma_b, s);
+    });
 }
 
 // ---- fused 1x1 head + tanh ------------------------------------------------------------------------------------
 size_t icn_head_workspace_floats(int M, int Cin) { return (M < 1 || Cin < 1) ? 0 : (size_t)icn::head_chunks(M) * 4 * (Cin + 4); }
 
 int icn_head_fwd(const float* x, const float* w, const float* bias, float* y, int M, int Cin, int Cout, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!x || !w || !bias || !y || M < 1) throw std::invalid_argument("icn_head_fwd: bad arguments");
         if (!icn::head_supported(Cin, Cout)) throw std::invalid_argument("icn_head_fwd: unsupported channel counts");
-        icn::launch_head_fwd(x, w, bias, y, M, Cin, Cout, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        icn::launch_head_fwd(x, w, bias, y, M, Cin, Cout, s);
+    });
 }
 
 int icn_head_bwd(const float* dy, const float* y, const float* x, const float* w, float* dx, float* dw, float* db, float* ws,
                  int M, int Cin, int Cout, void* stream) {
-    try {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
         if (!dy || !y || !x || !w || !dw || !db || !ws || M < 1) throw std::invalid_argument("icn_head_bwd: bad arguments");
         if (!icn::head_supported(Cin, Cout)) throw std::invalid_argument("icn_head_bwd: unsupported channel counts");
-        icn::launch_head_bwd(dy, y, x, w, dx, dw, db, ws, M, Cin, Cout, static_cast<hipStream_t>(stream));
-        ICN_HIP(hipGetLastError());
-        return 0;
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        icn::launch_head_bwd(dy, y, x, w, dx, dw, db, ws, M, Cin, Cout, s);
+    });
 }
 
 // ---- host-side introspection ----------------------------------------------------------------------------
 long icn_table_conv_fwd(int r_in, int stride, int corner_mode, int32_t* out, size_t cap) {
-    try {
+    return returns<long>([&] {
         std::vector<int32_t> v;
         icn::build_conv_fwd(r_in, stride, corner_mode, v);
-        if (out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(int32_t));
-        return (long)v.size();
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        return copy_out(out, cap, v);
+    });
 }
 
 long icn_table_wgrad7(int r_in, int stride, int corner_mode, int32_t* rows, size_t cap_rows, uint16_t* pos, size_t cap_pos, int* meta) {
-    try {
+    return returns<long>([&] {
         std::vector<int32_t> fwd;
         icn::build_conv_fwd(r_in, stride, corner_mode, fwd);
         const int P = (int)(fwd.size() / icn::NTAPS);
@@ -1745,56 +1615,44 @@ long icn_table_wgrad7(int r_in, int stride, int corner_mode, int32_t* rows, size
         icn::Wg7Table w7;
         if (!icn::build_wgrad7(h, P, wgrad7_union_rows(stride), w7)) {      // the very table make_conv_tables uploads
             if (meta) meta[0] = meta[1] = 0;
-            return 0;
+            return 0L;
         }
         if (meta) { meta[0] = w7.U; meta[1] = w7.npatch; }
-        if (rows) std::memcpy(rows, w7.urow.data(), std::min(cap_rows, w7.urow.size()) * sizeof(int32_t));
-        if (pos) std::memcpy(pos, w7.upos.data(), std::min(cap_pos, w7.upos.size()) * sizeof(uint16_t));
-        return (long)w7.urow.size();
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        copy_out(pos, cap_pos, w7.upos);
+        return copy_out(rows, cap_rows, w7.urow);
+    });
 }
 
 long icn_table_conv_bwd(int r_in, int stride, int corner_mode, int32_t* out, size_t cap, int* width) {
-    try {
+    return returns<long>([&] {
         std::vector<int32_t> v;
         const int E = icn::build_conv_bwd(r_in, stride, corner_mode, v);
         if (width) *width = E;
-        if (out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(int32_t));
-        return (long)v.size();
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        return copy_out(out, cap, v);
+    });
 }
 
 long icn_table_upsample(int r_in, int corner_mode, int transpose, int32_t* idx, float* coef, size_t cap, int* width) {
-    try {
+    return returns<long>([&] {
         icn::Ell f, b;
         icn::build_upsample(r_in, corner_mode, f, b);
         const icn::Ell& e = transpose ? b : f;
         if (width) *width = e.width;
-        if (idx) std::memcpy(idx, e.idx.data(), std::min(cap, e.idx.size()) * sizeof(int32_t));
-        if (coef) std::memcpy(coef, e.coef.data(), std::min(cap, e.coef.size()) * sizeof(float));
-        return (long)e.idx.size();
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        copy_out(coef, cap, e.coef);
+        return copy_out(idx, cap, e.idx);
+    });
 }
 
 long icn_table_upsample_pairs(int r_in, int32_t* out, size_t cap) {
-    try {
+    return returns<long>([&] {
         std::vector<int32_t> v;
         icn::build_upsample_pairs(r_in, v);
-        if (out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(int32_t));
-        return (long)v.size();
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        return copy_out(out, cap, v);
+    });
 }
 
 long icn_table_upconv(int r_in, int corner_mode, int32_t* ints, size_t cap_ints, float* floats, size_t cap_floats, int* meta) {
-    try {
+    return returns<long>([&] {
         icn::UpconvTable t;
         icn::build_upconv_fwd(r_in, corner_mode, t);
         std::vector<int32_t> iv;
@@ -1812,47 +1670,35 @@ long icn_table_upconv(int r_in, int corner_mode, int32_t* ints, size_t cap_ints,
             meta[0] = t.Pf; meta[1] = t.Pc; meta[2] = t.n_slots; meta[3] = t.E; meta[4] = t.nseg; meta[5] = icn::UPCONV_TAPS;
             meta[6] = (int)fv.size();
         }
-        if (ints) std::memcpy(ints, iv.data(), std::min(cap_ints, iv.size()) * sizeof(int32_t));
-        if (floats) std::memcpy(floats, fv.data(), std::min(cap_floats, fv.size()) * sizeof(float));
-        return (long)iv.size();
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        copy_out(floats, cap_floats, fv);
+        return copy_out(ints, cap_ints, iv);
+    });
 }
 
 long icn_table_upconv_bwd(int r_in, int corner_mode, int32_t* idx, float* coef, size_t cap, int* width) {
-    try {
+    return returns<long>([&] {
         icn::Ell e;
         icn::build_upconv_bwd(r_in, corner_mode, e);
         if (width) *width = e.width;
-        if (idx) std::memcpy(idx, e.idx.data(), std::min(cap, e.idx.size()) * sizeof(int32_t));
-        if (coef) std::memcpy(coef, e.coef.data(), std::min(cap, e.coef.size()) * sizeof(float));
-        return (long)e.idx.size();
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        copy_out(coef, cap, e.coef);
+        return copy_out(idx, cap, e.idx);
+    });
 }
 
 long icn_table_faces(int r, int32_t* out, size_t cap) {
-    try {
+    return returns<long>([&] {
         std::vector<int32_t> v;
         icn::build_faces(r, v);
-        if (out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(int32_t));
-        return (long)v.size();
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        return copy_out(out, cap, v);
+    });
 }
 
 long icn_table_vertex_stencils(int r, int32_t* out, size_t cap) {
-    try {
+    return returns<long>([&] {
         std::vector<int32_t> v;
         icn::build_vertex_stencils(r, v);
-        if (out) std::memcpy(out, v.data(), std::min(cap, v.size()) * sizeof(int32_t));
-        return (long)v.size();
-    } catch (const std::exception& e) {
-        return fail(e.what());
-    }
+        return copy_out(out, cap, v);
+    });
 }
 
 }  // extern "C"

@@ -16,7 +16,7 @@ import weakref
 import torch
 
 from . import _gradbuf, _lib
-from .ico_conv import (_nhwc, _stream, ico_conv_pair, ico_conv_pair_supported, ico_upconv_pair,
+from .ico_conv import (_nhwc, ico_conv_pair, ico_conv_pair_supported, ico_upconv_pair,
                        ico_upconv_pair_supported)
 
 _DISABLED = os.environ.get('ICN_NO_FUSED_BN', '') == '1'
@@ -99,30 +99,29 @@ class _BnReluFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, ga, ba, rm_a, rv_a, eps_a, mom_a, b, gb, bb, rm_b, rv_b, eps_b, mom_b):
-        L = _lib.lib()
+        L = _lib.api()
         ap = _nhwc(a)
         Bn, H, W, C = ap.shape
         M = Bn * H * W
         dual = b is not None
         bp = _nhwc(b) if dual else None
         dev = a.device
-        ws = torch.empty(L.icn_bn_workspace_floats(M, C), dtype=torch.float32, device=dev)
+        ws = _lib.workspace(L.icn_bn_workspace_floats(M, C), dev, torch.float32)
         stat_a = torch.empty(2 * C, dtype=torch.float32, device=dev)
         stat_b = torch.empty(2 * C, dtype=torch.float32, device=dev) if dual else None
         y = torch.empty_like(ap)
         with torch.cuda.device(dev):
-            st = _stream()
+            st = _lib.stream()
             if dual:        # both inputs' statistics in one pass
-                _lib.check(L.icn_bn_stats2(ap.data_ptr(), bp.data_ptr(), M, C, eps_a, mom_a, rm_a.data_ptr(), rv_a.data_ptr(),
-                                           stat_a.data_ptr(), eps_b, mom_b, rm_b.data_ptr(), rv_b.data_ptr(), stat_b.data_ptr(),
-                                           ws.data_ptr(), st), 'icn_bn_stats2')
+                L.icn_bn_stats2(ap.data_ptr(), bp.data_ptr(), M, C, eps_a, mom_a, rm_a.data_ptr(), rv_a.data_ptr(),
+                                stat_a.data_ptr(), eps_b, mom_b, rm_b.data_ptr(), rv_b.data_ptr(), stat_b.data_ptr(),
+                                ws.data_ptr(), st)
             else:
-                _lib.check(L.icn_bn_stats(ap.data_ptr(), M, C, eps_a, mom_a, rm_a.data_ptr(), rv_a.data_ptr(), stat_a.data_ptr(),
-                                          ws.data_ptr(), st), 'icn_bn_stats')
-            _lib.check(L.icn_bn_relu_fwd(ap.data_ptr(), bp.data_ptr() if dual else None, stat_a.data_ptr(),
-                                         stat_b.data_ptr() if dual else None, ga.data_ptr(), ba.data_ptr(),
-                                         gb.data_ptr() if dual else None, bb.data_ptr() if dual else None, y.data_ptr(), M, C,
-                                         st), 'icn_bn_relu_fwd')
+                L.icn_bn_stats(ap.data_ptr(), M, C, eps_a, mom_a, rm_a.data_ptr(), rv_a.data_ptr(), stat_a.data_ptr(),
+                               ws.data_ptr(), st)
+            L.icn_bn_relu_fwd(ap.data_ptr(), bp.data_ptr() if dual else None, stat_a.data_ptr(),
+                              stat_b.data_ptr() if dual else None, ga.data_ptr(), ba.data_ptr(),
+                              gb.data_ptr() if dual else None, bb.data_ptr() if dual else None, y.data_ptr(), M, C, st)
         ctx.save_for_backward(ap, bp, stat_a, stat_b, ga, ba, gb, bb)    # not y: the backward recomputes the ReLU mask
         ctx.dims = (M, C, dual)
         ctx.params = (ga, ba, gb, bb)                    # where the parameter gradients go (_gradbuf.lease)
@@ -131,7 +130,7 @@ class _BnReluFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        L = _lib.lib()
+        L = _lib.api()
         ap, bp, stat_a, stat_b, ga, ba, gb, bb = ctx.saved_tensors
         M, C, dual = ctx.dims
         gyp = _nhwc(gy)
@@ -139,7 +138,7 @@ class _BnReluFn(torch.autograd.Function):
         da = torch.empty_like(ap)
         db = torch.empty_like(bp) if dual else None
         sums = torch.empty(3 * C, dtype=torch.float32, device=dev)
-        ws = torch.empty(L.icn_bn_workspace_floats(M, C), dtype=torch.float32, device=dev)
+        ws = _lib.workspace(L.icn_bn_workspace_floats(M, C), dev, torch.float32)
         # the parameter gradients in tensors of their own (the kernel writes them beside `sums`): a view into a DDP bucket when
         # the trainer remembered one, else new
         pga, pba, pgb, pbb = ctx.params
@@ -147,12 +146,11 @@ class _BnReluFn(torch.autograd.Function):
         dgb = _gradbuf.lease(pgb, (C,), dev) if dual else None
         dbb = _gradbuf.lease(pbb, (C,), dev) if dual else None
         with torch.cuda.device(dev):
-            _lib.check(L.icn_bn_relu_bwd(gyp.data_ptr(), ap.data_ptr(), bp.data_ptr() if dual else None, stat_a.data_ptr(),
-                                         stat_b.data_ptr() if dual else None, ga.data_ptr(), ba.data_ptr(),
-                                         gb.data_ptr() if dual else None, bb.data_ptr() if dual else None, da.data_ptr(),
-                                         db.data_ptr() if dual else None, sums.data_ptr(), ws.data_ptr(), M, C, dba.data_ptr(),
-                                         dga.data_ptr(), dbb.data_ptr() if dual else None, dgb.data_ptr() if dual else None,
-                                         _stream()), 'icn_bn_relu_bwd')
+            L.icn_bn_relu_bwd(gyp.data_ptr(), ap.data_ptr(), bp.data_ptr() if dual else None, stat_a.data_ptr(),
+                              stat_b.data_ptr() if dual else None, ga.data_ptr(), ba.data_ptr(),
+                              gb.data_ptr() if dual else None, bb.data_ptr() if dual else None, da.data_ptr(),
+                              db.data_ptr() if dual else None, sums.data_ptr(), ws.data_ptr(), M, C, dba.data_ptr(),
+                              dga.data_ptr(), dbb.data_ptr() if dual else None, dgb.data_ptr() if dual else None, _lib.stream())
         out = [da.permute(0, 3, 1, 2), dga, dba, None, None, None, None]
         if dual:
             out += [db.permute(0, 3, 1, 2), dgb, dbb, None, None, None, None]
@@ -227,7 +225,7 @@ def _eval_stat(bn):
 
 
 def _bn_relu_eval(a, bn_a, b=None, bn_b=None):
-    L = _lib.lib()
+    L = _lib.api()
     ap = _nhwc(a.detach())
     Bn, H, W, C = ap.shape
     M = Bn * H * W
@@ -237,10 +235,10 @@ def _bn_relu_eval(a, bn_a, b=None, bn_b=None):
     stat_b = _eval_stat(bn_b) if dual else None
     y = torch.empty_like(ap)
     with torch.cuda.device(a.device):
-        _lib.check(L.icn_bn_relu_fwd(ap.data_ptr(), bp.data_ptr() if dual else None, stat_a.data_ptr(),
-                                     stat_b.data_ptr() if dual else None, bn_a.weight.data_ptr(), bn_a.bias.data_ptr(),
-                                     bn_b.weight.data_ptr() if dual else None, bn_b.bias.data_ptr() if dual else None,
-                                     y.data_ptr(), M, C, _stream()), 'icn_bn_relu_fwd')
+        L.icn_bn_relu_fwd(ap.data_ptr(), bp.data_ptr() if dual else None, stat_a.data_ptr(),
+                          stat_b.data_ptr() if dual else None, bn_a.weight.data_ptr(), bn_a.bias.data_ptr(),
+                          bn_b.weight.data_ptr() if dual else None, bn_b.bias.data_ptr() if dual else None,
+                          y.data_ptr(), M, C, _lib.stream())
     return y.permute(0, 3, 1, 2)
 
 
@@ -259,15 +257,14 @@ class _HeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        L = _lib.lib()
+        L = _lib.api()
         xp = _nhwc(x)
         Bn, H, W, Cin = xp.shape
         Cout, M = weight.shape[0], Bn * H * W
         w2 = weight.reshape(Cout, Cin).contiguous()
         y = torch.empty(Bn, H, W, Cout, dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(L.icn_head_fwd(xp.data_ptr(), w2.data_ptr(), bias.contiguous().data_ptr(), y.data_ptr(), M, Cin, Cout,
-                                      _stream()), 'icn_head_fwd')
+            L.icn_head_fwd(xp.data_ptr(), w2.data_ptr(), bias.contiguous().data_ptr(), y.data_ptr(), M, Cin, Cout, _lib.stream())
         ctx.save_for_backward(xp, w2, y)
         ctx.wshape, ctx.wstride = weight.shape, weight.stride()
         ctx.params = (weight, bias)
@@ -276,7 +273,7 @@ class _HeadFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        L = _lib.lib()
+        L = _lib.api()
         xp, w2, y = ctx.saved_tensors
         Bn, H, W, Cin = xp.shape
         Cout, M = w2.shape[0], Bn * H * W
@@ -287,11 +284,11 @@ class _HeadFn(torch.autograd.Function):
         # (Cout, Cin) row-major order -- so that DistributedDataParallel can alias it (gradient_as_bucket_view)
         dw = _gradbuf.lease(ctx.params[0], ctx.wshape, dev, stride=ctx.wstride)
         db = _gradbuf.lease(ctx.params[1], (Cout,), dev)
-        ws = torch.empty(L.icn_head_workspace_floats(M, Cin), dtype=torch.float32, device=dev)
+        ws = _lib.workspace(L.icn_head_workspace_floats(M, Cin), dev, torch.float32)
         with torch.cuda.device(dev):
-            _lib.check(L.icn_head_bwd(gyp.data_ptr(), y.data_ptr(), xp.data_ptr(), w2.data_ptr(),
-                                      dx.data_ptr() if dx is not None else None, dw.data_ptr(), db.data_ptr(), ws.data_ptr(), M,
-                                      Cin, Cout, _stream()), 'icn_head_bwd')
+            L.icn_head_bwd(gyp.data_ptr(), y.data_ptr(), xp.data_ptr(), w2.data_ptr(),
+                           dx.data_ptr() if dx is not None else None, dw.data_ptr(), db.data_ptr(), ws.data_ptr(), M,
+                           Cin, Cout, _lib.stream())
         return (dx.permute(0, 3, 1, 2) if dx is not None else None), dw, db
 
 
@@ -325,25 +322,23 @@ class _ReparamFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mu, logvar, eps):
-        L = _lib.lib()
+        L = _lib.api()
         m, lv, e = _nhwc(mu), _nhwc(logvar), _nhwc(eps)
         z = torch.empty_like(m)
         with torch.cuda.device(m.device):
-            _lib.check(L.icn_reparam_fwd(m.data_ptr(), lv.data_ptr(), e.data_ptr(), m.numel(), z.data_ptr(), _stream()),
-                       'icn_reparam_fwd')
+            L.icn_reparam_fwd(m.data_ptr(), lv.data_ptr(), e.data_ptr(), m.numel(), z.data_ptr(), _lib.stream())
         ctx.save_for_backward(lv, e)
         return z.permute(0, 3, 1, 2)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gz):
-        L = _lib.lib()
+        L = _lib.api()
         lv, e = ctx.saved_tensors
         g = _nhwc(gz)
         dm, dlv = torch.empty_like(g), torch.empty_like(g)
         with torch.cuda.device(g.device):
-            _lib.check(L.icn_reparam_bwd(g.data_ptr(), lv.data_ptr(), e.data_ptr(), g.numel(), dm.data_ptr(), dlv.data_ptr(),
-                                         _stream()), 'icn_reparam_bwd')
+            L.icn_reparam_bwd(g.data_ptr(), lv.data_ptr(), e.data_ptr(), g.numel(), dm.data_ptr(), dlv.data_ptr(), _lib.stream())
         return dm.permute(0, 3, 1, 2), dlv.permute(0, 3, 1, 2), None
 
 

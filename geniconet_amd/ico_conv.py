@@ -254,18 +254,10 @@ def _nhwc(x):
     return x.permute(0, 2, 3, 1).contiguous()
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _workspace(nbytes, device):
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
-
-
 class _IcoConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, r, stride, mode):
-        L = _lib.lib()
+        L = _lib.api()
         B, Cin = x.shape[0], x.shape[1]
         Cout = weight.shape[0]
         n_out = 2 ** r // stride
@@ -274,11 +266,10 @@ class _IcoConvFn(torch.autograd.Function):
         b = bias.contiguous() if bias is not None else None
         y = torch.empty(B, 5 * n_out, 2 * n_out, Cout, dtype=torch.float32, device=x.device)
         ws_bytes = L.icn_conv_workspace_bytes(_lib.OP_CONV_FWD, B, Cin, Cout, r, stride)
-        ws = _workspace(ws_bytes, x.device)
+        ws = _lib.workspace(ws_bytes, x.device)
         with torch.cuda.device(x.device):
-            rc = L.icn_conv_fwd(xp.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(),
-                                B, Cin, Cout, r, stride, mode, ws.data_ptr(), ws_bytes, _stream())
-        _lib.check(rc, 'icn_conv_fwd')
+            L.icn_conv_fwd(xp.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(),
+                           B, Cin, Cout, r, stride, mode, ws.data_ptr(), ws_bytes, _lib.stream())
         ctx.save_for_backward(xp, w)
         ctx.cfg = (B, Cin, Cout, r, stride, mode, bias is not None)
         ctx.params = (weight, bias)                      # where their gradients go (_gradbuf.lease)
@@ -287,7 +278,7 @@ class _IcoConvFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        L = _lib.lib()
+        L = _lib.api()
         xp, w = ctx.saved_tensors
         B, Cin, Cout, r, stride, mode, has_bias = ctx.cfg
         gyp = _nhwc(gy)
@@ -297,7 +288,7 @@ class _IcoConvFn(torch.autograd.Function):
                 dw = _gradbuf.lease(ctx.params[0], w.shape, w.device)
                 db = _gradbuf.lease(ctx.params[1], (Cout,), w.device) if has_bias else None
                 ws_bytes = L.icn_conv_workspace_bytes(_lib.OP_CONV_BWD_WEIGHT, B, Cin, Cout, r, stride)
-                ws = _workspace(ws_bytes, gyp.device)
+                ws = _lib.workspace(ws_bytes, gyp.device)
                 # (a convolution whose input needs no gradient -- the stem -- is the last thing in the pass: its weight gradient
                 #  stays on the current stream, which has nothing else left to do, instead of queueing behind the side stream's
                 #  backlog: +1.2 %, 4346-4370 against 4298-4314 meshes/s; keeping the last one or two OTHER weight gradients on
@@ -307,17 +298,15 @@ class _IcoConvFn(torch.autograd.Function):
                 # (Round 6: for a while this launch first joined the side stream -- the stem's weight gradient came out different from
                 #  run to run while the first residual block's bf16x3 pair gradient ran beside it.  The cause was in k_stem_wgrad's machine
                 #  code, not in the streams: v_pk_fma_f32 with a cross-dword op_sel, see csrc/Makefile and profiles/r06_stem_wgrad_race.txt.)
-                rc = L.icn_conv_bwd_weight(xp.data_ptr(), gyp.data_ptr(), dw.data_ptr(),
-                                           db.data_ptr() if db is not None else None, B, Cin, Cout, r, stride, mode,
-                                           ws.data_ptr(), ws_bytes, side.cuda_stream if side is not None else _stream())
-                _lib.check(rc, 'icn_conv_bwd_weight')
+                L.icn_conv_bwd_weight(xp.data_ptr(), gyp.data_ptr(), dw.data_ptr(),
+                                      db.data_ptr() if db is not None else None, B, Cin, Cout, r, stride, mode,
+                                      ws.data_ptr(), ws_bytes, side.cuda_stream if side is not None else _lib.stream())
             if ctx.needs_input_grad[0]:
                 dxp = torch.empty_like(xp)
                 ws_bytes = L.icn_conv_workspace_bytes(_lib.OP_CONV_BWD_DATA, B, Cin, Cout, r, stride)
-                ws = _workspace(ws_bytes, gyp.device)
-                rc = L.icn_conv_bwd_data(gyp.data_ptr(), w.data_ptr(), dxp.data_ptr(), B, Cin, Cout, r, stride, mode,
-                                         ws.data_ptr(), ws_bytes, _stream())
-                _lib.check(rc, 'icn_conv_bwd_data')
+                ws = _lib.workspace(ws_bytes, gyp.device)
+                L.icn_conv_bwd_data(gyp.data_ptr(), w.data_ptr(), dxp.data_ptr(), B, Cin, Cout, r, stride, mode,
+                                    ws.data_ptr(), ws_bytes, _lib.stream())
                 dx = dxp.permute(0, 3, 1, 2)
             _wgrad_done(gyp.device, side)
         return dx, dw, db, None, None, None
@@ -330,7 +319,7 @@ class _IcoConvPairFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w0, b0, w1, b1, r, stride, mode):
-        L = _lib.lib()
+        L = _lib.api()
         B, Cin = x.shape[0], x.shape[1]
         C0, C1 = w0.shape[0], w1.shape[0]
         n_out = 2 ** r // stride
@@ -341,12 +330,11 @@ class _IcoConvPairFn(torch.autograd.Function):
         y0 = torch.empty(B, 5 * n_out, 2 * n_out, C0, dtype=torch.float32, device=x.device)
         y1 = torch.empty(B, 5 * n_out, 2 * n_out, C1, dtype=torch.float32, device=x.device)
         ws_bytes = L.icn_conv_pair_workspace_bytes(_lib.OP_CONV_FWD, B, Cin, C0, C1, r, stride)
-        ws = _workspace(ws_bytes, x.device)
+        ws = _lib.workspace(ws_bytes, x.device)
         with torch.cuda.device(x.device):
-            rc = L.icn_conv_pair_fwd(xp.data_ptr(), w0c.data_ptr(), b0c.data_ptr() if b0c is not None else None,
-                                     w1c.data_ptr(), b1c.data_ptr() if b1c is not None else None, y0.data_ptr(),
-                                     y1.data_ptr(), B, Cin, C0, C1, r, stride, mode, ws.data_ptr(), ws_bytes, _stream())
-        _lib.check(rc, 'icn_conv_pair_fwd')
+            L.icn_conv_pair_fwd(xp.data_ptr(), w0c.data_ptr(), b0c.data_ptr() if b0c is not None else None,
+                                w1c.data_ptr(), b1c.data_ptr() if b1c is not None else None, y0.data_ptr(),
+                                y1.data_ptr(), B, Cin, C0, C1, r, stride, mode, ws.data_ptr(), ws_bytes, _lib.stream())
         ctx.save_for_backward(xp, w0c, w1c)
         ctx.cfg = (B, Cin, C0, C1, r, stride, mode, b0 is not None)
         ctx.params = (w0, b0, w1, b1)
@@ -355,7 +343,7 @@ class _IcoConvPairFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy0, gy1):
-        L = _lib.lib()
+        L = _lib.api()
         xp, w0, w1 = ctx.saved_tensors
         B, Cin, C0, C1, r, stride, mode, has_bias = ctx.cfg
         g0, g1 = _nhwc(gy0), _nhwc(gy1)
@@ -369,20 +357,18 @@ class _IcoConvPairFn(torch.autograd.Function):
                     db0 = _gradbuf.lease(pb0, (C0,), w0.device)
                     db1 = _gradbuf.lease(pb1, (C1,), w1.device)
                 ws_bytes = L.icn_conv_pair_workspace_bytes(_lib.OP_CONV_BWD_WEIGHT, B, Cin, C0, C1, r, stride)
-                ws = _workspace(ws_bytes, g0.device)
+                ws = _lib.workspace(ws_bytes, g0.device)
                 side = _wgrad_stream(g0.device, [(pw0, dw0), (pb0, db0), (pw1, dw1), (pb1, db1)], xp, g0, g1, ws)
-                rc = L.icn_conv_pair_bwd_weight(xp.data_ptr(), g0.data_ptr(), g1.data_ptr(), dw0.data_ptr(),
-                                                db0.data_ptr() if db0 is not None else None, dw1.data_ptr(),
-                                                db1.data_ptr() if db1 is not None else None, B, Cin, C0, C1, r, stride, mode,
-                                                ws.data_ptr(), ws_bytes, side.cuda_stream if side is not None else _stream())
-                _lib.check(rc, 'icn_conv_pair_bwd_weight')
+                L.icn_conv_pair_bwd_weight(xp.data_ptr(), g0.data_ptr(), g1.data_ptr(), dw0.data_ptr(),
+                                           db0.data_ptr() if db0 is not None else None, dw1.data_ptr(),
+                                           db1.data_ptr() if db1 is not None else None, B, Cin, C0, C1, r, stride, mode,
+                                           ws.data_ptr(), ws_bytes, side.cuda_stream if side is not None else _lib.stream())
             if need[0]:
                 dxp = torch.empty_like(xp)
                 ws_bytes = L.icn_conv_pair_workspace_bytes(_lib.OP_CONV_BWD_DATA, B, Cin, C0, C1, r, stride)
-                ws = _workspace(ws_bytes, g0.device)
-                rc = L.icn_conv_pair_bwd_data(g0.data_ptr(), g1.data_ptr(), w0.data_ptr(), w1.data_ptr(), dxp.data_ptr(),
-                                              B, Cin, C0, C1, r, stride, mode, ws.data_ptr(), ws_bytes, _stream())
-                _lib.check(rc, 'icn_conv_pair_bwd_data')
+                ws = _lib.workspace(ws_bytes, g0.device)
+                L.icn_conv_pair_bwd_data(g0.data_ptr(), g1.data_ptr(), w0.data_ptr(), w1.data_ptr(), dxp.data_ptr(),
+                                         B, Cin, C0, C1, r, stride, mode, ws.data_ptr(), ws_bytes, _lib.stream())
                 dx = dxp.permute(0, 3, 1, 2)
             _wgrad_done(g0.device, side)
         return dx, dw0, db0, dw1, db1, None, None, None
@@ -391,28 +377,26 @@ class _IcoConvPairFn(torch.autograd.Function):
 class _IcoUpsampleFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, r, mode):
-        L = _lib.lib()
+        L = _lib.api()
         B, C = x.shape[0], x.shape[1]
         n = 2 ** r
         xp = _nhwc(x)
         y = torch.empty(B, 10 * n, 4 * n, C, dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            rc = L.icn_upsample_fwd(xp.data_ptr(), y.data_ptr(), B, C, r, mode, _stream())
-        _lib.check(rc, 'icn_upsample_fwd')
+            L.icn_upsample_fwd(xp.data_ptr(), y.data_ptr(), B, C, r, mode, _lib.stream())
         ctx.cfg = (B, C, r, mode)
         return y.permute(0, 3, 1, 2)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        L = _lib.lib()
+        L = _lib.api()
         B, C, r, mode = ctx.cfg
         n = 2 ** r
         gyp = _nhwc(gy)
         dx = torch.empty(B, 5 * n, 2 * n, C, dtype=torch.float32, device=gy.device)
         with torch.cuda.device(gy.device):
-            rc = L.icn_upsample_bwd(gyp.data_ptr(), dx.data_ptr(), B, C, r, mode, _stream())
-        _lib.check(rc, 'icn_upsample_bwd')
+            L.icn_upsample_bwd(gyp.data_ptr(), dx.data_ptr(), B, C, r, mode, _lib.stream())
         return dx.permute(0, 3, 1, 2), None, None
 
 
@@ -427,7 +411,7 @@ class _IcoUpConvPairFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w0, b0, w1, b1, r, mode):
-        L = _lib.lib()
+        L = _lib.api()
         B, Cin = x.shape[0], x.shape[1]
         C0, C1 = w0.shape[0], w1.shape[0]
         nf = 2 ** (r + 1)
@@ -438,12 +422,11 @@ class _IcoUpConvPairFn(torch.autograd.Function):
         y0 = torch.empty(B, 5 * nf, 2 * nf, C0, dtype=torch.float32, device=x.device)
         y1 = torch.empty(B, 5 * nf, 2 * nf, C1, dtype=torch.float32, device=x.device)
         ws_bytes = L.icn_upconv_workspace_bytes(B, Cin, C0, C1, r)
-        ws = _workspace(ws_bytes, x.device)
+        ws = _lib.workspace(ws_bytes, x.device)
         with torch.cuda.device(x.device):
-            rc = L.icn_upconv_fwd(xp.data_ptr(), w0c.data_ptr(), b0c.data_ptr() if b0c is not None else None, w1c.data_ptr(),
-                                  b1c.data_ptr() if b1c is not None else None, y0.data_ptr(), y1.data_ptr(), B, Cin, C0, C1, r,
-                                  mode, ws.data_ptr(), ws_bytes, _stream())
-        _lib.check(rc, 'icn_upconv_fwd')
+            L.icn_upconv_fwd(xp.data_ptr(), w0c.data_ptr(), b0c.data_ptr() if b0c is not None else None, w1c.data_ptr(),
+                             b1c.data_ptr() if b1c is not None else None, y0.data_ptr(), y1.data_ptr(), B, Cin, C0, C1, r,
+                             mode, ws.data_ptr(), ws_bytes, _lib.stream())
         ctx.save_for_backward(xp, w0c, w1c)
         ctx.cfg = (B, Cin, C0, C1, r, mode, b0 is not None)
         ctx.params = (w0, b0, w1, b1)
@@ -452,7 +435,7 @@ class _IcoUpConvPairFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy0, gy1):
-        L = _lib.lib()
+        L = _lib.api()
         xp, w0, w1 = ctx.saved_tensors
         B, Cin, C0, C1, r, mode, has_bias = ctx.cfg
         rf, n, nf = r + 1, 2 ** r, 2 ** (r + 1)
@@ -471,43 +454,43 @@ class _IcoUpConvPairFn(torch.autograd.Function):
                     db0 = _gradbuf.lease(pb0, (C0,), dev)
                     db1 = _gradbuf.lease(pb1, (C1,), dev)
             ws_bytes = L.icn_upconv_bwd_workspace_bytes(B, Cin, C0, C1, r)
-            ws = _workspace(ws_bytes, dev)
+            ws = _lib.workspace(ws_bytes, dev)
             ptr = lambda t: t.data_ptr() if t is not None else None
             with torch.cuda.device(dev):
                 # the weight gradients (after the aggregate pass, which stays on the current stream) on the side stream
                 side = (_wgrad_stream(dev, [(pw0, dw0), (pb0, db0), (pw1, dw1), (pb1, db1)], xp, ws)
                         if want_w else None)
-                _lib.check(L.icn_upconv_bwd_streams(xp.data_ptr(), g0.data_ptr(), g1.data_ptr(), w0.data_ptr(), w1.data_ptr(),
-                                                    ptr(dxp), ptr(dw0), ptr(db0), ptr(dw1), ptr(db1), B, Cin, C0, C1, r, mode,
-                                                    ws.data_ptr(), ws_bytes, _stream(),
-                                                    side.cuda_stream if side is not None else None), 'icn_upconv_bwd_streams')
+                L.icn_upconv_bwd_streams(xp.data_ptr(), g0.data_ptr(), g1.data_ptr(), w0.data_ptr(), w1.data_ptr(),
+                                         ptr(dxp), ptr(dw0), ptr(db0), ptr(dw1), ptr(db1), B, Cin, C0, C1, r, mode,
+                                         ws.data_ptr(), ws_bytes, _lib.stream(),
+                                         side.cuda_stream if side is not None else None)
                 _wgrad_done(dev, side)
             return (dxp.permute(0, 3, 1, 2) if dxp is not None else None), dw0, db0, dw1, db1, None, None
         with torch.cuda.device(dev):
-            st = _stream()
+            st = _lib.stream()
             if need[0]:
                 dup = torch.empty(B, 5 * nf, 2 * nf, Cin, dtype=torch.float32, device=dev)
                 ws_bytes = L.icn_conv_pair_workspace_bytes(_lib.OP_CONV_BWD_DATA, B, Cin, C0, C1, rf, 1)
-                ws = _workspace(ws_bytes, dev)
-                _lib.check(L.icn_conv_pair_bwd_data(g0.data_ptr(), g1.data_ptr(), w0.data_ptr(), w1.data_ptr(), dup.data_ptr(), B,
-                                                    Cin, C0, C1, rf, 1, mode, ws.data_ptr(), ws_bytes, st), 'icn_conv_pair_bwd_data')
+                ws = _lib.workspace(ws_bytes, dev)
+                L.icn_conv_pair_bwd_data(g0.data_ptr(), g1.data_ptr(), w0.data_ptr(), w1.data_ptr(), dup.data_ptr(), B,
+                                         Cin, C0, C1, rf, 1, mode, ws.data_ptr(), ws_bytes, st)
                 dxp = torch.empty(B, 5 * n, 2 * n, Cin, dtype=torch.float32, device=dev)
-                _lib.check(L.icn_upsample_bwd(dup.data_ptr(), dxp.data_ptr(), B, Cin, r, mode, st), 'icn_upsample_bwd')
+                L.icn_upsample_bwd(dup.data_ptr(), dxp.data_ptr(), B, Cin, r, mode, st)
                 del dup
                 dx = dxp.permute(0, 3, 1, 2)
             if want_w:
                 up = torch.empty(B, 5 * nf, 2 * nf, Cin, dtype=torch.float32, device=dev)
-                _lib.check(L.icn_upsample_fwd(xp.data_ptr(), up.data_ptr(), B, Cin, r, mode, st), 'icn_upsample_fwd')
+                L.icn_upsample_fwd(xp.data_ptr(), up.data_ptr(), B, Cin, r, mode, st)
                 dw0, dw1 = torch.empty_like(w0), torch.empty_like(w1)
                 if has_bias:
                     db0 = torch.empty(C0, dtype=torch.float32, device=dev)
                     db1 = torch.empty(C1, dtype=torch.float32, device=dev)
                 ws_bytes = L.icn_conv_pair_workspace_bytes(_lib.OP_CONV_BWD_WEIGHT, B, Cin, C0, C1, rf, 1)
-                ws = _workspace(ws_bytes, dev)
-                _lib.check(L.icn_conv_pair_bwd_weight(up.data_ptr(), g0.data_ptr(), g1.data_ptr(), dw0.data_ptr(),
-                                                      db0.data_ptr() if db0 is not None else None, dw1.data_ptr(),
-                                                      db1.data_ptr() if db1 is not None else None, B, Cin, C0, C1, rf, 1, mode,
-                                                      ws.data_ptr(), ws_bytes, st), 'icn_conv_pair_bwd_weight')
+                ws = _lib.workspace(ws_bytes, dev)
+                L.icn_conv_pair_bwd_weight(up.data_ptr(), g0.data_ptr(), g1.data_ptr(), dw0.data_ptr(),
+                                           db0.data_ptr() if db0 is not None else None, dw1.data_ptr(),
+                                           db1.data_ptr() if db1 is not None else None, B, Cin, C0, C1, rf, 1, mode,
+                                           ws.data_ptr(), ws_bytes, st)
         return dx, dw0, db0, dw1, db1, None, None
 
 
@@ -516,7 +499,7 @@ def ico_upconv_pair_supported(x, weight0, weight1, subdivisions):
     backward kernels at the fine level; `subdivisions` is the level of x."""
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and weight0.dim() == 3 and weight1.dim() == 3):
         return False
-    L = _lib.lib()
+    L = _lib.api()
     B, Cin, C0, C1 = x.shape[0], x.shape[1], weight0.shape[0], weight1.shape[0]
     return bool(L.icn_upconv_supported(B, Cin, C0, C1, subdivisions)
                 and L.icn_conv_pair_supported(B, Cin, C0, C1, subdivisions + 1, 1))
@@ -554,7 +537,7 @@ def ico_conv_pair_supported(x, weight0, weight1, subdivisions, stride=1):
     """True when two convolutions of x with these weights can take the one-launch-per-pass pair path."""
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and weight0.dim() == 3 and weight1.dim() == 3):
         return False
-    return bool(_lib.lib().icn_conv_pair_supported(x.shape[0], x.shape[1], weight0.shape[0], weight1.shape[0],
+    return bool(_lib.api().icn_conv_pair_supported(x.shape[0], x.shape[1], weight0.shape[0], weight1.shape[0],
                                                     subdivisions, stride))
 
 

@@ -46,16 +46,15 @@ class _P2PLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, inputs, target, r, f_pos, f_nor, f_lap, lap_mode=0):
-        L = _lib.lib()
+        L = _lib.api()
         B = inputs.shape[0]
         grid = inputs.permute(0, 2, 3, 1).contiguous()            # (B, 5n, 2n, 3) = (B, P, 3); free for channels_last
         tgt = target.contiguous()
         terms = torch.empty(4, dtype=torch.float32, device=inputs.device)
-        ws = torch.empty(max(L.icn_p2p_loss_workspace_floats(B, r), 1), dtype=torch.float32, device=inputs.device)
+        ws = _lib.workspace(L.icn_p2p_loss_workspace_floats(B, r), inputs.device, torch.float32)
         with torch.cuda.device(inputs.device):
-            rc = L.icn_p2p_loss_fwd(grid.data_ptr(), tgt.data_ptr(), B, r, f_pos, f_nor, f_lap, lap_mode, terms.data_ptr(),
-                                    ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, 'icn_p2p_loss_fwd')
+            L.icn_p2p_loss_fwd(grid.data_ptr(), tgt.data_ptr(), B, r, f_pos, f_nor, f_lap, lap_mode, terms.data_ptr(),
+                               ws.data_ptr(), _lib.stream())
         ctx.save_for_backward(grid, tgt)
         ctx.cfg = (B, r, f_pos, f_nor, f_lap, lap_mode)
         total = terms[3].clone()
@@ -66,18 +65,16 @@ class _P2PLossFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gtotal, _gterms):
         B, r, f_pos, f_nor, f_lap, lap_mode = ctx.cfg
-        L = _lib.lib()
+        L = _lib.api()
         grid, tgt = ctx.saved_tensors
         dgrid = torch.empty_like(grid)
         up = gtotal.contiguous().to(torch.float32)
         ws = None
         if f_nor != 0 or f_lap != 0:
-            ws = torch.empty(L.icn_p2p_loss_bwd_workspace_floats(B, r), dtype=torch.float32, device=grid.device)
+            ws = _lib.workspace(L.icn_p2p_loss_bwd_workspace_floats(B, r), grid.device, torch.float32)
         with torch.cuda.device(grid.device):
-            rc = L.icn_p2p_loss_bwd(grid.data_ptr(), tgt.data_ptr(), up.data_ptr(), B, r, f_pos, f_nor, f_lap, lap_mode,
-                                    dgrid.data_ptr(), ws.data_ptr() if ws is not None else None,
-                                    torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, 'icn_p2p_loss_bwd')
+            L.icn_p2p_loss_bwd(grid.data_ptr(), tgt.data_ptr(), up.data_ptr(), B, r, f_pos, f_nor, f_lap, lap_mode,
+                               dgrid.data_ptr(), ws.data_ptr() if ws is not None else None, _lib.stream())
         return dgrid.permute(0, 3, 1, 2), None, None, None, None, None, None
 
 
@@ -87,15 +84,14 @@ class _KLDFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mu, logvar):
-        L = _lib.lib()
+        L = _lib.api()
         # elementwise + a full sum: any common element order will do; (B, H, W, C) storage is free for channels_last
         m, lv = (t.permute(0, 2, 3, 1).contiguous() if t.dim() == 4 else t.contiguous() for t in (mu, logvar))
         n = m.numel()
         out = torch.empty(1, dtype=torch.float32, device=m.device)
-        ws = torch.empty(max(L.icn_kld_workspace_floats(n), 1), dtype=torch.float32, device=m.device)
+        ws = _lib.workspace(L.icn_kld_workspace_floats(n), m.device, torch.float32)
         with torch.cuda.device(m.device):
-            rc = L.icn_kld_fwd(m.data_ptr(), lv.data_ptr(), n, out.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, 'icn_kld_fwd')
+            L.icn_kld_fwd(m.data_ptr(), lv.data_ptr(), n, out.data_ptr(), ws.data_ptr(), _lib.stream())
         ctx.save_for_backward(m, lv)
         ctx.dim4 = mu.dim() == 4
         return out[0]
@@ -103,14 +99,12 @@ class _KLDFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        L = _lib.lib()
+        L = _lib.api()
         m, lv = ctx.saved_tensors
         dm, dlv = torch.empty_like(m), torch.empty_like(lv)
         up = g.contiguous().to(torch.float32)
         with torch.cuda.device(m.device):
-            rc = L.icn_kld_bwd(m.data_ptr(), lv.data_ptr(), up.data_ptr(), m.numel(), dm.data_ptr(), dlv.data_ptr(),
-                               torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, 'icn_kld_bwd')
+            L.icn_kld_bwd(m.data_ptr(), lv.data_ptr(), up.data_ptr(), m.numel(), dm.data_ptr(), dlv.data_ptr(), _lib.stream())
         if ctx.dim4:
             return dm.permute(0, 3, 1, 2), dlv.permute(0, 3, 1, 2)
         return dm, dlv
@@ -267,15 +261,15 @@ class _MeshRegFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, inputs, r, f_edge, f_ncons, f_smooth, edge_length):
-        L = _lib.lib()
+        L = _lib.api()
         B = inputs.shape[0]
         grid = inputs.permute(0, 2, 3, 1).contiguous()            # (B, P, 3); free for channels_last
         terms = torch.empty(4, dtype=torch.float32, device=inputs.device)
-        ws = torch.empty(max(L.icn_mesh_reg_workspace_floats(B, r), 1), dtype=torch.float32, device=inputs.device)
+        ws = _lib.workspace(L.icn_mesh_reg_workspace_floats(B, r), inputs.device, torch.float32)
         with torch.cuda.device(inputs.device):
-            rc = L.icn_mesh_reg_fwd(grid.data_ptr(), B, r, f_edge, f_ncons, f_smooth, edge_length, terms.data_ptr(), ws.data_ptr(),
-                                    torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, 'icn_mesh_reg_fwd')
+            L.icn_mesh_reg_fwd(grid.data_ptr(), B, r, f_edge, f_ncons, f_smooth, edge_length, terms.data_ptr(), ws.data_ptr(),
+                               _lib.stream())
+
         ctx.save_for_backward(grid)
         ctx.cfg = (B, r, f_edge, f_ncons, f_smooth, edge_length)
         total = terms[3].clone()
@@ -286,17 +280,16 @@ class _MeshRegFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gtotal, _gterms):
         B, r, f_edge, f_ncons, f_smooth, edge_length = ctx.cfg
-        L = _lib.lib()
+        L = _lib.api()
         grid, = ctx.saved_tensors
         dgrid = torch.empty_like(grid)
         up = gtotal.contiguous().to(torch.float32)
         ws = None
         if f_smooth != 0:
-            ws = torch.empty(L.icn_mesh_reg_bwd_workspace_floats(B, r), dtype=torch.float32, device=grid.device)
+            ws = _lib.workspace(L.icn_mesh_reg_bwd_workspace_floats(B, r), grid.device, torch.float32)
         with torch.cuda.device(grid.device):
-            rc = L.icn_mesh_reg_bwd(grid.data_ptr(), up.data_ptr(), B, r, f_edge, f_ncons, f_smooth, edge_length, dgrid.data_ptr(),
-                                    ws.data_ptr() if ws is not None else None, torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, 'icn_mesh_reg_bwd')
+            L.icn_mesh_reg_bwd(grid.data_ptr(), up.data_ptr(), B, r, f_edge, f_ncons, f_smooth, edge_length, dgrid.data_ptr(),
+                               ws.data_ptr() if ws is not None else None, _lib.stream())
         return dgrid.permute(0, 3, 1, 2), None, None, None, None, None
 
 

@@ -141,7 +141,7 @@ def _check_search(search):
 def _hip_point_to_mesh(pts, vts, f32, search='brute'):
     """icn_point_to_mesh (search 'brute') or icn_point_to_mesh_grid ('grid') on contiguous fp32 ROCm tensors and int32 faces
     -> (dist, face int32, kind)."""
-    L = _lib.lib()
+    L = _lib.api()
     B, P, _ = pts.shape
     V, F = vts.shape[1], f32.shape[0]
     dist = torch.empty(B, P, dtype=torch.float32, device=pts.device)
@@ -153,16 +153,13 @@ def _hip_point_to_mesh(pts, vts, f32, search='brute'):
             if search == 'grid':
                 if ws is None:
                     ws_bytes = L.icn_point_to_mesh_grid_workspace_bytes(min(B, _MAX_GRID_Y), P, V, F)
-                    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pts.device)
-                rc = L.icn_point_to_mesh_grid(pts[b0:].data_ptr(), vts[b0:].data_ptr(), f32.data_ptr(), nb, P, V, F,
-                                              dist[b0:].data_ptr(), face[b0:].data_ptr(), kind[b0:].data_ptr(), ws.data_ptr(),
-                                              ws_bytes, torch.cuda.current_stream().cuda_stream)
-                _lib.check(rc, 'icn_point_to_mesh_grid')
+                    ws = _lib.workspace(ws_bytes, pts.device)
+                L.icn_point_to_mesh_grid(pts[b0:].data_ptr(), vts[b0:].data_ptr(), f32.data_ptr(), nb, P, V, F,
+                                         dist[b0:].data_ptr(), face[b0:].data_ptr(), kind[b0:].data_ptr(), ws.data_ptr(),
+                                         ws_bytes, _lib.stream())
                 continue
-            rc = L.icn_point_to_mesh(pts[b0:].data_ptr(), vts[b0:].data_ptr(), f32.data_ptr(), nb, P, V, F,
-                                     dist[b0:].data_ptr(), face[b0:].data_ptr(), kind[b0:].data_ptr(),
-                                     torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, 'icn_point_to_mesh')
+            L.icn_point_to_mesh(pts[b0:].data_ptr(), vts[b0:].data_ptr(), f32.data_ptr(), nb, P, V, F,
+                                dist[b0:].data_ptr(), face[b0:].data_ptr(), kind[b0:].data_ptr(), _lib.stream())
     return dist, face, kind
 
 
@@ -184,23 +181,21 @@ class _PointToMeshFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, ddist, _gface, _gkind):
-        L = _lib.lib()
+        L = _lib.api()
         pts, vts, f32, face, kind = ctx.saved_tensors
         (B, P, _), V, F = pts.shape, vts.shape[1], f32.shape[0]
         up = ddist.contiguous().to(torch.float32)
         dpts = torch.empty_like(pts) if ctx.needs_input_grad[0] else None
         dvts = torch.empty_like(vts) if ctx.needs_input_grad[1] else None
         ws_bytes = L.icn_point_to_mesh_bwd_workspace_bytes(min(B, _MAX_GRID_Y), P, V, F) if dvts is not None else 0
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pts.device) if ws_bytes else None
+        ws = _lib.workspace(ws_bytes, pts.device) if ws_bytes else None
         with torch.cuda.device(pts.device):
             for b0, nb in _batch_slices(B):
-                rc = L.icn_point_to_mesh_bwd(pts[b0:].data_ptr(), vts[b0:].data_ptr(), f32.data_ptr(), face[b0:].data_ptr(),
-                                             kind[b0:].data_ptr(), up[b0:].data_ptr(), nb, P, V, F,
-                                             dpts[b0:].data_ptr() if dpts is not None else None,
-                                             dvts[b0:].data_ptr() if dvts is not None else None,
-                                             ws.data_ptr() if ws is not None else None, ws_bytes,
-                                             torch.cuda.current_stream().cuda_stream)
-                _lib.check(rc, 'icn_point_to_mesh_bwd')
+                L.icn_point_to_mesh_bwd(pts[b0:].data_ptr(), vts[b0:].data_ptr(), f32.data_ptr(), face[b0:].data_ptr(),
+                                        kind[b0:].data_ptr(), up[b0:].data_ptr(), nb, P, V, F,
+                                        dpts[b0:].data_ptr() if dpts is not None else None,
+                                        dvts[b0:].data_ptr() if dvts is not None else None,
+                                        ws.data_ptr() if ws is not None else None, ws_bytes, _lib.stream())
         return dpts, dvts, None, None
 
 

@@ -51,7 +51,7 @@ class Adam(torch.optim.Adam):
         if groups is None:
             super().step()                    # the closure has run: not passed on
             return loss
-        L = _lib.lib()
+        L = _lib.api()
         for group, ps in groups:
             if not ps:
                 continue
@@ -82,9 +82,8 @@ class Adam(torch.optim.Adam):
                 ma = vp(*[self.state[ps[i]]['exp_avg'].data_ptr() for i in idx])
                 va = vp(*[self.state[ps[i]]['exp_avg_sq'].data_ptr() for i in idx])
                 with torch.cuda.device(dev):
-                    rc = L.icn_adam_step(n, pa, ga, ma, va, numel, ss, bc, float(beta1), float(beta2), float(group['eps']),
-                                         float(group['weight_decay']), torch.cuda.current_stream(dev).cuda_stream)
-                _lib.check(rc, 'icn_adam_step')
+                    L.icn_adam_step(n, pa, ga, ma, va, numel, ss, bc, float(beta1), float(beta2), float(group['eps']),
+                                    float(group['weight_decay']), _lib.stream())
         return loss
 
     # ---- the step as part of a HIP graph (Trainer, ICN_GRAPH=1) ---------------------------------------------------------------
@@ -120,10 +119,8 @@ class Adam(torch.optim.Adam):
         va = vp(*[self.state[p]['exp_avg_sq'].data_ptr() for p in ps])
         dev = ps[0].device
         with torch.cuda.device(dev):
-            rc = _lib.lib().icn_adam_step_dev(n, pa, ga, ma, va, numel, scalars_dev.data_ptr(), float(beta1), float(beta2),
-                                              float(group['eps']), float(group['weight_decay']),
-                                              torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(rc, 'icn_adam_step_dev')
+            _lib.api().icn_adam_step_dev(n, pa, ga, ma, va, numel, scalars_dev.data_ptr(), float(beta1), float(beta2),
+                                         float(group['eps']), float(group['weight_decay']), _lib.stream())
         self._captured = [self.state[p]['step'] for p in ps]
 
     def advance_host(self):

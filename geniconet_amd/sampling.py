@@ -56,34 +56,31 @@ def _torch_sample(vertices, faces, u):
 
 def _hip_sample(vts, f32, u):
     """icn_mesh_sample_fwd on contiguous fp32 ROCm tensors and int32 faces -> (points, face int32, weights)."""
-    L = _lib.lib()
+    L = _lib.api()
     (B, V, _), S, F = vts.shape, u.shape[1], f32.shape[0]
     points = torch.empty(B, S, 3, dtype=torch.float32, device=vts.device)
     face = torch.empty(B, S, dtype=torch.int32, device=vts.device)
     weights = torch.empty(B, S, 3, dtype=torch.float32, device=vts.device)
     ws_bytes = L.icn_mesh_sample_workspace_bytes(min(B, metrics._MAX_GRID_Y), S, V, F)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=vts.device)
+    ws = _lib.workspace(ws_bytes, vts.device)
     with torch.cuda.device(vts.device):
         for b0, nb in metrics._batch_slices(B):
-            rc = L.icn_mesh_sample_fwd(vts[b0:].data_ptr(), f32.data_ptr(), u[b0:].data_ptr(), nb, S, V, F, points[b0:].data_ptr(),
-                                       face[b0:].data_ptr(), weights[b0:].data_ptr(), ws.data_ptr(), ws_bytes,
-                                       torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, 'icn_mesh_sample_fwd')
+            L.icn_mesh_sample_fwd(vts[b0:].data_ptr(), f32.data_ptr(), u[b0:].data_ptr(), nb, S, V, F, points[b0:].data_ptr(),
+                                  face[b0:].data_ptr(), weights[b0:].data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream())
     return points, face, weights
 
 
 def _hip_sample_bwd(f32, face, weights, dpoints, V):
     """icn_mesh_sample_bwd -> dvertices (B, V, 3); face int32 (B, S), weights / dpoints contiguous fp32 (B, S, 3)."""
-    L = _lib.lib()
+    L = _lib.api()
     (B, S), F = face.shape, f32.shape[0]
     dvts = torch.empty(B, V, 3, dtype=torch.float32, device=face.device)
     ws_bytes = L.icn_mesh_sample_bwd_workspace_bytes(min(B, metrics._MAX_GRID_Y), S, V, F)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=face.device)
+    ws = _lib.workspace(ws_bytes, face.device)
     with torch.cuda.device(face.device):
         for b0, nb in metrics._batch_slices(B):
-            rc = L.icn_mesh_sample_bwd(f32.data_ptr(), face[b0:].data_ptr(), weights[b0:].data_ptr(), dpoints[b0:].data_ptr(), nb, S, V,
-                                       F, dvts[b0:].data_ptr(), ws.data_ptr(), ws_bytes, torch.cuda.current_stream().cuda_stream)
-            _lib.check(rc, 'icn_mesh_sample_bwd')
+            L.icn_mesh_sample_bwd(f32.data_ptr(), face[b0:].data_ptr(), weights[b0:].data_ptr(), dpoints[b0:].data_ptr(), nb, S, V,
+                                  F, dvts[b0:].data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream())
     return dvts
 
 

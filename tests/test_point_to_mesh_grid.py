@@ -51,9 +51,9 @@ def test_grid_symbols_are_exported_bound_and_abi_is_9():
     assert _lib.ABI_VERSION == 9 and _lib.lib().icn_abi_version() == 9
     header = open(os.path.join(ROOT, 'include', 'icn.h')).read()
     assert '#define ICN_ABI_VERSION 9' in header
-    res, args = _lib.SIGNATURES['icn_point_to_mesh_grid']
+    res, args = _lib.SIGNATURES['icn_point_to_mesh_grid'][:2]
     assert res is ctypes.c_int and len(args) == 13 and args[-2] is ctypes.c_size_t
-    res, args = _lib.SIGNATURES['icn_point_to_mesh_grid_workspace_bytes']
+    res, args = _lib.SIGNATURES['icn_point_to_mesh_grid_workspace_bytes'][:2]
     assert res is ctypes.c_size_t and args == [ctypes.c_int] * 4
 
 

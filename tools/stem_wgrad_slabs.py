@@ -23,9 +23,10 @@ saveA = torch.zeros(stem_bytes, dtype=torch.uint8, device='cuda')
 saveDy = torch.zeros(rows * 64, dtype=torch.float32, device='cuda')
 state = {'bypass': True, 'calls': 0, 'pending': False}
 
+checked = _lib.api()
 class Proxy:
     def __getattr__(self, name):
-        f = getattr(L, name)
+        f = getattr(checked, name)
         if name != 'icn_conv_bwd_weight':
             return f
         def wrapped(xp, dy, dw, db, Bb, Cin, Cout, r, stride, mode, ws, ws_bytes, stream):
@@ -39,7 +40,7 @@ class Proxy:
             return rc
         return wrapped
 proxy = Proxy()
-_lib.lib = lambda: proxy
+_lib.api = lambda: proxy                        # (the package's own calls go through the checked view)
 real_ws_stream = ico._wgrad_stream
 def ws_wrap(dev, dests, *tensors, allow=True):
     side = real_ws_stream(dev, dests, *tensors, allow=allow)
