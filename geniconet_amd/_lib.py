@@ -104,6 +104,14 @@ SIGNATURES = {
     'icn_table_upconv': (ctypes.c_long, [ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_size_t, _f32p, ctypes.c_size_t, _intp], COUNT),
 }
 
+# entry points added since the icn.h freeze at ABI 9: include/icn_ext.h one to one (checked by tests/test_abi_ext.py), same
+# conventions, same library
+SIGNATURES_EXT = {
+    'icn_face_normal_agree_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4, PLAIN),
+    'icn_face_normal_agree_fwd': (ctypes.c_int, ([_c_float_p] * 3 + [ctypes.c_int] * 2) * 2 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
+    'icn_face_normal_agree_bwd': (ctypes.c_int, ([_c_float_p] * 3 + [ctypes.c_int] * 2) * 2 + [ctypes.c_int] * 3 + [_c_float_p] * 3
+                                  + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+}
 
 
 class ProfileEntry(ctypes.Structure):
@@ -139,7 +147,7 @@ def lib():
                 '(or `make -C geniconet_amd/csrc`).' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
         checked = types.SimpleNamespace()
-        for name, (res, args, reply) in SIGNATURES.items():
+        for name, (res, args, reply) in list(SIGNATURES.items()) + list(SIGNATURES_EXT.items()):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             fn = handle[name]            # a function object of its own (handle.name is cached, handle[name] is not)
@@ -202,13 +210,13 @@ def set_arith(mode):
 
 
 def source_sha256():
-    """sha256 over the kernel / library sources under csrc/ and include/icn.h (names + contents, sorted): identifies the code a
+    """sha256 over the kernel / library sources under csrc/, include/icn.h and include/icn_ext.h (names + contents, sorted): identifies the code a
     profile was measured on (tools/profile_summary.py stores it, bench.py refuses a profile of other sources)."""
     import glob
     import hashlib
     h = hashlib.sha256()
     files = sorted(glob.glob(os.path.join(_HERE, 'csrc', '*.hip')) + glob.glob(os.path.join(_HERE, 'csrc', '*.h'))
-                   + glob.glob(os.path.join(_HERE, 'csrc', '*.cpp')) + [os.path.join(os.path.dirname(_HERE), 'include', 'icn.h')])
+                   + glob.glob(os.path.join(_HERE, 'csrc', '*.cpp')) + [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('icn.h', 'icn_ext.h')])
     for f in files:
         h.update(os.path.basename(f).encode() + b'\0')
         h.update(open(f, 'rb').read())

@@ -13,7 +13,7 @@
 #include <tuple>
 #include <vector>
 
-#include "../../include/icn.h"
+#include "../../include/icn_ext.h"
 #include "icn_geometry.h"
 #include "icn_launch.h"
 #include "icn_streamk.h"
@@ -784,7 +784,9 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_p2m_grid_bounds", "k_p2m_grid_count", "k_p2m_grid_scan", "k_p2m_grid_fill",
                                             "k_p2m_grid_query",
                                             "k_msample_area", "k_msample_scan", "k_msample_point", "k_msample_bwd_record",
-                                            "k_msample_bwd_vertex"};   // both ..._bwd_vertex: k_vertex_scatter, by its caller
+                                            "k_msample_bwd_vertex",
+                                            "k_fnormal_agree", "k_fnormal_agree_bwd_record",
+                                            "k_fnormal_agree_bwd_vertex"};   // every ..._bwd_vertex: k_vertex_scatter, by its caller
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1396,6 +1398,45 @@ int icn_mesh_sample_bwd(const int32_t* faces, const int32_t* face, const float* 
         check_mesh_sizes("icn_mesh_sample_bwd", B, S, V, F);
         check_workspace("icn_mesh_sample_bwd", ws, ws_bytes, icn::vertex_records_bytes((size_t)B * S));
         icn::launch_mesh_sample_bwd(faces, face, weights, dpoints, B, S, V, F, dvertices, ws, s);
+    });
+}
+
+// ---- normal agreement of two sampled surfaces (include/icn_ext.h) ------------------------------------------------------------
+namespace {
+bool normal_agree_sizes_ok(int B, int S, int Va, int Fa, int Vb, int Fb) {
+    return mesh_sizes_ok(B, S, Va, Fa) && mesh_sizes_ok(B, S, Vb, Fb) && S <= 0x7fffffff / 2;        // 2 S records per mesh: an int
+}
+void check_normal_agree_sizes(const char* who, int B, int S, int Va, int Fa, int Vb, int Fb) {
+    if (!normal_agree_sizes_ok(B, S, Va, Fa, Vb, Fb)) throw std::invalid_argument(std::string(who) + ": bad sizes");
+}
+}  // namespace
+
+size_t icn_face_normal_agree_bwd_workspace_bytes(int B, int S, int Va, int Vb) {
+    return normal_agree_sizes_ok(B, S, Va, 1, Vb, 1) ? icn::vertex_records_bytes((size_t)B * 2 * S) : 0;
+}
+
+int icn_face_normal_agree_fwd(const float* va, const int32_t* faces_a, const int32_t* face_a, int Va, int Fa, const float* vb,
+                              const int32_t* faces_b, const int32_t* face_b, int Vb, int Fb, int B, int S, int oriented, float* t,
+                              void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!va || !faces_a || !face_a || !vb || !faces_b || !face_b || !t) throw std::invalid_argument("icn_face_normal_agree_fwd: null pointer");
+        check_normal_agree_sizes("icn_face_normal_agree_fwd", B, S, Va, Fa, Vb, Fb);
+        icn::launch_face_normal_agree_fwd(va, faces_a, face_a, Va, Fa, vb, faces_b, face_b, Vb, Fb, B, S, oriented != 0, t, s);
+    });
+}
+
+int icn_face_normal_agree_bwd(const float* va, const int32_t* faces_a, const int32_t* face_a, int Va, int Fa, const float* vb,
+                              const int32_t* faces_b, const int32_t* face_b, int Vb, int Fb, int B, int S, int oriented, const float* dt,
+                              float* dva, float* dvb, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return guarded([&] {                                             // (not `launched`: the early way out touches no device)
+        if (!va || !faces_a || !face_a || !vb || !faces_b || !face_b || !dt) throw std::invalid_argument("icn_face_normal_agree_bwd: null pointer");
+        check_normal_agree_sizes("icn_face_normal_agree_bwd", B, S, Va, Fa, Vb, Fb);
+        if (!dva && !dvb) return;                                    // no gradient asked for
+        check_workspace("icn_face_normal_agree_bwd", ws, ws_bytes, icn::vertex_records_bytes((size_t)B * 2 * S));
+        icn::launch_face_normal_agree_bwd(va, faces_a, face_a, Va, Fa, vb, faces_b, face_b, Vb, Fb, B, S, oriented != 0, dt, dva, dvb, ws, s);
+        ICN_HIP(hipGetLastError());
     });
 }
 

@@ -245,6 +245,17 @@ void launch_mesh_sample_bwd(const int32_t* faces, const int32_t* face, const flo
 size_t vertex_records_bytes(size_t n);
 void launch_vertex_scatter(int prof_kind, void* ws, int B, int n, int V, float* dvts, hipStream_t s);
 
+// normal agreement of two sampled surfaces (icn_sample.hip; include/icn_ext.h): t (B, S) from the face each sample lies on, on
+// either mesh.  One launch on s, no workspace.
+void launch_face_normal_agree_fwd(const float* va, const int32_t* faces_a, const int32_t* face_a, int Va, int Fa, const float* vb,
+                                  const int32_t* faces_b, const int32_t* face_b, int Vb, int Fb, int B, int S, int oriented, float* t,
+                                  hipStream_t s);
+// its backward to the vertices of either side (dva / dvb: null = not wanted, not both): two records per sample, then
+// launch_vertex_scatter with n = 2 S, per side; ws vertex_records_bytes(B * 2 * S) bytes, 16-byte aligned, shared by the sides.
+void launch_face_normal_agree_bwd(const float* va, const int32_t* faces_a, const int32_t* face_a, int Va, int Fa, const float* vb,
+                                  const int32_t* faces_b, const int32_t* face_b, int Vb, int Fb, int B, int S, int oriented,
+                                  const float* dt, float* dva, float* dvb, void* ws, hipStream_t s);
+
 // developer routing flags (ICN_DEBUG / icn_set_debug_flags): 16 = convs on k_gather_gemm, 32 = wgrads on k_wgrad,
 // 128 = no stream-K, 256 = fault injection: every stream-K finisher reports its partners lost (tests of the failure path),
 // 512 = masked launches walk tiles b, b + G, ... instead of the balanced tile lists, 1024 = the sparse passes of the decoder-block
@@ -255,7 +266,7 @@ int debug_flags();
 int set_debug_flags(int flags);
 
 // ---- optional per-launch HIP-event timing of the MFMA kernels (bench.py's live roofline measurement) and of the
-// point-to-mesh and surface-sampling kernels ----------
+// point-to-mesh, surface-sampling and normal-agreement kernels ----------
 enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA_64x64, PROF_GG_128x128, PROF_GG_128x64,
                 PROF_GG_64x128, PROF_GG_64x64, PROF_WGD_128x128, PROF_WGD_128x64, PROF_WGD_64x128, PROF_WGD_64x64, PROF_WG_128x128,
                 PROF_WG_128x64, PROF_WG_64x128, PROF_WG_64x64,
@@ -271,6 +282,7 @@ enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA
                 PROF_P2M, PROF_P2M_BWD_POINT, PROF_P2M_BWD_VERTEX,    // point-to-mesh distance and its backward (not MFMA; flops 0)
                 PROF_P2M_GRID_BOUNDS, PROF_P2M_GRID_COUNT, PROF_P2M_GRID_SCAN, PROF_P2M_GRID_FILL, PROF_P2M_GRID_QUERY,   // grid search
                 PROF_MSAMPLE_AREA, PROF_MSAMPLE_SCAN, PROF_MSAMPLE_POINT, PROF_MSAMPLE_BWD_RECORD, PROF_MSAMPLE_BWD_VERTEX,   // surface sampling
+                PROF_FNORMAL_AGREE, PROF_FNORMAL_AGREE_BWD_RECORD, PROF_FNORMAL_AGREE_BWD_VERTEX,   // normal agreement of sampled surfaces
                 PROF_KINDS };
 extern const char* const PROF_NAMES[PROF_KINDS];
 void prof_mark_begin(int kind, double flops, hipStream_t s);   // no-ops unless profiling is on

@@ -20,6 +20,18 @@
 //   k_msample_bwd_record  one thread per sample: the three vertex ids (-1 where the face or a vertex id is out of range: such a sample
 //                         contributes nothing and nothing is read out of bounds), dpoints and the weights -> a VertexRecords entry
 //   k_vertex_scatter      the records -> dvertices, below; also the vertex pass of the point-to-mesh backward (icn_loss.hip)
+//
+// Normal agreement of two sampled surfaces (icn_face_normal_agree_fwd / _bwd in include/icn_ext.h): per sample s of mesh pair b the
+// faces fa = face_a[b, s] of mesh a and fb = face_b[b, s] of mesh b, t = 1 - n^_a . n^_b (oriented) or 1 - |n^_a . n^_b|.
+//   n = e1 x e2 (face_normal), resolved iff |n|^2 2^22 > |e1|^2 |e2|^2 with all of it finite (TRI_FLAT of tri_dist2, icn_loss.hip);
+//   n^ = n / |n| where resolved.  An unresolved face on either side -- a face id outside [0, F) and a vertex id outside [0, V)
+//   count as one, nothing is read out of bounds -- gives t = 1 and no gradient on either side.
+//   k_fnormal_agree             one thread per sample: the six vertices -> t[b, s]
+//   k_fnormal_agree_bwd_record  one thread per sample, for ONE side ("own", the other side's arguments swapped in for side b):
+//                               h = -sigma dt (n^_other - c n^_own) / |n_own|, d/dv1 = e2 x h, d/dv2 = h x e1, d/dv0 = -(both):
+//                               two VertexRecords entries, 2 s: ids (i1, i0, -1), vector d/dv1, weights (1, -1, 0); 2 s + 1:
+//                               ids (i2, i0, -1), vector d/dv2, weights (1, -1, 0); ids (-1, -1, -1) where unresolved
+//   k_vertex_scatter            n = 2 S records per mesh -> dvertices of that side, as above
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -120,6 +132,89 @@ __global__ __launch_bounds__(SAMPLE_BLOCK) void k_msample_bwd_record(const int32
     rec.w12[at] = make_float2(weights[at * 3 + 1], weights[at * 3 + 2]);
 }
 
+// ---- normal agreement -------------------------------------------------------------------------------------------------------
+constexpr float NORMAL_FLAT = 4194304.f;       // 2^22: TRI_FLAT of tri_dist2 (icn_loss.hip), here a constant of the definition
+
+struct FaceFrame {
+    f3 e1, e2, unit;                            // edges from vertex 0, n / |n|
+    float len;                                  // |n|
+    int i0, i1, i2;
+    bool ok;                                    // ids in range and the normal resolved; nothing else is valid otherwise
+};
+
+__device__ __forceinline__ FaceFrame face_frame(const float* __restrict__ vts, const int32_t* __restrict__ faces, int b, int f, int V,
+                                                int F) {
+    FaceFrame r;
+    r.ok = false;
+    r.i0 = r.i1 = r.i2 = -1;
+    r.e1 = r.e2 = r.unit = f3{0.f, 0.f, 0.f};
+    r.len = 1.f;
+    if (f < 0 || f >= F) return r;
+    const int i0 = faces[(size_t)f * 3], i1 = faces[(size_t)f * 3 + 1], i2 = faces[(size_t)f * 3 + 2];
+    if (!(i0 >= 0 && i0 < V && i1 >= 0 && i1 < V && i2 >= 0 && i2 < V)) return r;
+    const f3 p0 = load3(vts + ((size_t)b * V + i0) * 3);
+    const f3 e1 = load3(vts + ((size_t)b * V + i1) * 3) - p0, e2 = load3(vts + ((size_t)b * V + i2) * 3) - p0;
+    const f3 n = face_normal(e1, e2);           // every product rounded on its own: exactly 0 for coincident vertices
+    const float nn = fmaf(n.z, n.z, fmaf(n.x, n.x, n.y * n.y));
+    const float q = nn * NORMAL_FLAT, ll = dot(e1, e1) * dot(e2, e2);
+    if (!(q > ll) || !(q <= 3.4028234663852886e38f)) return r;            // flat, NaN or overflowed (ll = inf fails q > ll)
+    const float len = sqrtf(nn);
+    r.e1 = e1; r.e2 = e2;
+    r.unit = f3{n.x / len, n.y / len, n.z / len};
+    r.len = len;
+    r.i0 = i0; r.i1 = i1; r.i2 = i2;
+    r.ok = true;
+    return r;
+}
+
+__global__ __launch_bounds__(SAMPLE_BLOCK) void k_fnormal_agree(const float* __restrict__ va, const int32_t* __restrict__ faces_a,
+                                                                 const int32_t* __restrict__ face_a, int Va, int Fa,
+                                                                 const float* __restrict__ vb, const int32_t* __restrict__ faces_b,
+                                                                 const int32_t* __restrict__ face_b, int Vb, int Fb, int S,
+                                                                 int oriented, float* __restrict__ t) {
+    const int b = blockIdx.y, s = blockIdx.x * SAMPLE_BLOCK + threadIdx.x;
+    if (s >= S) return;
+    const size_t at = (size_t)b * S + s;
+    const FaceFrame A = face_frame(va, faces_a, b, face_a[at], Va, Fa);
+    const FaceFrame Bf = face_frame(vb, faces_b, b, face_b[at], Vb, Fb);
+    float tv = 1.f;
+    if (A.ok && Bf.ok) {
+        const float c = dot(A.unit, Bf.unit);
+        tv = 1.f - (oriented ? c : fabsf(c));
+    }
+    t[at] = tv;
+}
+
+// the records of side "own" (vo, faces_o, face_o); "other" (vx, ...) enters through its unit normal only
+__global__ __launch_bounds__(SAMPLE_BLOCK) void k_fnormal_agree_bwd_record(const float* __restrict__ vo, const int32_t* __restrict__ faces_o,
+                                                                            const int32_t* __restrict__ face_o, int Vo, int Fo,
+                                                                            const float* __restrict__ vx, const int32_t* __restrict__ faces_x,
+                                                                            const int32_t* __restrict__ face_x, int Vx, int Fx, int S,
+                                                                            int oriented, const float* __restrict__ dt, VertexRecords rec) {
+    const int b = blockIdx.y, s = blockIdx.x * SAMPLE_BLOCK + threadIdx.x;
+    if (s >= S) return;
+    const size_t at = (size_t)b * S + s;
+    const FaceFrame O = face_frame(vo, faces_o, b, face_o[at], Vo, Fo);
+    const FaceFrame X = face_frame(vx, faces_x, b, face_x[at], Vx, Fx);
+    int4 id1 = make_int4(-1, -1, -1, -1), id2 = id1;
+    f3 d1 = {0.f, 0.f, 0.f}, d2 = d1;
+    if (O.ok && X.ok) {
+        const float c = dot(O.unit, X.unit);
+        const float sigma = oriented ? 1.f : (c > 0.f ? 1.f : (c < 0.f ? -1.f : 0.f));     // d|c| / dc, 0 at c = 0
+        const f3 h = scaled(X.unit - scaled(O.unit, c), -sigma * dt[at] / O.len);
+        d1 = cross(O.e2, h);
+        d2 = cross(h, O.e1);
+        id1 = make_int4(O.i1, O.i0, -1, -1);
+        id2 = make_int4(O.i2, O.i0, -1, -1);
+    }
+    rec.id[2 * at] = id1;
+    rec.gw[2 * at] = make_float4(d1.x, d1.y, d1.z, 1.f);
+    rec.w12[2 * at] = make_float2(-1.f, 0.f);
+    rec.id[2 * at + 1] = id2;
+    rec.gw[2 * at + 1] = make_float4(d2.x, d2.y, d2.z, 1.f);
+    rec.w12[2 * at + 1] = make_float2(-1.f, 0.f);
+}
+
 // One thread per vertex: the n records of its mesh go through LDS in tiles of 256 and every thread adds those addressed to it IN
 // RECORD ORDER (then vertex 0, 1, 2 of the face) -- a fixed order, no atomics, bit-identical run to run.  n * V integer compares
 // per mesh, one broadcast ds_read_b128 per record and wave; a vertex no record addresses gets an exact zero.
@@ -193,6 +288,36 @@ void launch_mesh_sample_bwd(const int32_t* faces, const int32_t* face, const flo
                        weights, dpoints, S, V, F, vertex_records(ws, (size_t)B * S));
     prof_mark_end(s);
     launch_vertex_scatter(PROF_MSAMPLE_BWD_VERTEX, ws, B, S, V, dvts, s);
+}
+
+void launch_face_normal_agree_fwd(const float* va, const int32_t* faces_a, const int32_t* face_a, int Va, int Fa, const float* vb,
+                                  const int32_t* faces_b, const int32_t* face_b, int Vb, int Fb, int B, int S, int oriented, float* t,
+                                  hipStream_t s) {
+    prof_mark_begin(PROF_FNORMAL_AGREE, 0.0, s);
+    hipLaunchKernelGGL(k_fnormal_agree, dim3((S + SAMPLE_BLOCK - 1) / SAMPLE_BLOCK, B), dim3(SAMPLE_BLOCK), 0, s, va, faces_a, face_a, Va,
+                       Fa, vb, faces_b, face_b, Vb, Fb, S, oriented, t);
+    prof_mark_end(s);
+}
+
+void launch_face_normal_agree_bwd(const float* va, const int32_t* faces_a, const int32_t* face_a, int Va, int Fa, const float* vb,
+                                  const int32_t* faces_b, const int32_t* face_b, int Vb, int Fb, int B, int S, int oriented,
+                                  const float* dt, float* dva, float* dvb, void* ws, hipStream_t s) {
+    const dim3 grid((S + SAMPLE_BLOCK - 1) / SAMPLE_BLOCK, B);
+    const VertexRecords rec = vertex_records(ws, (size_t)B * 2 * S);
+    if (dva) {
+        prof_mark_begin(PROF_FNORMAL_AGREE_BWD_RECORD, 0.0, s);
+        hipLaunchKernelGGL(k_fnormal_agree_bwd_record, grid, dim3(SAMPLE_BLOCK), 0, s, va, faces_a, face_a, Va, Fa, vb, faces_b, face_b,
+                           Vb, Fb, S, oriented, dt, rec);
+        prof_mark_end(s);
+        launch_vertex_scatter(PROF_FNORMAL_AGREE_BWD_VERTEX, ws, B, 2 * S, Va, dva, s);
+    }
+    if (dvb) {                                                             // the same workspace again, in stream order
+        prof_mark_begin(PROF_FNORMAL_AGREE_BWD_RECORD, 0.0, s);
+        hipLaunchKernelGGL(k_fnormal_agree_bwd_record, grid, dim3(SAMPLE_BLOCK), 0, s, vb, faces_b, face_b, Vb, Fb, va, faces_a, face_a,
+                           Va, Fa, S, oriented, dt, rec);
+        prof_mark_end(s);
+        launch_vertex_scatter(PROF_FNORMAL_AGREE_BWD_VERTEX, ws, B, 2 * S, Vb, dvb, s);
+    }
 }
 
 }  // namespace icn

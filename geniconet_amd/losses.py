@@ -19,7 +19,8 @@ on icn_kld_fwd / icn_kld_bwd under the same conditions.
 
 Point2Mesh_Loss is not in the reference: the surface distance it reports at test time (ico_utils.py:26-44) as a loss term.
 Surface_Loss / SurfaceKLD_Loss (train.build_criterion: 'surface' / 'surfacekld') make a training criterion of it: the distance in
-both directions plus Mesh_Regularizer (edge length, normal consistency, Laplacian smoothness; HIP kernels icn_mesh_reg_*).
+both directions plus Mesh_Regularizer (edge length, normal consistency, Laplacian smoothness; HIP kernels icn_mesh_reg_*); from
+surface samples (samples > 0) optionally with the normal agreement of the two surfaces (factor_normal; icn_face_normal_agree_*).
 """
 import math
 import os
@@ -439,20 +440,44 @@ class Surface_Loss(torch.nn.Module):
     device takes 0.36 ms forward and 1.04 ms forward + backward against 0.09 / 1.24 ms on the HIP path: the HIP forward is 4 x
     faster, the fixed-order HIP backward is what buys run-to-run identity and is no faster than torch's atomic index_put.  This whole
     term, forward + backward: samples = 0 33.2 ms ('brute') / 2.8 ms ('grid'); samples = S 38.4 / 4.2 ms, beside a training step of
-    6.6 ms."""
+    6.6 ms.
+
+    factor_normal != 0 (needs samples > 0: a vertex has no face of its own; ValueError otherwise) adds what the distances cannot
+    see -- a sheet that lies on the target but faces the wrong way, wrinkles across the surface below the sample scale -- from the
+    faces the forward already has, with fna = metrics.face_normal_agreement (1 - n^_a . n^_b per sample, or 1 - |n^_a . n^_b| with
+    normal_oriented=False; an unresolved face gives 1 and no gradient):
+        l_n = 0.5 * ( mean fna(out mesh, face of sample_points(out mesh, u[0]),   ref mesh, closest ref face of those points)
+                    + mean fna(ref mesh, face of sample_points(ref mesh, u[1]),   out mesh, closest out face of those points) )
+        loss += factor_normal * l_n                                      gradient to the output through icn_face_normal_agree_bwd
+    The term draws no random numbers of its own (the draw order above stays the contract) and never synchronises the host; last_normal
+    holds l_n (a device tensor; 0 while the term is off) and get_last_losses() keeps its five-tuple.  With factor_normal = 0 (the
+    default) the term is not evaluated: the same kernels, the same draw, the same results bit for bit.
+    Cost of factor_normal != 0 on an MI355X at I5 / batch 36 with S = 10 242 (HIP events, median of 10, profiles/normal_agreement.txt,
+    from `python tools/time_normal_agreement.py 10`): k_fnormal_agree 0.02 ms, k_fnormal_agree_bwd_record 0.02 ms,
+    k_fnormal_agree_bwd_vertex 2.04 ms per side (2 S V integer compares per mesh: twice the sampler's scatter).  The torch formulation on
+    the device takes 0.69 ms forward and 1.89 ms forward + backward of both sides against 0.05 / 4.33 ms on the HIP path: the HIP forward
+    is 15 x faster, the fixed-order HIP backward is again what buys run-to-run identity and does not beat torch's atomic index_put.
+    This whole term, forward + backward, samples = S: 38.2 -> 42.3 ms ('brute'), 4.2 -> 8.4 ms ('grid') with the normal term (the
+    output's side of both halves: two record passes and two scatters)."""
 
     def __init__(self, subdivisions, factor_p2m=1.0, factor_m2p=1.0, factor_edge=0.0, factor_ncons=0.0, factor_smooth=0.0,
-                 edge_length=0.0, search='brute', samples=0, sample_seed=0):
+                 edge_length=0.0, search='brute', samples=0, sample_seed=0, factor_normal=0.0, normal_oriented=True):
         super().__init__()
         from .metrics import _check_search
         _check_search(search)
         _check_subdivisions('Surface_Loss', subdivisions)
-        _check_factors('Surface_Loss', factor_p2m=factor_p2m, factor_m2p=factor_m2p)
+        _check_factors('Surface_Loss', factor_p2m=factor_p2m, factor_m2p=factor_m2p, factor_normal=factor_normal)
         if isinstance(samples, bool) or not isinstance(samples, int) or samples < 0:
             raise ValueError('%s: samples must be a non-negative integer, got %r' % (type(self).__name__, samples))
         if isinstance(sample_seed, bool) or not isinstance(sample_seed, int):
             raise ValueError('%s: sample_seed must be an integer, got %r' % (type(self).__name__, sample_seed))
+        if factor_normal != 0 and samples == 0:
+            raise ValueError('%s: factor_normal needs samples > 0 (a vertex has no face of its own), got samples = 0'
+                             % type(self).__name__)
+        if not isinstance(normal_oriented, bool):
+            raise ValueError('%s: normal_oriented must be a bool, got %r' % (type(self).__name__, normal_oriented))
         self.samples, self.sample_seed, self._sample_generator = samples, sample_seed, None
+        self.factor_normal, self.normal_oriented = factor_normal, normal_oriented
         self.subdivisions, self.search = subdivisions, search
         self.factor_p2m, self.factor_m2p = factor_p2m, factor_m2p
         self.regularizer = Mesh_Regularizer(subdivisions, factor_edge, factor_ncons, factor_smooth, edge_length)
@@ -461,7 +486,7 @@ class Surface_Loss(torch.nn.Module):
         if faces.ndim != 2 or faces.shape[1] != 3 or faces.min() < 0 or faces.max() >= nv:
             raise ValueError('Surface_Loss: the face table does not index %d vertices' % nv)
         self.register_buffer('ico_faces', torch.from_numpy(faces).to(torch.int32))
-        self.last_p2m = self.last_m2p = self.last_reg = self.last_loss_total = 0
+        self.last_p2m = self.last_m2p = self.last_reg = self.last_loss_total = self.last_normal = 0
 
     def _draw_uniforms(self, B, device):
         """The (2, B, S, 3) uniforms of one forward, from the generator seeded with sample_seed on the first forward's device."""
@@ -485,16 +510,27 @@ class Surface_Loss(torch.nn.Module):
         faces = self.ico_faces if self.ico_faces.device == out.device else self.ico_faces.to(out.device)
         p_out, p_ref = out, ref                                               # the points measured against the other surface
         u = self._draw_uniforms(out.shape[0], out.device) if self.samples else None
+        normal = self.factor_normal != 0                                      # (then samples > 0: checked at construction)
         with torch.set_grad_enabled(grad and self.factor_p2m != 0):
             if u is not None:
-                p_out = _sample_points_unchecked(out, faces, u[0])[0]
-            l_p2m = _point_to_mesh_unchecked(p_out, ref, faces, self.search)[0].mean()
+                p_out, on_out, _ = _sample_points_unchecked(out, faces, u[0])
+            l_p2m, near_ref, _ = _point_to_mesh_unchecked(p_out, ref, faces, self.search)
+            l_p2m = l_p2m.mean()
         with torch.set_grad_enabled(grad and self.factor_m2p != 0):
             if u is not None:
-                p_ref = _sample_points_unchecked(ref, faces, u[1])[0]
-            l_m2p = _point_to_mesh_unchecked(p_ref, out, faces, self.search)[0].mean()
+                p_ref, on_ref, _ = _sample_points_unchecked(ref, faces, u[1])
+            l_m2p, near_out, _ = _point_to_mesh_unchecked(p_ref, out, faces, self.search)
+            l_m2p = l_m2p.mean()
         l_reg = self.regularizer(output)
         loss = self.factor_p2m * l_p2m + self.factor_m2p * l_m2p + l_reg
+        if normal:                                                            # no further draw: the faces the forward already has
+            from .metrics import _face_normal_agreement_unchecked as fna
+            l_n = 0.5 * (fna(out, faces, on_out, ref, faces, near_ref, self.normal_oriented).mean()
+                         + fna(ref, faces, on_ref, out, faces, near_out, self.normal_oriented).mean())
+            loss = loss + self.factor_normal * l_n
+            self.last_normal = l_n.detach()
+        else:
+            self.last_normal = 0                                              # (not a tensor: the default path launches nothing new)
         self.last_p2m, self.last_m2p, self.last_reg = l_p2m.detach(), l_m2p.detach(), l_reg.detach()
         self.last_loss_total = loss.detach()
         return loss
@@ -555,9 +591,9 @@ class SurfaceKLD_Loss(Surface_Loss, KLD_Loss):
     """Surface_Loss of the reconstruction + factor_kl * KLD, for (recon, mu, logvar) outputs -- as P2PKLD_Loss is to P2P_Loss."""
 
     def __init__(self, subdivisions, factor_p2m=1.0, factor_m2p=1.0, factor_edge=0.0, factor_ncons=0.0, factor_smooth=0.0,
-                 edge_length=0.0, search='brute', factor_kl=1.0, samples=0, sample_seed=0):
+                 edge_length=0.0, search='brute', factor_kl=1.0, samples=0, sample_seed=0, factor_normal=0.0, normal_oriented=True):
         super().__init__(subdivisions, factor_p2m, factor_m2p, factor_edge, factor_ncons, factor_smooth, edge_length, search,
-                         samples=samples, sample_seed=sample_seed)
+                         samples=samples, sample_seed=sample_seed, factor_normal=factor_normal, normal_oriented=normal_oriented)
         _check_factors('SurfaceKLD_Loss', factor_kl=factor_kl)
         self.factor_kl = factor_kl
 

@@ -29,6 +29,9 @@ Like kaolin's function, dist2 is differentiable in the points and in the mesh ve
 through autograd, the HIP path through icn_point_to_mesh_bwd (_PointToMeshFn below) whenever one of the two requires a gradient;
 face and kind never carry one.  Where two different closest points are equally near the gradient is discontinuous (either side
 is a valid subgradient).
+
+face_normal_agreement (below) compares the normals of two such surfaces sample by sample: the face a surface sample lies on against
+the closest face of the other mesh, `face` of sampling.sample_points and of point_to_mesh_distance.
 """
 import torch
 
@@ -231,6 +234,146 @@ def point_to_mesh_distance(pointclouds, vertices, faces, search='brute'):
         return _point_to_mesh_unchecked(pointclouds, vertices, faces.to(device=pointclouds.device, dtype=torch.int32).contiguous(),
                                         search)
     return _torch_point_to_mesh(pointclouds, vertices, faces.to(pointclouds.device))
+
+
+# ---- normal agreement of two sampled surfaces ---------------------------------------------------------------------------------------
+_NORMAL_FLAT = 4194304.0           # 2^22: TRI_FLAT of tri_dist2 (csrc/icn_loss.hip); a constant of the definition, in every dtype
+
+
+def _resolved_unit_normals(vertices, faces, face):
+    """(n^ (B, S, 3), |n| (B, S), resolved (B, S)) of faces[face] of every mesh, as face_normal_agreement defines them: n^ is 0 and
+    carries no gradient where the normal is unresolved (a face id outside [0, F) and a vertex id outside [0, V) included; ids are
+    clamped before they index anything)."""
+    from .losses import Mesh_Regularizer
+    V, F = vertices.shape[1], faces.shape[0]
+    face = face.long()
+    ids = faces.long()[face.clamp(0, F - 1)]                                             # (B, S, 3)
+    ok = (face >= 0) & (face < F) & ((ids >= 0) & (ids < V)).all(-1)
+    corners = torch.gather(vertices, 1, ids.clamp(0, V - 1).reshape(ids.shape[0], -1, 1).expand(-1, -1, 3)).view(*ids.shape, 3)
+    e1, e2 = corners[:, :, 1] - corners[:, :, 0], corners[:, :, 2] - corners[:, :, 0]
+    with torch.no_grad():
+        n = Mesh_Regularizer._face_normal(e1, e2)
+        q = (n * n).sum(-1) * _NORMAL_FLAT
+        ok = ok & (q > (e1 * e1).sum(-1) * (e2 * e2).sum(-1)) & torch.isfinite(q)
+    # an unresolved face enters as a zero triangle: its (possibly non-finite) vertices meet no arithmetic that autograd records
+    zero = torch.zeros_like(e1)
+    e1, e2 = torch.where(ok[..., None], e1, zero), torch.where(ok[..., None], e2, zero)
+    n = Mesh_Regularizer._face_normal(e1, e2)
+    nn = (n * n).sum(-1)
+    length = torch.where(ok, nn, torch.ones_like(nn)).sqrt()
+    return n / length[..., None], length, ok
+
+
+def _torch_face_normal_agreement(vertices_a, faces_a, face_a, vertices_b, faces_b, face_b, oriented=True):
+    """The definition of face_normal_agreement in torch, differentiable in both vertex tensors through autograd."""
+    ua, _, _ = _resolved_unit_normals(vertices_a, faces_a, face_a)
+    ub, _, _ = _resolved_unit_normals(vertices_b, faces_b, face_b)
+    c = (ua * ub).sum(-1)                                                                # 0 where either side is unresolved
+    return 1 - (c if oriented else c.abs())                                              # (abs: derivative 0 at c = 0)
+
+
+def _hip_face_normal_agreement(va, fa32, face_a, vb, fb32, face_b, oriented):
+    """icn_face_normal_agree_fwd on contiguous fp32 ROCm vertices, int32 face tables and int32 (B, S) face ids -> t (B, S)."""
+    L = _lib.api()
+    (B, S), Va, Vb, Fa, Fb = face_a.shape, va.shape[1], vb.shape[1], fa32.shape[0], fb32.shape[0]
+    t = torch.empty(B, S, dtype=torch.float32, device=va.device)
+    with torch.cuda.device(va.device):
+        for b0, nb in _batch_slices(B):
+            L.icn_face_normal_agree_fwd(va[b0:].data_ptr(), fa32.data_ptr(), face_a[b0:].data_ptr(), Va, Fa, vb[b0:].data_ptr(),
+                                        fb32.data_ptr(), face_b[b0:].data_ptr(), Vb, Fb, nb, S, int(oriented), t[b0:].data_ptr(),
+                                        _lib.stream())
+    return t
+
+
+class _FaceNormalAgreementFn(torch.autograd.Function):
+    """face_normal_agreement on the HIP path (icn_face_normal_agree_fwd / _bwd in include/icn_ext.h); only the sides autograd asks
+    for are computed, each summed in a fixed order (bit-identical run to run)."""
+
+    @staticmethod
+    def forward(ctx, vertices_a, fa32, face_a, vertices_b, fb32, face_b, oriented):
+        va, vb = vertices_a.contiguous(), vertices_b.contiguous()
+        ia, ib = face_a.to(torch.int32).contiguous(), face_b.to(torch.int32).contiguous()
+        ctx.save_for_backward(va, fa32, ia, vb, fb32, ib)
+        ctx.oriented = int(oriented)
+        return _hip_face_normal_agreement(va, fa32, ia, vb, fb32, ib, oriented)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dt):
+        L = _lib.api()
+        va, fa32, ia, vb, fb32, ib = ctx.saved_tensors
+        (B, S), Va, Vb, Fa, Fb = ia.shape, va.shape[1], vb.shape[1], fa32.shape[0], fb32.shape[0]
+        up = dt.contiguous().to(torch.float32)
+        dva = torch.empty_like(va) if ctx.needs_input_grad[0] else None
+        dvb = torch.empty_like(vb) if ctx.needs_input_grad[3] else None
+        if dva is None and dvb is None:
+            return (None,) * 7
+        ws_bytes = L.icn_face_normal_agree_bwd_workspace_bytes(min(B, _MAX_GRID_Y), S, Va, Vb)
+        ws = _lib.workspace(ws_bytes, va.device)
+        with torch.cuda.device(va.device):
+            for b0, nb in _batch_slices(B):
+                L.icn_face_normal_agree_bwd(va[b0:].data_ptr(), fa32.data_ptr(), ia[b0:].data_ptr(), Va, Fa, vb[b0:].data_ptr(),
+                                            fb32.data_ptr(), ib[b0:].data_ptr(), Vb, Fb, nb, S, ctx.oriented, up[b0:].data_ptr(),
+                                            dva[b0:].data_ptr() if dva is not None else None,
+                                            dvb[b0:].data_ptr() if dvb is not None else None, ws.data_ptr(), ws_bytes, _lib.stream())
+        return dva, None, None, dvb, None, None, None
+
+
+def _face_normal_agreement_unchecked(vertices_a, fa32, face_a, vertices_b, fb32, face_b, oriented=True):
+    """face_normal_agreement without its argument checks and without a host synchronisation, for callers that validated once
+    (losses.Surface_Loss): fa32 / fb32 are int32 (F, 3) tensors on the vertices' device, F >= 1; face_a / face_b (B, S) integer
+    tensors there.  Ids out of range are safe on either path: such a sample is unresolved (t = 1, no gradient)."""
+    from . import losses
+    if (not losses._NO_HIP_LOSS and vertices_a.is_cuda and vertices_a.dtype == torch.float32 and vertices_b.dtype == torch.float32):
+        if torch.is_grad_enabled() and (vertices_a.requires_grad or vertices_b.requires_grad):
+            return _FaceNormalAgreementFn.apply(vertices_a, fa32, face_a, vertices_b, fb32, face_b, bool(oriented))
+        return _hip_face_normal_agreement(vertices_a.detach().contiguous(), fa32, face_a.to(torch.int32).contiguous(),
+                                          vertices_b.detach().contiguous(), fb32, face_b.to(torch.int32).contiguous(), bool(oriented))
+    return _torch_face_normal_agreement(vertices_a, fa32, face_a, vertices_b, fb32, face_b, oriented)
+
+
+def face_normal_agreement(vertices_a, faces_a, face_a, vertices_b, faces_b, face_b, oriented=True):
+    """Normal agreement of two sampled surfaces, t (B, S): for sample s of mesh pair b, face face_a[b, s] of mesh a (vertices_a
+    (B, Va, 3), faces_a (Fa, 3) shared by the batch) against face face_b[b, s] of mesh b -- typically the face a surface sample lies
+    on (sampling.sample_points) and the closest face of the other mesh (point_to_mesh_distance).  What pytorch3d's
+    chamfer_distance(x_normals=...) adds to the distance, from face normals.
+
+    One definition for the HIP kernels (include/icn_ext.h), the torch formulation and the tests.  For a face (i0, i1, i2):
+        e1 = v1 - v0, e2 = v2 - v0, n = e1 x e2 with every product of the cross product rounded on its own
+        (Mesh_Regularizer._face_normal; face_normal on the device): a face with two coincident vertices has n exactly 0
+        the normal is RESOLVED iff |n|^2 2^22 > |e1|^2 |e2|^2 and all of that is finite (the constant of tri_dist2, in every dtype)
+        n^ = n / |n| where resolved, else 0, and no gradient passes through that face
+        c = n^_a . n^_b;   t = 1 - c (oriented, the default)  or  1 - |c| (the derivative of |c| at c = 0 is taken as 0)
+    An unresolved face on either side gives t = 1 and a zero gradient on both sides; non-finite vertices are unresolved, never NaN
+    in the gradient.  Differentiable in both vertex tensors: ROCm fp32 tensors run on icn_face_normal_agree_fwd / _bwd (the
+    gradient of each side that requires one, summed in a fixed order without atomics: bit-identical run to run, an exact zero at a
+    vertex no sample touches); ICN_NO_HIP_LOSS=1, CPU tensors and other dtypes take the torch formulation through autograd.
+    Shapes are checked (ValueError); face ids against F and face tables against V with one read-back (IndexError)."""
+    who = 'face_normal_agreement'
+    for v, name in ((vertices_a, 'vertices_a'), (vertices_b, 'vertices_b')):
+        if v.dim() != 3 or v.shape[-1] != 3 or v.shape[0] < 1 or v.shape[1] < 1 or not v.is_floating_point():
+            raise ValueError('%s: expected floating-point %s (B, V, 3), got %s' % (who, name, tuple(v.shape)))
+    if vertices_a.shape[0] != vertices_b.shape[0] or vertices_a.dtype != vertices_b.dtype or vertices_a.device != vertices_b.device:
+        raise ValueError('%s: the two vertex tensors differ in batch size, dtype or device' % who)
+    for f, name in ((faces_a, 'faces_a'), (faces_b, 'faces_b')):
+        if f.dim() != 2 or f.shape[1] != 3 or f.shape[0] < 1 or f.is_floating_point():
+            raise ValueError('%s: expected integer %s (F, 3) with F >= 1, got %s' % (who, name, tuple(f.shape)))
+    B = vertices_a.shape[0]
+    for f, name in ((face_a, 'face_a'), (face_b, 'face_b')):
+        if f.dim() != 2 or f.shape[0] != B or f.shape[1] < 1 or f.is_floating_point() or f.dtype == torch.bool:
+            raise ValueError('%s: expected integer %s (%d, S) with S >= 1, got %s' % (who, name, B, tuple(f.shape)))
+    if face_a.shape != face_b.shape:
+        raise ValueError('%s: face_a %s and face_b %s differ in shape' % (who, tuple(face_a.shape), tuple(face_b.shape)))
+    dev = vertices_a.device
+    fa32, fb32 = (f.to(device=dev, dtype=torch.int32).contiguous() for f in (faces_a, faces_b))
+    face_a, face_b = face_a.to(dev), face_b.to(dev)
+    spans = torch.stack([torch.stack(x.aminmax()).long() for x in (fa32, fb32, face_a, face_b)]).tolist()      # one read-back
+    for (lo, hi), limit, what, of in zip(spans, (vertices_a.shape[1], vertices_b.shape[1], fa32.shape[0], fb32.shape[0]),
+                                         ('faces_a indexes', 'faces_b indexes', 'face_a indexes', 'face_b indexes'),
+                                         ('vertices', 'vertices', 'faces', 'faces')):
+        if lo < 0 or hi >= limit:
+            raise IndexError('%s: %s [%d, %d] but there are %d %s' % (who, what, lo, hi, limit, of))
+    return _face_normal_agreement_unchecked(vertices_a, fa32, face_a, vertices_b, fb32, face_b, oriented)
 
 
 def output2vertices(subdivisions, output):
