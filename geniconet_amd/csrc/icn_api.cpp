@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/icn_ext.h"
+#include "../../include/icn_measure.h"
 #include "icn_geometry.h"
 #include "icn_launch.h"
 #include "icn_streamk.h"
@@ -786,7 +787,8 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_msample_area", "k_msample_scan", "k_msample_point", "k_msample_bwd_record",
                                             "k_msample_bwd_vertex",
                                             "k_fnormal_agree", "k_fnormal_agree_bwd_record",
-                                            "k_fnormal_agree_bwd_vertex"};   // every ..._bwd_vertex: k_vertex_scatter, by its caller
+                                            "k_fnormal_agree_bwd_vertex",    // every ..._bwd_vertex: k_vertex_scatter, by its caller
+                                            "k_mesh_measure_face", "k_mesh_measure_finish", "k_mesh_measure_bwd"};
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1437,6 +1439,39 @@ int icn_face_normal_agree_bwd(const float* va, const int32_t* faces_a, const int
         check_workspace("icn_face_normal_agree_bwd", ws, ws_bytes, icn::vertex_records_bytes((size_t)B * 2 * S));
         icn::launch_face_normal_agree_bwd(va, faces_a, face_a, Va, Fa, vb, faces_b, face_b, Vb, Fb, B, S, oriented != 0, dt, dva, dvb, ws, s);
         ICN_HIP(hipGetLastError());
+    });
+}
+
+// ---- surface area and enclosed volume (include/icn_measure.h) ----------------------------------------------------------------
+namespace {
+bool measure_sizes_ok(int B, int V, int F) { return mesh_sizes_ok(B, 1, V, F) && F <= 0x7fffffff / 3; }      // 3 F corners: an int
+void check_measure_sizes(const char* who, int B, int V, int F) {
+    if (!measure_sizes_ok(B, V, F)) throw std::invalid_argument(std::string(who) + ": bad sizes");
+}
+}  // namespace
+
+size_t icn_mesh_measure_workspace_bytes(int B, int V, int F) {
+    return measure_sizes_ok(B, V, F) ? icn::mesh_measure_bytes(B, F) : 0;
+}
+
+int icn_mesh_measure_fwd(const float* vertices, const int32_t* faces, int B, int V, int F, float* area, float* volume, void* ws,
+                         size_t ws_bytes, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!vertices || !faces || !area || !volume) throw std::invalid_argument("icn_mesh_measure_fwd: null pointer");
+        check_measure_sizes("icn_mesh_measure_fwd", B, V, F);
+        check_workspace("icn_mesh_measure_fwd", ws, ws_bytes, icn::mesh_measure_bytes(B, F));
+        icn::launch_mesh_measure_fwd(vertices, faces, B, V, F, area, volume, ws, s);
+    });
+}
+
+int icn_mesh_measure_bwd(const float* vertices, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_corners,
+                         const float* darea, const float* dvolume, int B, int V, int F, float* dvertices, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!vertices || !faces || !vf_offsets || !vf_corners || !dvertices) throw std::invalid_argument("icn_mesh_measure_bwd: null pointer");
+        check_measure_sizes("icn_mesh_measure_bwd", B, V, F);
+        icn::launch_mesh_measure_bwd(vertices, faces, vf_offsets, vf_corners, darea, dvolume, B, V, F, dvertices, s);
     });
 }
 

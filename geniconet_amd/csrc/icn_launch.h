@@ -256,6 +256,16 @@ void launch_face_normal_agree_bwd(const float* va, const int32_t* faces_a, const
                                   const int32_t* faces_b, const int32_t* face_b, int Vb, int Fb, int B, int S, int oriented,
                                   const float* dt, float* dva, float* dvb, void* ws, hipStream_t s);
 
+// surface area and enclosed volume per mesh (icn_measure.hip; include/icn_measure.h).  ws: mesh_measure_bytes(B, F) bytes (two doubles
+// per mesh and block of faces), 16-byte aligned.  Two launches on s.
+size_t mesh_measure_bytes(int B, int F);
+void launch_mesh_measure_fwd(const float* vts, const int32_t* faces, int B, int V, int F, float* area, float* volume, void* ws,
+                             hipStream_t s);
+// its backward to the vertices: a gather over the vertex -> corner incidence table (offsets (V + 1), corners (3 F)); darea / dvolume
+// null = that term skipped.  One launch on s, no workspace, no atomics.
+void launch_mesh_measure_bwd(const float* vts, const int32_t* faces, const int32_t* offsets, const int32_t* corners, const float* darea,
+                             const float* dvolume, int B, int V, int F, float* dvts, hipStream_t s);
+
 // developer routing flags (ICN_DEBUG / icn_set_debug_flags): 16 = convs on k_gather_gemm, 32 = wgrads on k_wgrad,
 // 128 = no stream-K, 256 = fault injection: every stream-K finisher reports its partners lost (tests of the failure path),
 // 512 = masked launches walk tiles b, b + G, ... instead of the balanced tile lists, 1024 = the sparse passes of the decoder-block
@@ -266,7 +276,7 @@ int debug_flags();
 int set_debug_flags(int flags);
 
 // ---- optional per-launch HIP-event timing of the MFMA kernels (bench.py's live roofline measurement) and of the
-// point-to-mesh, surface-sampling and normal-agreement kernels ----------
+// point-to-mesh, surface-sampling, normal-agreement and mesh-measure kernels ----------
 enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA_64x64, PROF_GG_128x128, PROF_GG_128x64,
                 PROF_GG_64x128, PROF_GG_64x64, PROF_WGD_128x128, PROF_WGD_128x64, PROF_WGD_64x128, PROF_WGD_64x64, PROF_WG_128x128,
                 PROF_WG_128x64, PROF_WG_64x128, PROF_WG_64x64,
@@ -283,6 +293,7 @@ enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA
                 PROF_P2M_GRID_BOUNDS, PROF_P2M_GRID_COUNT, PROF_P2M_GRID_SCAN, PROF_P2M_GRID_FILL, PROF_P2M_GRID_QUERY,   // grid search
                 PROF_MSAMPLE_AREA, PROF_MSAMPLE_SCAN, PROF_MSAMPLE_POINT, PROF_MSAMPLE_BWD_RECORD, PROF_MSAMPLE_BWD_VERTEX,   // surface sampling
                 PROF_FNORMAL_AGREE, PROF_FNORMAL_AGREE_BWD_RECORD, PROF_FNORMAL_AGREE_BWD_VERTEX,   // normal agreement of sampled surfaces
+                PROF_MESH_MEASURE_FACE, PROF_MESH_MEASURE_FINISH, PROF_MESH_MEASURE_BWD,            // area and volume per mesh
                 PROF_KINDS };
 extern const char* const PROF_NAMES[PROF_KINDS];
 void prof_mark_begin(int kind, double flops, hipStream_t s);   // no-ops unless profiling is on

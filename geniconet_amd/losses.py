@@ -20,7 +20,8 @@ on icn_kld_fwd / icn_kld_bwd under the same conditions.
 Point2Mesh_Loss is not in the reference: the surface distance it reports at test time (ico_utils.py:26-44) as a loss term.
 Surface_Loss / SurfaceKLD_Loss (train.build_criterion: 'surface' / 'surfacekld') make a training criterion of it: the distance in
 both directions plus Mesh_Regularizer (edge length, normal consistency, Laplacian smoothness; HIP kernels icn_mesh_reg_*); from
-surface samples (samples > 0) optionally with the normal agreement of the two surfaces (factor_normal; icn_face_normal_agree_*).
+surface samples (samples > 0) optionally with the normal agreement of the two surfaces (factor_normal; icn_face_normal_agree_*),
+and optionally with the enclosed volume and the surface area held to the target's (factor_volume / factor_area; icn_mesh_measure_*).
 """
 import math
 import os
@@ -458,15 +459,37 @@ class Surface_Loss(torch.nn.Module):
     the device takes 0.69 ms forward and 1.89 ms forward + backward of both sides against 0.05 / 4.33 ms on the HIP path: the HIP forward
     is 15 x faster, the fixed-order HIP backward is again what buys run-to-run identity and does not beat torch's atomic index_put.
     This whole term, forward + backward, samples = S: 38.2 -> 42.3 ms ('brute'), 4.2 -> 8.4 ms ('grid') with the normal term (the
-    output's side of both halves: two record passes and two scatters)."""
+    output's side of both halves: two record passes and two scatters).
+
+    factor_volume / factor_area != 0 hold the two global measures of the output mesh to the target's.  The three regularisers are
+    local and share one global failure -- they shrink the mesh (the umbrella operator is the textbook case) -- which nothing else
+    here measures.  With (area, vol) = metrics.mesh_area_volume(., ico_faces) (every ico mesh is closed and wound outwards, so the
+    signed volume is well defined and positive):
+        l_vol = mean_b (vol(out) - vol(ref))^2;   l_area = mean_b (area(out) - area(ref))^2       absolute: the data are normalised
+        loss += factor_volume * l_vol + factor_area * l_area                                       to the unit sphere
+    The gradient to the output runs through icn_mesh_measure_bwd, one gather over the vertex -> corner incidence table of the ico
+    faces (a buffer built at construction), O(F) per mesh, fixed order, no atomics.  The terms need no samples (they work with
+    samples = 0), draw no random numbers and never synchronise the host; a term is evaluated only when its factor is non-zero.
+    last_volume / last_area hold l_vol / l_area (device tensors; 0 while the term is off), get_last_losses() keeps its five-tuple.
+    With both factors 0 (the default) nothing new is launched and the loss is bit for bit what it was.
+    Cost on an MI355X at I5 / batch 36 (HIP events, median of 10, profiles/mesh_measure.txt, from `python tools/time_mesh_measure.py
+    10`): k_mesh_measure_face 0.008 ms, k_mesh_measure_finish 0.007 ms, k_mesh_measure_bwd 0.017 ms -- the incidence gather
+    against 1.04 ms (k_msample_bwd_vertex) and 2.04 ms per side (k_fnormal_agree_bwd_vertex) for the record scatters above, whose callers
+    could move to the same table.  Through autograd the HIP path takes 0.04 ms forward and 0.34 ms forward + backward (the three kernels
+    are 0.03 ms of that; the rest is launch and autograd overhead on the host, 0.22 ms in another run) against 0.43 / 3.3 ms (1.87 ms in
+    that other run) for the torch formulation on the device: 10 x either way; building the table on demand instead adds 0.10 - 0.13 ms
+    per backward.  This whole term, forward + backward, search='grid': samples = 0 6.07 -> 6.14 ms, samples = 10 242 7.83 -> 7.98 ms with
+    both factors."""
 
     def __init__(self, subdivisions, factor_p2m=1.0, factor_m2p=1.0, factor_edge=0.0, factor_ncons=0.0, factor_smooth=0.0,
-                 edge_length=0.0, search='brute', samples=0, sample_seed=0, factor_normal=0.0, normal_oriented=True):
+                 edge_length=0.0, search='brute', samples=0, sample_seed=0, factor_normal=0.0, normal_oriented=True,
+                 factor_volume=0.0, factor_area=0.0):
         super().__init__()
         from .metrics import _check_search
         _check_search(search)
         _check_subdivisions('Surface_Loss', subdivisions)
-        _check_factors('Surface_Loss', factor_p2m=factor_p2m, factor_m2p=factor_m2p, factor_normal=factor_normal)
+        _check_factors('Surface_Loss', factor_p2m=factor_p2m, factor_m2p=factor_m2p, factor_normal=factor_normal,
+                       factor_volume=factor_volume, factor_area=factor_area)
         if isinstance(samples, bool) or not isinstance(samples, int) or samples < 0:
             raise ValueError('%s: samples must be a non-negative integer, got %r' % (type(self).__name__, samples))
         if isinstance(sample_seed, bool) or not isinstance(sample_seed, int):
@@ -478,6 +501,7 @@ class Surface_Loss(torch.nn.Module):
             raise ValueError('%s: normal_oriented must be a bool, got %r' % (type(self).__name__, normal_oriented))
         self.samples, self.sample_seed, self._sample_generator = samples, sample_seed, None
         self.factor_normal, self.normal_oriented = factor_normal, normal_oriented
+        self.factor_volume, self.factor_area = factor_volume, factor_area
         self.subdivisions, self.search = subdivisions, search
         self.factor_p2m, self.factor_m2p = factor_p2m, factor_m2p
         self.regularizer = Mesh_Regularizer(subdivisions, factor_edge, factor_ncons, factor_smooth, edge_length)
@@ -486,7 +510,14 @@ class Surface_Loss(torch.nn.Module):
         if faces.ndim != 2 or faces.shape[1] != 3 or faces.min() < 0 or faces.max() >= nv:
             raise ValueError('Surface_Loss: the face table does not index %d vertices' % nv)
         self.register_buffer('ico_faces', torch.from_numpy(faces).to(torch.int32))
+        # vertex -> corner incidence table of the ico faces (the gather of icn_mesh_measure_bwd); derived from the subdivisions, so
+        # not part of state_dict
+        from .metrics import vertex_face_table
+        offsets, corners = vertex_face_table(self.ico_faces, nv)
+        self.register_buffer('ico_vf_offsets', offsets, persistent=False)
+        self.register_buffer('ico_vf_corners', corners, persistent=False)
         self.last_p2m = self.last_m2p = self.last_reg = self.last_loss_total = self.last_normal = 0
+        self.last_volume = self.last_area = 0
 
     def _draw_uniforms(self, B, device):
         """The (2, B, S, 3) uniforms of one forward, from the generator seeded with sample_seed on the first forward's device."""
@@ -531,6 +562,21 @@ class Surface_Loss(torch.nn.Module):
             self.last_normal = l_n.detach()
         else:
             self.last_normal = 0                                              # (not a tensor: the default path launches nothing new)
+        self.last_volume = self.last_area = 0
+        if self.factor_volume != 0 or self.factor_area != 0:                  # one forward serves both; a backward term per factor
+            from .metrics import _mesh_area_volume_unchecked
+            table = tuple(t if t.device == out.device else t.to(out.device) for t in (self.ico_vf_offsets, self.ico_vf_corners))
+            area_out, vol_out = _mesh_area_volume_unchecked(out, faces, table)
+            with torch.no_grad():
+                area_ref, vol_ref = _mesh_area_volume_unchecked(ref, faces)
+            if self.factor_volume != 0:
+                l_vol = ((vol_out - vol_ref) ** 2).mean()
+                loss = loss + self.factor_volume * l_vol
+                self.last_volume = l_vol.detach()
+            if self.factor_area != 0:
+                l_area = ((area_out - area_ref) ** 2).mean()
+                loss = loss + self.factor_area * l_area
+                self.last_area = l_area.detach()
         self.last_p2m, self.last_m2p, self.last_reg = l_p2m.detach(), l_m2p.detach(), l_reg.detach()
         self.last_loss_total = loss.detach()
         return loss
@@ -591,9 +637,11 @@ class SurfaceKLD_Loss(Surface_Loss, KLD_Loss):
     """Surface_Loss of the reconstruction + factor_kl * KLD, for (recon, mu, logvar) outputs -- as P2PKLD_Loss is to P2P_Loss."""
 
     def __init__(self, subdivisions, factor_p2m=1.0, factor_m2p=1.0, factor_edge=0.0, factor_ncons=0.0, factor_smooth=0.0,
-                 edge_length=0.0, search='brute', factor_kl=1.0, samples=0, sample_seed=0, factor_normal=0.0, normal_oriented=True):
+                 edge_length=0.0, search='brute', factor_kl=1.0, samples=0, sample_seed=0, factor_normal=0.0, normal_oriented=True,
+                 factor_volume=0.0, factor_area=0.0):
         super().__init__(subdivisions, factor_p2m, factor_m2p, factor_edge, factor_ncons, factor_smooth, edge_length, search,
-                         samples=samples, sample_seed=sample_seed, factor_normal=factor_normal, normal_oriented=normal_oriented)
+                         samples=samples, sample_seed=sample_seed, factor_normal=factor_normal, normal_oriented=normal_oriented,
+                         factor_volume=factor_volume, factor_area=factor_area)
         _check_factors('SurfaceKLD_Loss', factor_kl=factor_kl)
         self.factor_kl = factor_kl
 
