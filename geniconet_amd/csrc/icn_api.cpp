@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/icn_ext.h"
+#include "../../include/icn_curvature.h"
 #include "../../include/icn_measure.h"
 #include "icn_geometry.h"
 #include "icn_launch.h"
@@ -788,7 +789,8 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_msample_bwd_vertex",
                                             "k_fnormal_agree", "k_fnormal_agree_bwd_record",
                                             "k_fnormal_agree_bwd_vertex",    // every ..._bwd_vertex: k_vertex_scatter, by its caller
-                                            "k_mesh_measure_face", "k_mesh_measure_finish", "k_mesh_measure_bwd"};
+                                            "k_mesh_measure_face", "k_mesh_measure_finish", "k_mesh_measure_bwd",
+                                            "k_mesh_cotlap_fwd", "k_mesh_willmore_finish", "k_mesh_willmore_upstream", "k_mesh_cotlap_bwd"};
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1472,6 +1474,56 @@ int icn_mesh_measure_bwd(const float* vertices, const int32_t* faces, const int3
         if (!vertices || !faces || !vf_offsets || !vf_corners || !dvertices) throw std::invalid_argument("icn_mesh_measure_bwd: null pointer");
         check_measure_sizes("icn_mesh_measure_bwd", B, V, F);
         icn::launch_mesh_measure_bwd(vertices, faces, vf_offsets, vf_corners, darea, dvolume, B, V, F, dvertices, s);
+    });
+}
+
+// ---- cotangent Laplacian and Willmore energy (include/icn_curvature.h): the sizes of the measure entries ------------------------
+size_t icn_mesh_willmore_workspace_bytes(int B, int V, int F) {
+    return measure_sizes_ok(B, V, F) ? icn::mesh_willmore_bytes(B, V) : 0;
+}
+
+int icn_mesh_cotlap_fwd(const float* vertices, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_corners, int B, int V,
+                        int F, float* lap, float* varea, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!vertices || !faces || !vf_offsets || !vf_corners || !lap || !varea) throw std::invalid_argument("icn_mesh_cotlap_fwd: null pointer");
+        check_measure_sizes("icn_mesh_cotlap_fwd", B, V, F);
+        icn::launch_mesh_cotlap_fwd(vertices, faces, vf_offsets, vf_corners, B, V, F, lap, varea, s);
+    });
+}
+
+int icn_mesh_cotlap_bwd(const float* vertices, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_corners,
+                        const float* dlap, const float* dvarea, int B, int V, int F, float* dvertices, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!vertices || !faces || !vf_offsets || !vf_corners || !dvertices) throw std::invalid_argument("icn_mesh_cotlap_bwd: null pointer");
+        check_measure_sizes("icn_mesh_cotlap_bwd", B, V, F);
+        icn::launch_mesh_cotlap_bwd(vertices, faces, vf_offsets, vf_corners, dlap, dvarea, B, V, F, dvertices, s);
+    });
+}
+
+int icn_mesh_willmore_fwd(const float* vertices, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_corners, int B, int V,
+                          int F, float* lap, float* varea, float* energy, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!vertices || !faces || !vf_offsets || !vf_corners || !lap || !varea || !energy)
+            throw std::invalid_argument("icn_mesh_willmore_fwd: null pointer");
+        check_measure_sizes("icn_mesh_willmore_fwd", B, V, F);
+        check_workspace("icn_mesh_willmore_fwd", ws, ws_bytes, icn::mesh_willmore_bytes(B, V));
+        icn::launch_mesh_willmore_fwd(vertices, faces, vf_offsets, vf_corners, B, V, F, lap, varea, energy, ws, s);
+    });
+}
+
+int icn_mesh_willmore_bwd(const float* vertices, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_corners,
+                          const float* lap, const float* varea, const float* denergy, int B, int V, int F, float* dvertices, void* ws,
+                          size_t ws_bytes, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!vertices || !faces || !vf_offsets || !vf_corners || !lap || !varea || !denergy || !dvertices)
+            throw std::invalid_argument("icn_mesh_willmore_bwd: null pointer");
+        check_measure_sizes("icn_mesh_willmore_bwd", B, V, F);
+        check_workspace("icn_mesh_willmore_bwd", ws, ws_bytes, icn::mesh_willmore_bytes(B, V));
+        icn::launch_mesh_willmore_bwd(vertices, faces, vf_offsets, vf_corners, lap, varea, denergy, B, V, F, dvertices, ws, s);
     });
 }
 

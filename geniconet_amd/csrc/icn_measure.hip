@@ -34,15 +34,8 @@ namespace {
 constexpr int MEASURE_PER_THREAD = 4;
 constexpr int MEASURE_SPAN = MESH_BLOCK * MEASURE_PER_THREAD;                // faces of one block: 1024
 
-__device__ __forceinline__ bool ids_ok(int i0, int i1, int i2, int V) {
-    return i0 >= 0 && i0 < V && i1 >= 0 && i1 < V && i2 >= 0 && i2 < V;
-}
-
-__device__ __forceinline__ float norm2(f3 n) { return fmaf(n.z, n.z, fmaf(n.x, n.x, n.y * n.y)); }
-
 __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_measure_face(const float* __restrict__ vts, const int32_t* __restrict__ faces, int V,
                                                                    int F, double* __restrict__ partial) {
-    __shared__ double red[2][MESH_BLOCK / 64];
     const int b = blockIdx.y;
     const float* v = vts + (size_t)b * V * 3;
     const f3 o = load3(v);                                                   // vertex 0 (V >= 1)
@@ -57,46 +50,17 @@ __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_measure_face(const float* _
         area += (double)(0.5f * sqrtf(norm2(face_normal(p1 - p0, p2 - p0))));
         trip += (double)dot(p0 - o, cross(p1 - o, p2 - o));
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        area += __shfl_xor(area, d, 64);
-        trip += __shfl_xor(trip, d, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = area;
-        red[1][threadIdx.x >> 6] = trip;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double* out = partial + ((size_t)b * gridDim.x + blockIdx.x) * 2;
-        out[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        out[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    }
+    double sums[2] = {area, trip};
+    block_sum_store(sums, partial + ((size_t)b * gridDim.x + blockIdx.x) * 2);
 }
 
 __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_measure_finish(const double* __restrict__ partial, int nblocks,
                                                                      float* __restrict__ area, float* __restrict__ volume) {
-    __shared__ double red[2][MESH_BLOCK];
-    const int b = blockIdx.x;
-    const double* p = partial + (size_t)b * nblocks * 2;
-    double a = 0.0, t = 0.0;
-    for (int k = threadIdx.x; k < nblocks; k += MESH_BLOCK) {
-        a += p[(size_t)k * 2];
-        t += p[(size_t)k * 2 + 1];
-    }
-    red[0][threadIdx.x] = a;
-    red[1][threadIdx.x] = t;
-    __syncthreads();
-    for (int d = MESH_BLOCK / 2; d >= 1; d >>= 1) {
-        if ((int)threadIdx.x < d) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + d];
-            red[1][threadIdx.x] += red[1][threadIdx.x + d];
-        }
-        __syncthreads();
-    }
+    double sums[2];
+    partials_sum(partial + (size_t)blockIdx.x * nblocks * 2, nblocks, sums);
     if (threadIdx.x == 0) {
-        area[b] = (float)red[0][0];
-        volume[b] = (float)(red[1][0] / 6.0);
+        area[blockIdx.x] = (float)sums[0];
+        volume[blockIdx.x] = (float)(sums[1] / 6.0);
     }
 }
 

@@ -1,4 +1,4 @@
-// Device code shared by the mesh kernels of icn_loss.hip and icn_sample.hip: 3-vectors, the pixel <-> vertex rule of the
+// Device code shared by the mesh kernels of icn_loss.hip, icn_sample.hip, icn_measure.hip and icn_curvature.hip: 3-vectors, the pixel <-> vertex rule of the
 // icosahedral grid, fixed-order block reductions, the tiled block scan and the per-record vertex scatter's record set.
 // Everything here is inlined into its callers; every sum has a fixed order (bit-identical run to run).
 #pragma once
@@ -26,6 +26,12 @@ __device__ __forceinline__ f3 load3(const float* __restrict__ p) { return {p[0],
 __device__ __forceinline__ f3 face_normal(f3 a, f3 b) {
 #pragma clang fp contract(off)
     return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+
+// |n|^2 of a face normal, and whether the three vertex ids of a face index V vertices (a face that fails takes no part in anything)
+__device__ __forceinline__ float norm2(f3 n) { return fmaf(n.z, n.z, fmaf(n.x, n.x, n.y * n.y)); }
+__device__ __forceinline__ bool ids_ok(int i0, int i1, int i2, int V) {
+    return i0 >= 0 && i0 < V && i1 >= 0 && i1 < V && i2 >= 0 && i2 < V;
 }
 
 // ---- pixels and vertices of the icosahedral grid (n = 2^r) ------------------------------------------------------------------
@@ -69,10 +75,10 @@ __device__ __forceinline__ void store_pixel_grad(float* __restrict__ dg, int b, 
 
 // ---- reductions -------------------------------------------------------------------------------------------------------------
 // Block sum of N values per thread in a fixed order (xor shuffles inside a wave, then a tree over the 4 wave totals);
-// thread 0 stores the N sums to out.  Every thread of the block calls it.
-template <int N>
-__device__ __forceinline__ void block_sum_store(float (&v)[N], float* __restrict__ out) {
-    __shared__ float red[N][MESH_BLOCK / 64];
+// thread 0 stores the N sums to out.  Every thread of the block calls it.  T: float or double.
+template <int N, typename T>
+__device__ __forceinline__ void block_sum_store(T (&v)[N], T* __restrict__ out) {
+    __shared__ T red[N][MESH_BLOCK / 64];
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1)
 #pragma unroll
@@ -86,10 +92,10 @@ __device__ __forceinline__ void block_sum_store(float (&v)[N], float* __restrict
         for (int c = 0; c < N; ++c) out[c] = (red[c][0] + red[c][1]) + (red[c][2] + red[c][3]);
 }
 
-// Second level: one block sums nblocks rows of N partials in double (lanes stride over the rows, then a fixed tree); the N
-// sums are valid in thread 0.
-template <int N>
-__device__ __forceinline__ void partials_sum(const float* __restrict__ partial, int nblocks, double (&s)[N]) {
+// Second level: one block sums nblocks rows of N partials (float or double) in double (lanes stride over the rows, then a fixed
+// tree); the N sums are valid in thread 0.
+template <int N, typename T>
+__device__ __forceinline__ void partials_sum(const T* __restrict__ partial, int nblocks, double (&s)[N]) {
     __shared__ double red[N][MESH_BLOCK];
     for (int c = 0; c < N; ++c) s[c] = 0.0;
     for (int k = threadIdx.x; k < nblocks; k += MESH_BLOCK)

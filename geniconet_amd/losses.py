@@ -21,7 +21,8 @@ Point2Mesh_Loss is not in the reference: the surface distance it reports at test
 Surface_Loss / SurfaceKLD_Loss (train.build_criterion: 'surface' / 'surfacekld') make a training criterion of it: the distance in
 both directions plus Mesh_Regularizer (edge length, normal consistency, Laplacian smoothness; HIP kernels icn_mesh_reg_*); from
 surface samples (samples > 0) optionally with the normal agreement of the two surfaces (factor_normal; icn_face_normal_agree_*),
-and optionally with the enclosed volume and the surface area held to the target's (factor_volume / factor_area; icn_mesh_measure_*).
+and optionally with the enclosed volume and the surface area held to the target's (factor_volume / factor_area; icn_mesh_measure_*)
+and with the Willmore bending energy of the output (factor_willmore; icn_mesh_willmore_*), the smoothness term that does not shrink.
 """
 import math
 import os
@@ -479,17 +480,35 @@ class Surface_Loss(torch.nn.Module):
     are 0.03 ms of that; the rest is launch and autograd overhead on the host, 0.22 ms in another run) against 0.43 / 3.3 ms (1.87 ms in
     that other run) for the torch formulation on the device: 10 x either way; building the table on demand instead adds 0.10 - 0.13 ms
     per backward.  This whole term, forward + backward, search='grid': samples = 0 6.07 -> 6.14 ms, samples = 10 242 7.83 -> 7.98 ms with
-    both factors."""
+    both factors.
+
+    factor_willmore != 0 adds the remedy for the cause: a smoothness measure that is geometric -- weighted by the triangles, not by
+    vertex valence -- and that does not shrink the mesh.  W = metrics.willmore_energy(out, ico_faces) is the discrete integral of
+    H^2 from the cotangent Laplace-Beltrami operator (metrics.cotangent_laplacian): invariant under scaling, rotation and
+    translation, 4 pi for a sphere of any radius, so it cannot be lowered by shrinking and does not drag vertices tangentially the
+    way the umbrella of factor_smooth does:
+        loss += factor_willmore * mean_b W(out mesh)
+    The gradient to the output runs through icn_mesh_willmore_bwd over the same incidence table (the ico_vf_* buffers).  The term
+    needs no samples, draws no random numbers and never synchronises the host; last_willmore holds mean_b W (a device tensor; 0
+    while the term is off), get_last_losses() keeps its five-tuple and state_dict is unchanged.  With the factor 0 (the default)
+    nothing new is launched and the loss is bit for bit what it was.
+    Cost on an MI355X at I5 / batch 36 (HIP events, median of 10, profiles/mesh_curvature.txt, from `python
+    tools/time_mesh_curvature.py 10`): k_mesh_cotlap_fwd 0.018 ms, k_mesh_willmore_finish 0.007 ms, k_mesh_willmore_upstream
+    0.007 ms, k_mesh_cotlap_bwd 0.026 ms.  Through autograd the HIP path takes 0.04 ms forward and 0.21 ms forward + backward
+    (the four kernels are 0.06 ms of that; the rest is launch and autograd overhead on the host) against 0.80 / 2.6 ms for the
+    torch formulation on the device: 21 x and 13 x, and here the fixed-order HIP backward does beat torch's atomic index_add.
+    Building the table on entry instead adds 0.12 ms.  This whole term, forward + backward, search='grid': samples = 0
+    6.01 -> 6.01 ms, samples = 10 242 7.75 -> 7.81 ms with the factor."""
 
     def __init__(self, subdivisions, factor_p2m=1.0, factor_m2p=1.0, factor_edge=0.0, factor_ncons=0.0, factor_smooth=0.0,
                  edge_length=0.0, search='brute', samples=0, sample_seed=0, factor_normal=0.0, normal_oriented=True,
-                 factor_volume=0.0, factor_area=0.0):
+                 factor_volume=0.0, factor_area=0.0, factor_willmore=0.0):
         super().__init__()
         from .metrics import _check_search
         _check_search(search)
         _check_subdivisions('Surface_Loss', subdivisions)
         _check_factors('Surface_Loss', factor_p2m=factor_p2m, factor_m2p=factor_m2p, factor_normal=factor_normal,
-                       factor_volume=factor_volume, factor_area=factor_area)
+                       factor_volume=factor_volume, factor_area=factor_area, factor_willmore=factor_willmore)
         if isinstance(samples, bool) or not isinstance(samples, int) or samples < 0:
             raise ValueError('%s: samples must be a non-negative integer, got %r' % (type(self).__name__, samples))
         if isinstance(sample_seed, bool) or not isinstance(sample_seed, int):
@@ -502,6 +521,7 @@ class Surface_Loss(torch.nn.Module):
         self.samples, self.sample_seed, self._sample_generator = samples, sample_seed, None
         self.factor_normal, self.normal_oriented = factor_normal, normal_oriented
         self.factor_volume, self.factor_area = factor_volume, factor_area
+        self.factor_willmore = factor_willmore
         self.subdivisions, self.search = subdivisions, search
         self.factor_p2m, self.factor_m2p = factor_p2m, factor_m2p
         self.regularizer = Mesh_Regularizer(subdivisions, factor_edge, factor_ncons, factor_smooth, edge_length)
@@ -510,14 +530,14 @@ class Surface_Loss(torch.nn.Module):
         if faces.ndim != 2 or faces.shape[1] != 3 or faces.min() < 0 or faces.max() >= nv:
             raise ValueError('Surface_Loss: the face table does not index %d vertices' % nv)
         self.register_buffer('ico_faces', torch.from_numpy(faces).to(torch.int32))
-        # vertex -> corner incidence table of the ico faces (the gather of icn_mesh_measure_bwd); derived from the subdivisions, so
+        # vertex -> corner incidence table of the ico faces (the gather of icn_mesh_measure_bwd and icn_mesh_willmore_*); derived from the subdivisions, so
         # not part of state_dict
         from .metrics import vertex_face_table
         offsets, corners = vertex_face_table(self.ico_faces, nv)
         self.register_buffer('ico_vf_offsets', offsets, persistent=False)
         self.register_buffer('ico_vf_corners', corners, persistent=False)
         self.last_p2m = self.last_m2p = self.last_reg = self.last_loss_total = self.last_normal = 0
-        self.last_volume = self.last_area = 0
+        self.last_volume = self.last_area = self.last_willmore = 0
 
     def _draw_uniforms(self, B, device):
         """The (2, B, S, 3) uniforms of one forward, from the generator seeded with sample_seed on the first forward's device."""
@@ -577,6 +597,13 @@ class Surface_Loss(torch.nn.Module):
                 l_area = ((area_out - area_ref) ** 2).mean()
                 loss = loss + self.factor_area * l_area
                 self.last_area = l_area.detach()
+        self.last_willmore = 0
+        if self.factor_willmore != 0:
+            from .metrics import _willmore_energy_unchecked
+            table = tuple(t if t.device == out.device else t.to(out.device) for t in (self.ico_vf_offsets, self.ico_vf_corners))
+            l_w = _willmore_energy_unchecked(out, faces, table).mean()
+            loss = loss + self.factor_willmore * l_w
+            self.last_willmore = l_w.detach()
         self.last_p2m, self.last_m2p, self.last_reg = l_p2m.detach(), l_m2p.detach(), l_reg.detach()
         self.last_loss_total = loss.detach()
         return loss
@@ -638,10 +665,10 @@ class SurfaceKLD_Loss(Surface_Loss, KLD_Loss):
 
     def __init__(self, subdivisions, factor_p2m=1.0, factor_m2p=1.0, factor_edge=0.0, factor_ncons=0.0, factor_smooth=0.0,
                  edge_length=0.0, search='brute', factor_kl=1.0, samples=0, sample_seed=0, factor_normal=0.0, normal_oriented=True,
-                 factor_volume=0.0, factor_area=0.0):
+                 factor_volume=0.0, factor_area=0.0, factor_willmore=0.0):
         super().__init__(subdivisions, factor_p2m, factor_m2p, factor_edge, factor_ncons, factor_smooth, edge_length, search,
                          samples=samples, sample_seed=sample_seed, factor_normal=factor_normal, normal_oriented=normal_oriented,
-                         factor_volume=factor_volume, factor_area=factor_area)
+                         factor_volume=factor_volume, factor_area=factor_area, factor_willmore=factor_willmore)
         _check_factors('SurfaceKLD_Loss', factor_kl=factor_kl)
         self.factor_kl = factor_kl
 

@@ -36,6 +36,11 @@ the closest face of the other mesh, `face` of sampling.sample_points and of poin
 mesh_area_volume (below) gives the surface area and the enclosed volume of every mesh of a batch, differentiable in the vertices
 (icn_mesh_measure_fwd / _bwd, include/icn_measure.h; the backward gathers over vertex_face_table, the vertex -> corner incidence
 table of the face list); volume_error is the relative volume error of one mesh pair, to stand beside compute_distance.
+
+cotangent_laplacian and willmore_energy (below) give the integrated cotangent Laplace-Beltrami operator with the barycentric vertex
+areas, and the Willmore bending energy (the integral of H^2) of every mesh of a batch, differentiable in the vertices
+(icn_mesh_cotlap_* / icn_mesh_willmore_*, include/icn_curvature.h; every kernel gathers over vertex_face_table): the smoothness
+measure that is geometric and scale invariant, where the uniform umbrella of losses.Mesh_Regularizer shrinks the mesh.
 """
 import torch
 
@@ -536,6 +541,224 @@ def volume_error(outvertices, refvertices, faces):
     vol_out = mesh_area_volume(outvertices[None], faces)[1]
     vol_ref = mesh_area_volume(refvertices[None], faces)[1]
     return float((vol_out - vol_ref).abs() / vol_ref.abs())
+
+
+# ---- cotangent Laplacian and Willmore bending energy ------------------------------------------------------------------------------
+def _torch_cotangent_laplacian(vertices, faces):
+    """The definition of cotangent_laplacian in torch, differentiable in the vertices through autograd: (lap (B, V, 3), varea (B, V))
+    in the vertices' dtype."""
+    from .losses import Mesh_Regularizer
+    V = vertices.shape[1]
+    ids = faces.long()
+    ok = ((ids >= 0) & (ids < V)).all(-1)                                                 # (F,): the others take no part
+    ids = ids.clamp(0, V - 1)
+    tri = vertices[:, ids]                                                                # (B, F, 3 corners, 3)
+    with torch.no_grad():
+        nn = (Mesh_Regularizer._face_normal(tri[:, :, 1] - tri[:, :, 0], tri[:, :, 2] - tri[:, :, 0]) ** 2).sum(-1)
+        flat = ~((nn > 0) & torch.isfinite(nn)) | ~ok                                     # unresolved: nothing to lap, the subgradient 0
+        a_flat = torch.where(ok, 0.5 * nn.sqrt(), torch.zeros_like(nn))                   # ... and its area all the same (NaN stays NaN)
+    # an unresolved face enters autograd as a zero triangle: its vertices meet no arithmetic that autograd records
+    tri = torch.where(flat[..., None, None], torch.zeros_like(tri), tri)
+    p = [tri[:, :, k] for k in range(3)]
+    n = Mesh_Regularizer._face_normal(p[1] - p[0], p[2] - p[0])
+    length = torch.where(flat, torch.ones_like(nn), (n * n).sum(-1)).sqrt()
+    unit = n / length[..., None]                                                          # 0 for a zero triangle
+    a = torch.where(flat, a_flat, 0.5 * length)
+    lap = torch.zeros_like(vertices)
+    varea = torch.zeros_like(vertices[..., 0])
+    for k in range(3):
+        lap = lap.index_add(1, ids[:, k], -0.5 * Mesh_Regularizer._face_normal(unit, p[(k + 2) % 3] - p[(k + 1) % 3]))
+        varea = varea.index_add(1, ids[:, k], a)
+    return lap, varea / 3
+
+
+def _willmore_from(lap, varea):
+    """energy (B,) = sum_i |lap_i|^2 / (4 varea_i) over the vertices with varea_i != 0, summed in float64; no gradient passes through
+    the others."""
+    has = varea != 0                                                                      # NaN counts: it propagates
+    lap = torch.where(has[..., None], lap, torch.zeros_like(lap))
+    w = (lap * lap).sum(-1) / (4 * torch.where(has, varea, torch.ones_like(varea)))
+    return w.double().sum(1).to(lap.dtype)
+
+
+def _torch_willmore_energy(vertices, faces):
+    """The definition of willmore_energy in torch, differentiable in the vertices through autograd."""
+    return _willmore_from(*_torch_cotangent_laplacian(vertices, faces))
+
+
+def _hip_curvature(vts, f32, offsets, corners, energy):
+    """icn_mesh_cotlap_fwd (energy False) or icn_mesh_willmore_fwd on contiguous fp32 ROCm vertices, an int32 face table and its
+    incidence table -> (lap (B, V, 3), varea (B, V), energy (B,) or None)."""
+    L = _lib.api()
+    B, V, F = vts.shape[0], vts.shape[1], f32.shape[0]
+    lap = torch.empty_like(vts)
+    varea = torch.empty(B, V, dtype=torch.float32, device=vts.device)
+    tables = (f32.data_ptr(), offsets.data_ptr(), corners.data_ptr())
+    with torch.cuda.device(vts.device):
+        if not energy:
+            for b0, nb in _batch_slices(B):
+                L.icn_mesh_cotlap_fwd(vts[b0:].data_ptr(), *tables, nb, V, F, lap[b0:].data_ptr(), varea[b0:].data_ptr(), _lib.stream())
+            return lap, varea, None
+        out = torch.empty(B, dtype=torch.float32, device=vts.device)
+        ws_bytes = L.icn_mesh_willmore_workspace_bytes(min(B, _MAX_GRID_Y), V, F)
+        ws = _lib.workspace(ws_bytes, vts.device)
+        for b0, nb in _batch_slices(B):
+            L.icn_mesh_willmore_fwd(vts[b0:].data_ptr(), *tables, nb, V, F, lap[b0:].data_ptr(), varea[b0:].data_ptr(),
+                                    out[b0:].data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream())
+    return lap, varea, out
+
+
+class _CotLapFn(torch.autograd.Function):
+    """cotangent_laplacian on the HIP path (icn_mesh_cotlap_fwd / _bwd in include/icn_curvature.h): both directions are one gather
+    over the vertex -> corner incidence table, summed in a fixed order: bit-identical run to run.  An output nobody differentiates
+    sends no gradient and its term is skipped; with neither nothing is launched."""
+
+    @staticmethod
+    def forward(ctx, vertices, f32, offsets, corners):
+        vts = vertices.contiguous()
+        ctx.save_for_backward(vts, f32, offsets, corners)
+        ctx.set_materialize_grads(False)
+        return _hip_curvature(vts, f32, offsets, corners, False)[:2]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dlap, dvarea):
+        if dlap is None and dvarea is None:
+            return None, None, None, None
+        L = _lib.api()
+        vts, f32, offsets, corners = ctx.saved_tensors
+        B, V, F = vts.shape[0], vts.shape[1], f32.shape[0]
+        dl = dlap.contiguous().to(torch.float32) if dlap is not None else None
+        da = dvarea.contiguous().to(torch.float32) if dvarea is not None else None
+        dvts = torch.empty_like(vts)
+        with torch.cuda.device(vts.device):
+            for b0, nb in _batch_slices(B):
+                L.icn_mesh_cotlap_bwd(vts[b0:].data_ptr(), f32.data_ptr(), offsets.data_ptr(), corners.data_ptr(),
+                                      dl[b0:].data_ptr() if dl is not None else None,
+                                      da[b0:].data_ptr() if da is not None else None, nb, V, F, dvts[b0:].data_ptr(), _lib.stream())
+        return dvts, None, None, None
+
+
+class _WillmoreFn(torch.autograd.Function):
+    """willmore_energy on the HIP path (icn_mesh_willmore_fwd / _bwd in include/icn_curvature.h).  The forward keeps lap and varea for
+    the backward: the per-vertex upstreams, then the gather of icn_mesh_cotlap_bwd; a fixed order, bit-identical run to run."""
+
+    @staticmethod
+    def forward(ctx, vertices, f32, offsets, corners):
+        vts = vertices.contiguous()
+        lap, varea, energy = _hip_curvature(vts, f32, offsets, corners, True)
+        ctx.save_for_backward(vts, f32, offsets, corners, lap, varea)
+        ctx.set_materialize_grads(False)
+        return energy
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, denergy):
+        if denergy is None:
+            return None, None, None, None
+        L = _lib.api()
+        vts, f32, offsets, corners, lap, varea = ctx.saved_tensors
+        B, V, F = vts.shape[0], vts.shape[1], f32.shape[0]
+        de = denergy.contiguous().to(torch.float32)
+        dvts = torch.empty_like(vts)
+        ws_bytes = L.icn_mesh_willmore_workspace_bytes(min(B, _MAX_GRID_Y), V, F)
+        ws = _lib.workspace(ws_bytes, vts.device)
+        with torch.cuda.device(vts.device):
+            for b0, nb in _batch_slices(B):
+                L.icn_mesh_willmore_bwd(vts[b0:].data_ptr(), f32.data_ptr(), offsets.data_ptr(), corners.data_ptr(), lap[b0:].data_ptr(),
+                                        varea[b0:].data_ptr(), de[b0:].data_ptr(), nb, V, F, dvts[b0:].data_ptr(), ws.data_ptr(),
+                                        ws_bytes, _lib.stream())
+        return dvts, None, None, None
+
+
+def _on_hip_path(vertices):
+    from . import losses
+    return not losses._NO_HIP_LOSS and vertices.is_cuda and vertices.dtype == torch.float32
+
+
+def _cotangent_laplacian_unchecked(vertices, f32, table=None):
+    """cotangent_laplacian without its argument checks and without a host synchronisation, for callers that validated once: f32 is an
+    int32 (F, 3) tensor on the vertices' device, F >= 1; table = vertex_face_table(f32, V) on that device, or None (built here: the
+    forward gathers over it too).  A vertex id out of range is safe on either path: that face takes no part."""
+    if _on_hip_path(vertices):
+        offsets, corners = table if table is not None else vertex_face_table(f32, vertices.shape[1])
+        if torch.is_grad_enabled() and vertices.requires_grad:
+            return _CotLapFn.apply(vertices, f32, offsets, corners)
+        return _hip_curvature(vertices.detach().contiguous(), f32, offsets, corners, False)[:2]
+    return _torch_cotangent_laplacian(vertices, f32)
+
+
+def _willmore_energy_unchecked(vertices, f32, table=None):
+    """willmore_energy without its argument checks and without a host synchronisation (losses.Surface_Loss); arguments as
+    _cotangent_laplacian_unchecked."""
+    if _on_hip_path(vertices):
+        offsets, corners = table if table is not None else vertex_face_table(f32, vertices.shape[1])
+        if torch.is_grad_enabled() and vertices.requires_grad:
+            return _WillmoreFn.apply(vertices, f32, offsets, corners)
+        return _hip_curvature(vertices.detach().contiguous(), f32, offsets, corners, True)[2]
+    return _torch_willmore_energy(vertices, f32)
+
+
+def _check_mesh_arguments(who, vertices, faces, table):
+    """The argument checks of mesh_area_volume for `who`: shapes (ValueError), face ids against V with one read-back (IndexError), the
+    table's shapes -> (int32 faces on the vertices' device, the table there or None)."""
+    if vertices.dim() != 3 or vertices.shape[-1] != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1 or not vertices.is_floating_point():
+        raise ValueError('%s: expected floating-point vertices (B, V, 3), got %s' % (who, tuple(vertices.shape)))
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1 or faces.is_floating_point() or faces.dtype == torch.bool:
+        raise ValueError('%s: expected integer faces (F, 3) with F >= 1, got %s' % (who, tuple(faces.shape)))
+    V, F = vertices.shape[1], faces.shape[0]
+    if 3 * F > 0x7fffffff:
+        raise ValueError('%s: %d faces: 3 F must fit an int32' % (who, F))
+    dev = vertices.device
+    if table is not None:
+        if (not isinstance(table, (tuple, list)) or len(table) != 2 or any(not torch.is_tensor(x) or x.dtype != torch.int32 for x in table)
+                or tuple(table[0].shape) != (V + 1,) or tuple(table[1].shape) != (3 * F,)):
+            raise ValueError('%s: table must be vertex_face_table(faces, %d): int32 tensors (%d,) and (%d,)' % (who, V, V + 1, 3 * F))
+        table = tuple(x.to(dev).contiguous() for x in table)
+    f32 = faces.to(device=dev, dtype=torch.int32).contiguous()
+    lo, hi = (int(x) for x in f32.aminmax())
+    if lo < 0 or hi >= V:
+        raise IndexError('%s: faces index [%d, %d] but there are %d vertices' % (who, lo, hi, V))
+    return f32, table
+
+
+def cotangent_laplacian(vertices, faces, table=None):
+    """(lap (B, V, 3), varea (B, V)) of the triangle meshes vertices (B, V, 3), faces (F, 3) integer and shared by the batch: the
+    integrated cotangent Laplace-Beltrami operator and the barycentric vertex area -- the smoothness measure that is weighted by
+    the triangles, not by vertex valence, and that does not drag vertices tangentially the way the uniform umbrella does.
+
+    One definition for the HIP kernels (include/icn_curvature.h), the torch formulation and the tests.  For a face (i0, i1, i2):
+        n = (v1 - v0) x (v2 - v0) with every product of the cross product rounded on its own (as mesh_area_volume), A_f = 0.5 |n|;
+        the face is RESOLVED iff |n|^2 > 0 and |n|^2 is finite
+    and for a vertex i, with k the corner of f that sits at i and corner indices taken modulo 3:
+        varea_i = (sum_{f at i} A_f) / 3
+        lap_i   = - sum_{f at i, resolved} 0.5 n^_f x (v_{k+2} - v_{k+1}),   n^ = n / |n|
+    lap_i equals the textbook sum_j 0.5 (cot alpha_ij + cot beta_ij)(v_j - v_i) over the neighbours j of i, alpha and beta the two
+    angles opposite edge (i, j), because that sum is - d area / d v_i (both to 2e-16 in float64 on icospheres); the cross product
+    form divides by |n| only, never by a sine: a needle triangle costs one factor of its aspect ratio, no cotangent overflows.
+    lap_i = 2 varea_i H normal with H the mean curvature.  An unresolved face adds nothing to lap (and its area, exactly 0 for
+    coincident vertices, to varea); a vertex no face references has lap = 0 and varea = 0 exactly; non-finite vertices propagate.
+    Differentiable in the vertices; the gradient treats an unresolved face as the subgradient 0, through lap and through varea.
+    ROCm fp32 tensors run on icn_mesh_cotlap_fwd / _bwd, one thread per (mesh, vertex) gathering over `table` =
+    vertex_face_table(faces, V) in a fixed order without atomics (bit-identical run to run) -- pass the table when the face list is
+    reused, else it is built on entry: here the forward needs it too.  ICN_NO_HIP_LOSS=1, CPU tensors and other dtypes take the
+    torch formulation through autograd.
+    Shapes are checked (ValueError); face ids against V with one read-back (IndexError)."""
+    f32, table = _check_mesh_arguments('cotangent_laplacian', vertices, faces, table)
+    return _cotangent_laplacian_unchecked(vertices, f32, table)
+
+
+def willmore_energy(vertices, faces, table=None):
+    """W (B,) of the triangle meshes vertices (B, V, 3), faces (F, 3): the discrete Willmore bending energy, the integral of H^2,
+        w_i = |lap_i|^2 / (4 varea_i) where varea_i != 0, else 0 (and no gradient passes through vertex i);   W[b] = sum_i w_i
+    with (lap, varea) = cotangent_laplacian(vertices, faces): w_i = H^2 varea_i.  W is invariant under scaling, rotation and
+    translation and is 4 pi for a sphere of any radius (W / 4 pi of the unit icosphere: 0.762, 0.931, 0.982, 0.996 for 0 .. 3
+    subdivisions), so it cannot be lowered by shrinking the mesh -- the failure the edge, normal-consistency and umbrella
+    regularisers share.  Summed in double in a fixed order, the output has the vertices' dtype; non-finite vertices propagate.
+    Differentiable in the vertices.  ROCm fp32 tensors run on icn_mesh_willmore_fwd / _bwd (include/icn_curvature.h), which keep
+    lap and varea of the forward for the backward; paths, `table` and checks as cotangent_laplacian."""
+    f32, table = _check_mesh_arguments('willmore_energy', vertices, faces, table)
+    return _willmore_energy_unchecked(vertices, f32, table)
 
 
 def output2vertices(subdivisions, output):
