@@ -15,6 +15,7 @@
 
 #include "../../include/icn_ext.h"
 #include "../../include/icn_curvature.h"
+#include "../../include/icn_gauss.h"
 #include "../../include/icn_measure.h"
 #include "icn_geometry.h"
 #include "icn_launch.h"
@@ -790,7 +791,8 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_fnormal_agree", "k_fnormal_agree_bwd_record",
                                             "k_fnormal_agree_bwd_vertex",    // every ..._bwd_vertex: k_vertex_scatter, by its caller
                                             "k_mesh_measure_face", "k_mesh_measure_finish", "k_mesh_measure_bwd",
-                                            "k_mesh_cotlap_fwd", "k_mesh_willmore_finish", "k_mesh_willmore_upstream", "k_mesh_cotlap_bwd"};
+                                            "k_mesh_cotlap_fwd", "k_mesh_willmore_finish", "k_mesh_willmore_upstream", "k_mesh_cotlap_bwd",
+                                            "k_mesh_angle_defect_fwd", "k_mesh_angle_defect_bwd"};
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1524,6 +1526,28 @@ int icn_mesh_willmore_bwd(const float* vertices, const int32_t* faces, const int
         check_measure_sizes("icn_mesh_willmore_bwd", B, V, F);
         check_workspace("icn_mesh_willmore_bwd", ws, ws_bytes, icn::mesh_willmore_bytes(B, V));
         icn::launch_mesh_willmore_bwd(vertices, faces, vf_offsets, vf_corners, lap, varea, denergy, B, V, F, dvertices, ws, s);
+    });
+}
+
+// ---- angle defect, the integrated Gaussian curvature (include/icn_gauss.h): the sizes of the measure entries ------------------
+int icn_mesh_angle_defect_fwd(const float* vertices, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_corners, int B,
+                              int V, int F, float* defect, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!vertices || !faces || !vf_offsets || !vf_corners || !defect) throw std::invalid_argument("icn_mesh_angle_defect_fwd: null pointer");
+        check_measure_sizes("icn_mesh_angle_defect_fwd", B, V, F);
+        icn::launch_mesh_angle_defect_fwd(vertices, faces, vf_offsets, vf_corners, B, V, F, defect, s);
+    });
+}
+
+int icn_mesh_angle_defect_bwd(const float* vertices, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_corners,
+                              const float* ddefect, int B, int V, int F, float* dvertices, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!vertices || !faces || !vf_offsets || !vf_corners || !ddefect || !dvertices)
+            throw std::invalid_argument("icn_mesh_angle_defect_bwd: null pointer");
+        check_measure_sizes("icn_mesh_angle_defect_bwd", B, V, F);
+        icn::launch_mesh_angle_defect_bwd(vertices, faces, vf_offsets, vf_corners, ddefect, B, V, F, dvertices, s);
     });
 }
 

@@ -36,25 +36,6 @@ int mesh_curvature_blocks(int V) { return (int)(((long long)V + MESH_BLOCK - 1) 
 
 namespace {
 
-// one incident face of vertex j, as every kernel here meets it: its three vertex ids, j's corner k, and whether to use it at all
-struct Incident {
-    int id[3], k;
-    bool ok;
-};
-
-__device__ __forceinline__ Incident incident(const int32_t* __restrict__ faces, const int32_t* __restrict__ corners, int at, int j, int nc,
-                                             int V) {
-    Incident t;
-    t.ok = false;
-    const int c = corners[at];
-    if (c < 0 || c >= nc || faces[c] != j) return t;
-    const int f = c / 3;
-    t.k = c - 3 * f;
-    t.id[0] = faces[(size_t)f * 3], t.id[1] = faces[(size_t)f * 3 + 1], t.id[2] = faces[(size_t)f * 3 + 2];
-    t.ok = ids_ok(t.id[0], t.id[1], t.id[2], V);
-    return t;
-}
-
 __device__ __forceinline__ bool resolved(float nn) { return nn > 0.f && nn <= 3.4028234663852886e38f; }   // not 0, NaN or overflowed
 
 __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_cotlap_fwd(const float* __restrict__ vts, const int32_t* __restrict__ faces,

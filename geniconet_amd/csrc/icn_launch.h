@@ -279,6 +279,13 @@ void launch_mesh_willmore_fwd(const float* vts, const int32_t* faces, const int3
 void launch_mesh_willmore_bwd(const float* vts, const int32_t* faces, const int32_t* offsets, const int32_t* corners, const float* lap,
                               const float* varea, const float* denergy, int B, int V, int F, float* dvts, void* ws, hipStream_t s);
 
+// angle defect (integrated Gaussian curvature) per vertex and its backward to the vertices (icn_gauss.hip; include/icn_gauss.h): one
+// thread per (mesh, vertex) over the incidence table, double arithmetic, fp32 in and out.  One launch each on s, no workspace.
+void launch_mesh_angle_defect_fwd(const float* vts, const int32_t* faces, const int32_t* offsets, const int32_t* corners, int B, int V,
+                                  int F, float* defect, hipStream_t s);
+void launch_mesh_angle_defect_bwd(const float* vts, const int32_t* faces, const int32_t* offsets, const int32_t* corners,
+                                  const float* ddefect, int B, int V, int F, float* dvts, hipStream_t s);
+
 // developer routing flags (ICN_DEBUG / icn_set_debug_flags): 16 = convs on k_gather_gemm, 32 = wgrads on k_wgrad,
 // 128 = no stream-K, 256 = fault injection: every stream-K finisher reports its partners lost (tests of the failure path),
 // 512 = masked launches walk tiles b, b + G, ... instead of the balanced tile lists, 1024 = the sparse passes of the decoder-block
@@ -289,7 +296,7 @@ int debug_flags();
 int set_debug_flags(int flags);
 
 // ---- optional per-launch HIP-event timing of the MFMA kernels (bench.py's live roofline measurement) and of the
-// point-to-mesh, surface-sampling, normal-agreement, mesh-measure and mesh-curvature kernels ----------
+// point-to-mesh, surface-sampling, normal-agreement, mesh-measure, mesh-curvature and angle-defect kernels ----------
 enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA_64x64, PROF_GG_128x128, PROF_GG_128x64,
                 PROF_GG_64x128, PROF_GG_64x64, PROF_WGD_128x128, PROF_WGD_128x64, PROF_WGD_64x128, PROF_WGD_64x64, PROF_WG_128x128,
                 PROF_WG_128x64, PROF_WG_64x128, PROF_WG_64x64,
@@ -308,6 +315,7 @@ enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA
                 PROF_FNORMAL_AGREE, PROF_FNORMAL_AGREE_BWD_RECORD, PROF_FNORMAL_AGREE_BWD_VERTEX,   // normal agreement of sampled surfaces
                 PROF_MESH_MEASURE_FACE, PROF_MESH_MEASURE_FINISH, PROF_MESH_MEASURE_BWD,            // area and volume per mesh
                 PROF_MESH_COTLAP_FWD, PROF_MESH_WILLMORE_FINISH, PROF_MESH_WILLMORE_UPSTREAM, PROF_MESH_COTLAP_BWD,   // cotangent Laplacian, Willmore energy
+                PROF_MESH_ANGLE_DEFECT_FWD, PROF_MESH_ANGLE_DEFECT_BWD,                             // angle defect (Gaussian curvature)
                 PROF_KINDS };
 extern const char* const PROF_NAMES[PROF_KINDS];
 void prof_mark_begin(int kind, double flops, hipStream_t s);   // no-ops unless profiling is on

@@ -1,5 +1,5 @@
-// Device code shared by the mesh kernels of icn_loss.hip, icn_sample.hip, icn_measure.hip and icn_curvature.hip: 3-vectors, the pixel <-> vertex rule of the
-// icosahedral grid, fixed-order block reductions, the tiled block scan and the per-record vertex scatter's record set.
+// Device code shared by the mesh kernels of icn_loss.hip, icn_sample.hip, icn_measure.hip, icn_curvature.hip and icn_gauss.hip: 3-vectors, the
+// incident face of a per-vertex gather, the pixel <-> vertex rule of the icosahedral grid, fixed-order block reductions, the tiled block scan and the per-record vertex scatter's record set.
 // Everything here is inlined into its callers; every sum has a fixed order (bit-identical run to run).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,6 +32,28 @@ __device__ __forceinline__ f3 face_normal(f3 a, f3 b) {
 __device__ __forceinline__ float norm2(f3 n) { return fmaf(n.z, n.z, fmaf(n.x, n.x, n.y * n.y)); }
 __device__ __forceinline__ bool ids_ok(int i0, int i1, int i2, int V) {
     return i0 >= 0 && i0 < V && i1 >= 0 && i1 < V && i2 >= 0 && i2 < V;
+}
+
+// One incident face of vertex j, as the per-vertex gathers of icn_curvature.hip and icn_gauss.hip meet it in j's slice of the
+// vertex -> corner incidence table: its three vertex ids, j's corner k, and whether to use it at all.  Entry `at` of `corners` is
+// used only if it names a corner c in [0, nc = 3 F) with faces[c] == j, and only if the face's three ids index V vertices: whatever
+// the table holds, nothing is read out of bounds.
+struct Incident {
+    int id[3], k;
+    bool ok;
+};
+
+__device__ __forceinline__ Incident incident(const int32_t* __restrict__ faces, const int32_t* __restrict__ corners, int at, int j, int nc,
+                                             int V) {
+    Incident t;
+    t.ok = false;
+    const int c = corners[at];
+    if (c < 0 || c >= nc || faces[c] != j) return t;
+    const int f = c / 3;
+    t.k = c - 3 * f;
+    t.id[0] = faces[(size_t)f * 3], t.id[1] = faces[(size_t)f * 3 + 1], t.id[2] = faces[(size_t)f * 3 + 2];
+    t.ok = ids_ok(t.id[0], t.id[1], t.id[2], V);
+    return t;
 }
 
 // ---- pixels and vertices of the icosahedral grid (n = 2^r) ------------------------------------------------------------------

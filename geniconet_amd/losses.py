@@ -22,7 +22,8 @@ Surface_Loss / SurfaceKLD_Loss (train.build_criterion: 'surface' / 'surfacekld')
 both directions plus Mesh_Regularizer (edge length, normal consistency, Laplacian smoothness; HIP kernels icn_mesh_reg_*); from
 surface samples (samples > 0) optionally with the normal agreement of the two surfaces (factor_normal; icn_face_normal_agree_*),
 and optionally with the enclosed volume and the surface area held to the target's (factor_volume / factor_area; icn_mesh_measure_*)
-and with the Willmore bending energy of the output (factor_willmore; icn_mesh_willmore_*), the smoothness term that does not shrink.
+and with the Willmore bending energy of the output (factor_willmore; icn_mesh_willmore_*), the smoothness term that does not shrink,
+and with the Gaussian curvature of the output held to the target's vertex by vertex (factor_gauss; icn_mesh_angle_defect_*).
 """
 import math
 import os
@@ -498,17 +499,39 @@ class Surface_Loss(torch.nn.Module):
     (the four kernels are 0.06 ms of that; the rest is launch and autograd overhead on the host) against 0.80 / 2.6 ms for the
     torch formulation on the device: 21 x and 13 x, and here the fixed-order HIP backward does beat torch's atomic index_add.
     Building the table on entry instead adds 0.12 ms.  This whole term, forward + backward, search='grid': samples = 0
-    6.01 -> 6.01 ms, samples = 10 242 7.75 -> 7.81 ms with the factor."""
+    6.01 -> 6.01 ms, samples = 10 242 7.75 -> 7.81 ms with the factor.
+
+    factor_gauss != 0 compares the CURVATURE of the output with that of the target, which none of the terms above does: W penalises
+    mean curvature everywhere, pulls every mesh towards the round sphere and erases the target's own creases and bumps as readily as
+    noise.  Output and target share the ico faces, so the comparison is vertex by vertex.  With defect = metrics.angle_defect(.,
+    ico_faces), the angle defect 2 pi - sum theta, which is the Gaussian curvature integrated over a vertex's cell:
+        l_gauss = mean_b sum_i (defect(out)_i - defect(ref)_i)^2;   loss += factor_gauss * l_gauss
+    The term holds the output to the TARGET's features where W flattens them.  The defect is intrinsic and dimensionless, so the
+    term is invariant under scaling of either mesh and shrinking cannot lower it; by Gauss-Bonnet sum_i defect_i = 4 pi on both
+    sides, so the differences sum to zero and cannot all be driven one way.  defect(ref) is computed without a graph; both sides
+    gather over the ico_vf_* buffers; the gradient to the output runs through icn_mesh_angle_defect_bwd.  The kernels compute in
+    double from the fp32 vertices and round once (in fp32 the defect of an I5 mesh, 1e-3, carries an error of 1e-6).  The term needs
+    no samples, draws no random numbers and never synchronises the host; last_gauss holds l_gauss (a device tensor; 0 while the
+    term is off), get_last_losses() keeps its five-tuple and state_dict is unchanged.  With the factor 0 (the default) nothing new
+    is launched and the loss is bit for bit what it was.
+    Cost on an MI355X at I5 / batch 36 (HIP events, median of 10, profiles/mesh_gauss.txt, from `python tools/time_mesh_gauss.py
+    10`): k_mesh_angle_defect_fwd 0.024 ms, k_mesh_angle_defect_bwd 0.026 ms, beside k_mesh_cotlap_fwd 0.017 ms and
+    k_mesh_cotlap_bwd 0.024 ms in the same run -- the same gathers in fp32 -- so the double arithmetic costs 1.4 x forward (six
+    atan2 per vertex) and 1.06 x backward (1.04 - 1.05 in two other runs).  Through autograd the HIP path takes 0.03 ms forward and
+    0.23 ms forward + backward (the rest is launch and autograd overhead on the host: 0.11 and 0.18 ms in the other runs) against
+    0.80 / 2.31 ms for the float64 torch formulation on the device: 25 x and 10 x.  Building the table on entry instead adds
+    0.11 ms.  This whole term, forward + backward, search='grid': samples = 0 6.00 -> 6.13 ms, samples = 10 242 7.81 -> 7.92 ms
+    with the factor (two forwards and one backward)."""
 
     def __init__(self, subdivisions, factor_p2m=1.0, factor_m2p=1.0, factor_edge=0.0, factor_ncons=0.0, factor_smooth=0.0,
                  edge_length=0.0, search='brute', samples=0, sample_seed=0, factor_normal=0.0, normal_oriented=True,
-                 factor_volume=0.0, factor_area=0.0, factor_willmore=0.0):
+                 factor_volume=0.0, factor_area=0.0, factor_willmore=0.0, factor_gauss=0.0):
         super().__init__()
         from .metrics import _check_search
         _check_search(search)
         _check_subdivisions('Surface_Loss', subdivisions)
         _check_factors('Surface_Loss', factor_p2m=factor_p2m, factor_m2p=factor_m2p, factor_normal=factor_normal,
-                       factor_volume=factor_volume, factor_area=factor_area, factor_willmore=factor_willmore)
+                       factor_volume=factor_volume, factor_area=factor_area, factor_willmore=factor_willmore, factor_gauss=factor_gauss)
         if isinstance(samples, bool) or not isinstance(samples, int) or samples < 0:
             raise ValueError('%s: samples must be a non-negative integer, got %r' % (type(self).__name__, samples))
         if isinstance(sample_seed, bool) or not isinstance(sample_seed, int):
@@ -521,7 +544,7 @@ class Surface_Loss(torch.nn.Module):
         self.samples, self.sample_seed, self._sample_generator = samples, sample_seed, None
         self.factor_normal, self.normal_oriented = factor_normal, normal_oriented
         self.factor_volume, self.factor_area = factor_volume, factor_area
-        self.factor_willmore = factor_willmore
+        self.factor_willmore, self.factor_gauss = factor_willmore, factor_gauss
         self.subdivisions, self.search = subdivisions, search
         self.factor_p2m, self.factor_m2p = factor_p2m, factor_m2p
         self.regularizer = Mesh_Regularizer(subdivisions, factor_edge, factor_ncons, factor_smooth, edge_length)
@@ -537,7 +560,7 @@ class Surface_Loss(torch.nn.Module):
         self.register_buffer('ico_vf_offsets', offsets, persistent=False)
         self.register_buffer('ico_vf_corners', corners, persistent=False)
         self.last_p2m = self.last_m2p = self.last_reg = self.last_loss_total = self.last_normal = 0
-        self.last_volume = self.last_area = self.last_willmore = 0
+        self.last_volume = self.last_area = self.last_willmore = self.last_gauss = 0
 
     def _draw_uniforms(self, B, device):
         """The (2, B, S, 3) uniforms of one forward, from the generator seeded with sample_seed on the first forward's device."""
@@ -604,6 +627,16 @@ class Surface_Loss(torch.nn.Module):
             l_w = _willmore_energy_unchecked(out, faces, table).mean()
             loss = loss + self.factor_willmore * l_w
             self.last_willmore = l_w.detach()
+        self.last_gauss = 0
+        if self.factor_gauss != 0:
+            from .metrics import _angle_defect_unchecked
+            table = tuple(t if t.device == out.device else t.to(out.device) for t in (self.ico_vf_offsets, self.ico_vf_corners))
+            defect_out = _angle_defect_unchecked(out, faces, table)
+            with torch.no_grad():
+                defect_ref = _angle_defect_unchecked(ref, faces, table)
+            l_g = ((defect_out - defect_ref) ** 2).sum(1).mean()
+            loss = loss + self.factor_gauss * l_g
+            self.last_gauss = l_g.detach()
         self.last_p2m, self.last_m2p, self.last_reg = l_p2m.detach(), l_m2p.detach(), l_reg.detach()
         self.last_loss_total = loss.detach()
         return loss
@@ -665,10 +698,11 @@ class SurfaceKLD_Loss(Surface_Loss, KLD_Loss):
 
     def __init__(self, subdivisions, factor_p2m=1.0, factor_m2p=1.0, factor_edge=0.0, factor_ncons=0.0, factor_smooth=0.0,
                  edge_length=0.0, search='brute', factor_kl=1.0, samples=0, sample_seed=0, factor_normal=0.0, normal_oriented=True,
-                 factor_volume=0.0, factor_area=0.0, factor_willmore=0.0):
+                 factor_volume=0.0, factor_area=0.0, factor_willmore=0.0, factor_gauss=0.0):
         super().__init__(subdivisions, factor_p2m, factor_m2p, factor_edge, factor_ncons, factor_smooth, edge_length, search,
                          samples=samples, sample_seed=sample_seed, factor_normal=factor_normal, normal_oriented=normal_oriented,
-                         factor_volume=factor_volume, factor_area=factor_area, factor_willmore=factor_willmore)
+                         factor_volume=factor_volume, factor_area=factor_area, factor_willmore=factor_willmore,
+                         factor_gauss=factor_gauss)
         _check_factors('SurfaceKLD_Loss', factor_kl=factor_kl)
         self.factor_kl = factor_kl
 

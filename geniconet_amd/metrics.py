@@ -41,6 +41,13 @@ cotangent_laplacian and willmore_energy (below) give the integrated cotangent La
 areas, and the Willmore bending energy (the integral of H^2) of every mesh of a batch, differentiable in the vertices
 (icn_mesh_cotlap_* / icn_mesh_willmore_*, include/icn_curvature.h; every kernel gathers over vertex_face_table): the smoothness
 measure that is geometric and scale invariant, where the uniform umbrella of losses.Mesh_Regularizer shrinks the mesh.
+
+angle_defect, gaussian_curvature and total_curvature (below) give the discrete Gaussian curvature of every mesh of a batch: the
+angle defect 2 pi - sum theta per vertex, that defect over the barycentric vertex area, and its sum per mesh (2 pi chi by
+Gauss-Bonnet: 4 pi for a sphere), differentiable in the vertices (icn_mesh_angle_defect_fwd / _bwd, include/icn_gauss.h; the same
+gather over vertex_face_table, in double from the fp32 vertices, because the defect of a fine mesh is lost in fp32).  With
+cotangent_laplacian this completes the pair (H, K); curvature_error is the relative defect error of one mesh pair, to stand beside
+volume_error and compute_distance.
 """
 import torch
 
@@ -759,6 +766,162 @@ def willmore_energy(vertices, faces, table=None):
     lap and varea of the forward for the backward; paths, `table` and checks as cotangent_laplacian."""
     f32, table = _check_mesh_arguments('willmore_energy', vertices, faces, table)
     return _willmore_energy_unchecked(vertices, f32, table)
+
+
+# ---- Gaussian curvature by angle defect ---------------------------------------------------------------------------------------------
+_TWO_PI = 6.283185307179586
+
+
+def _torch_angle_defect(vertices, faces):
+    """The definition of angle_defect in torch, differentiable in the vertices through autograd: float64 up to the final rounding,
+    defect (B, V) in the vertices' dtype."""
+    from .losses import Mesh_Regularizer
+    V = vertices.shape[1]
+    ids = faces.long()
+    ok = ((ids >= 0) & (ids < V)).all(-1)                                                 # (F,): the others take no part
+    ids = ids.clamp(0, V - 1)
+    tri = vertices.double()[:, ids]                                                       # (B, F, 3 corners, 3)
+    with torch.no_grad():
+        nn = (Mesh_Regularizer._face_normal(tri[:, :, 1] - tri[:, :, 0], tri[:, :, 2] - tri[:, :, 0]) ** 2).sum(-1)
+        flat = ~(nn != 0) | ~ok                                                           # unresolved (NaN is not: it propagates)
+        # an unresolved face enters autograd as a fixed right triangle whose angles are then dropped: its vertices meet no
+        # arithmetic that autograd records, and no atan2(0, 0) or sqrt(0) gives a NaN gradient
+        safe = torch.eye(3, dtype=tri.dtype, device=tri.device)
+    tri = torch.where(flat[..., None, None], safe, tri)
+    p = [tri[:, :, k] for k in range(3)]
+    n = Mesh_Regularizer._face_normal(p[1] - p[0], p[2] - p[0])
+    length = (n * n).sum(-1).sqrt()
+    total = torch.zeros(vertices.shape[:2], dtype=tri.dtype, device=tri.device)
+    count = torch.zeros_like(total)
+    live = (~flat).to(tri.dtype)
+    for k in range(3):
+        a, b = p[(k + 1) % 3] - p[k], p[(k + 2) % 3] - p[k]
+        theta = torch.atan2(length, (a * b).sum(-1))
+        total = total.index_add(1, ids[:, k], torch.where(flat, torch.zeros_like(theta), theta))
+        count = count.index_add(1, ids[:, k], live)
+    return torch.where(count > 0, _TWO_PI - total, torch.zeros_like(total)).to(vertices.dtype)
+
+
+def _hip_angle_defect(vts, f32, offsets, corners):
+    """icn_mesh_angle_defect_fwd on contiguous fp32 ROCm vertices, an int32 face table and its incidence table -> defect (B, V)."""
+    L = _lib.api()
+    B, V, F = vts.shape[0], vts.shape[1], f32.shape[0]
+    defect = torch.empty(B, V, dtype=torch.float32, device=vts.device)
+    with torch.cuda.device(vts.device):
+        for b0, nb in _batch_slices(B):
+            L.icn_mesh_angle_defect_fwd(vts[b0:].data_ptr(), f32.data_ptr(), offsets.data_ptr(), corners.data_ptr(), nb, V, F,
+                                        defect[b0:].data_ptr(), _lib.stream())
+    return defect
+
+
+class _AngleDefectFn(torch.autograd.Function):
+    """angle_defect on the HIP path (icn_mesh_angle_defect_fwd / _bwd in include/icn_gauss.h): both directions are one gather over the
+    vertex -> corner incidence table in double, summed in a fixed order: bit-identical run to run.  When no gradient arrives
+    nothing is launched."""
+
+    @staticmethod
+    def forward(ctx, vertices, f32, offsets, corners):
+        vts = vertices.contiguous()
+        ctx.save_for_backward(vts, f32, offsets, corners)
+        ctx.set_materialize_grads(False)
+        return _hip_angle_defect(vts, f32, offsets, corners)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, ddefect):
+        if ddefect is None:
+            return None, None, None, None
+        L = _lib.api()
+        vts, f32, offsets, corners = ctx.saved_tensors
+        B, V, F = vts.shape[0], vts.shape[1], f32.shape[0]
+        dd = ddefect.contiguous().to(torch.float32)
+        dvts = torch.empty_like(vts)
+        with torch.cuda.device(vts.device):
+            for b0, nb in _batch_slices(B):
+                L.icn_mesh_angle_defect_bwd(vts[b0:].data_ptr(), f32.data_ptr(), offsets.data_ptr(), corners.data_ptr(),
+                                            dd[b0:].data_ptr(), nb, V, F, dvts[b0:].data_ptr(), _lib.stream())
+        return dvts, None, None, None
+
+
+def _angle_defect_unchecked(vertices, f32, table=None):
+    """angle_defect without its argument checks and without a host synchronisation (losses.Surface_Loss); arguments as
+    _cotangent_laplacian_unchecked."""
+    if _on_hip_path(vertices):
+        offsets, corners = table if table is not None else vertex_face_table(f32, vertices.shape[1])
+        if torch.is_grad_enabled() and vertices.requires_grad:
+            return _AngleDefectFn.apply(vertices, f32, offsets, corners)
+        return _hip_angle_defect(vertices.detach().contiguous(), f32, offsets, corners)
+    return _torch_angle_defect(vertices, f32)
+
+
+def _gaussian_curvature_unchecked(vertices, f32, table=None):
+    """gaussian_curvature without its argument checks and without a host synchronisation; arguments as
+    _cotangent_laplacian_unchecked (on the HIP path the table is built once here and serves both operators)."""
+    if table is None and _on_hip_path(vertices):
+        table = vertex_face_table(f32, vertices.shape[1])
+    defect = _angle_defect_unchecked(vertices, f32, table)
+    varea = _cotangent_laplacian_unchecked(vertices, f32, table)[1]
+    has = varea != 0                                                                      # NaN counts: it propagates
+    return torch.where(has, defect, torch.zeros_like(defect)) / torch.where(has, varea, torch.ones_like(varea))
+
+
+def angle_defect(vertices, faces, table=None):
+    """defect (B, V) of the triangle meshes vertices (B, V, 3), faces (F, 3) integer and shared by the batch: the angle defect
+    2 pi - sum theta at every vertex, which is the discrete GAUSSIAN curvature integrated over the vertex's cell.  It is intrinsic
+    (unchanged by bending without stretching), dimensionless (invariant under scaling, rotation and translation), and by
+    Gauss-Bonnet it sums to 2 pi chi over a closed mesh: 4 pi for every sphere, whatever its shape (total_curvature).
+
+    One definition for the HIP kernels (include/icn_gauss.h), the torch formulation and the tests.  All arithmetic up to the final
+    rounding is float64, whatever the vertices' dtype; the output has the vertices' dtype.  For a face (i0, i1, i2) and its corner k,
+    corner indices modulo 3:
+        a = v_{k+1} - v_k,  b = v_{k+2} - v_k,  n = (v1 - v0) x (v2 - v0) with every product of the cross product rounded on its own
+        theta_k = atan2(|n|, a . b)                      (|a x b| = |n| at every corner; no rounded cosine ever meets an acos)
+        the face is RESOLVED iff |n|^2 != 0              (a face with two coincident vertices has n exactly 0)
+        defect_i = 2 pi - sum_{resolved f at i} theta_k(f),   exactly 0 at a vertex that has no resolved face
+    An unresolved face adds no angle and sends no gradient; a vertex no face references, or all of whose faces are unresolved, has
+    defect 0 exactly (as lap and varea of cotangent_laplacian); non-finite vertices propagate NaN into their own mesh only.
+    Why float64: written in fp32 the defect carries an absolute error of 8 - 22 units of 2^-24, about 1e-6 whatever the resolution,
+    while the defect of a smooth I5 mesh is itself 1.1e-3 .. 1.5e-3; the errors do not average out (the fp32 I5 total misses 4 pi by
+    1.8e-3, float64 by 2e-13).
+    Differentiable in the vertices.  For L = sum_i g_i defect_i a resolved face sends to its corner k, with n^ = n / |n|,
+        (g_{k+1} - g_k) (n^ x a) / |a|^2  +  (g_k - g_{k+2}) (n^ x b) / |b|^2
+    and the HIP backward computes exactly this difference form: a uniform upstream gives a gradient of exactly 0 at every vertex
+    (the total curvature cannot be changed), which autograd of the torch formulation reaches only to rounding.
+    ROCm fp32 tensors run on icn_mesh_angle_defect_fwd / _bwd, one thread per (mesh, vertex) gathering over `table` =
+    vertex_face_table(faces, V) in double in a fixed order without atomics (bit-identical run to run); paths, `table` and checks as
+    cotangent_laplacian.  Cost on an MI355X: see losses.Surface_Loss (factor_gauss)."""
+    f32, table = _check_mesh_arguments('angle_defect', vertices, faces, table)
+    return _angle_defect_unchecked(vertices, f32, table)
+
+
+def gaussian_curvature(vertices, faces, table=None):
+    """K (B, V) = defect_i / varea_i, the pointwise Gaussian curvature: angle_defect over the barycentric vertex area of
+    cotangent_laplacian; 0 where varea_i = 0, and no gradient passes there.  1 / R^2 on a sphere of radius R (on the icosphere the
+    six-valent vertices narrow towards it, 1.045 at one subdivision and 1.0001 at three; the twelve five-valent vertices stay near
+    1.146, because a third of the incident area is not their Voronoi cell).  Together with lap = 2 varea H normal this completes the
+    pair (H, K).  Differentiable in the vertices, on the HIP path through the kernels of both operators; paths, `table` and checks
+    as cotangent_laplacian."""
+    f32, table = _check_mesh_arguments('gaussian_curvature', vertices, faces, table)
+    return _gaussian_curvature_unchecked(vertices, f32, table)
+
+
+def total_curvature(vertices, faces, table=None):
+    """(B,): sum_i defect_i of angle_defect, summed in double, in the vertices' dtype.  By Gauss-Bonnet it is 2 pi chi for a closed
+    mesh -- 4 pi for a sphere, 0 for a torus -- and 2 pi for a disc: the cheapest check that a face list is a closed sphere, and a
+    constant of the vertices (its gradient vanishes)."""
+    f32, table = _check_mesh_arguments('total_curvature', vertices, faces, table)
+    return _angle_defect_unchecked(vertices, f32, table).double().sum(1).to(vertices.dtype)
+
+
+def curvature_error(outvertices, refvertices, faces):
+    """sqrt(sum_i (defect_out_i - defect_ref_i)^2 / sum_i defect_ref_i^2) of one mesh pair ((V, 3) tensors sharing `faces`) as a
+    Python float, to stand beside volume_error and compute_distance: how far the output's Gaussian curvature is from the
+    reference's, vertex by vertex.  Defects as angle_defect defines them."""
+    if outvertices.dim() != 2 or refvertices.dim() != 2:
+        raise ValueError('curvature_error: expected (V, 3) vertices, got %s and %s' % (tuple(outvertices.shape), tuple(refvertices.shape)))
+    d_out = angle_defect(outvertices[None], faces).double()
+    d_ref = angle_defect(refvertices[None], faces).double()
+    return float(((d_out - d_ref) ** 2).sum().sqrt() / (d_ref ** 2).sum().sqrt())
 
 
 def output2vertices(subdivisions, output):

@@ -85,7 +85,8 @@ def build_criterion(params, device):
                   search=ico.get('p2m_search', 'brute'), samples=ico.get('surface_samples', 0),
                   sample_seed=ico.get('surface_sample_seed', 0), factor_normal=ico.get('factor_normal', 0.0),
                   normal_oriented=ico.get('normal_oriented', True), factor_volume=ico.get('factor_volume', 0.0),
-                  factor_area=ico.get('factor_area', 0.0), factor_willmore=ico.get('factor_willmore', 0.0))
+                  factor_area=ico.get('factor_area', 0.0), factor_willmore=ico.get('factor_willmore', 0.0),
+                  factor_gauss=ico.get('factor_gauss', 0.0))
         if loss_kind == 'surface':
             crit = losses.Surface_Loss(ico['subdivisions'], **kw)
         else:
