@@ -138,6 +138,12 @@ SIGNATURES_GAUSS = {
     'icn_mesh_angle_defect_bwd': (ctypes.c_int, [_c_float_p] * 5 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
 }
 
+# self-intersection count of meshes: include/icn_isect.h one to one (checked by tests/test_abi_isect.py), same conventions, same
+# library
+SIGNATURES_ISECT = {
+    'icn_mesh_self_intersect': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
+}
+
 
 class ProfileEntry(ctypes.Structure):
     _fields_ = [('kernel', ctypes.c_char_p), ('launches', ctypes.c_long), ('total_ms', ctypes.c_double),
@@ -173,7 +179,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         checked = types.SimpleNamespace()
         for name, (res, args, reply) in (list(SIGNATURES.items()) + list(SIGNATURES_EXT.items()) + list(SIGNATURES_MEASURE.items())
-                                         + list(SIGNATURES_CURV.items()) + list(SIGNATURES_GAUSS.items())):
+                                         + list(SIGNATURES_CURV.items()) + list(SIGNATURES_GAUSS.items()) + list(SIGNATURES_ISECT.items())):
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             fn = handle[name]            # a function object of its own (handle.name is cached, handle[name] is not)
@@ -236,13 +242,13 @@ def set_arith(mode):
 
 
 def source_sha256():
-    """sha256 over the kernel / library sources under csrc/, include/icn.h, include/icn_ext.h, include/icn_measure.h, include/icn_curvature.h and include/icn_gauss.h (names + contents, sorted): identifies the code a
+    """sha256 over the kernel / library sources under csrc/, include/icn.h, include/icn_ext.h, include/icn_measure.h, include/icn_curvature.h, include/icn_gauss.h and include/icn_isect.h (names + contents, sorted): identifies the code a
     profile was measured on (tools/profile_summary.py stores it, bench.py refuses a profile of other sources)."""
     import glob
     import hashlib
     h = hashlib.sha256()
     files = sorted(glob.glob(os.path.join(_HERE, 'csrc', '*.hip')) + glob.glob(os.path.join(_HERE, 'csrc', '*.h'))
-                   + glob.glob(os.path.join(_HERE, 'csrc', '*.cpp')) + [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('icn.h', 'icn_ext.h', 'icn_measure.h', 'icn_curvature.h', 'icn_gauss.h')])
+                   + glob.glob(os.path.join(_HERE, 'csrc', '*.cpp')) + [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('icn.h', 'icn_ext.h', 'icn_measure.h', 'icn_curvature.h', 'icn_gauss.h', 'icn_isect.h')])
     for f in files:
         h.update(os.path.basename(f).encode() + b'\0')
         h.update(open(f, 'rb').read())

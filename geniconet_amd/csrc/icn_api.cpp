@@ -16,6 +16,7 @@
 #include "../../include/icn_ext.h"
 #include "../../include/icn_curvature.h"
 #include "../../include/icn_gauss.h"
+#include "../../include/icn_isect.h"
 #include "../../include/icn_measure.h"
 #include "icn_geometry.h"
 #include "icn_launch.h"
@@ -792,7 +793,7 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_fnormal_agree_bwd_vertex",    // every ..._bwd_vertex: k_vertex_scatter, by its caller
                                             "k_mesh_measure_face", "k_mesh_measure_finish", "k_mesh_measure_bwd",
                                             "k_mesh_cotlap_fwd", "k_mesh_willmore_finish", "k_mesh_willmore_upstream", "k_mesh_cotlap_bwd",
-                                            "k_mesh_angle_defect_fwd", "k_mesh_angle_defect_bwd"};
+                                            "k_mesh_angle_defect_fwd", "k_mesh_angle_defect_bwd", "k_mesh_self_intersect"};
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1548,6 +1549,17 @@ int icn_mesh_angle_defect_bwd(const float* vertices, const int32_t* faces, const
             throw std::invalid_argument("icn_mesh_angle_defect_bwd: null pointer");
         check_measure_sizes("icn_mesh_angle_defect_bwd", B, V, F);
         icn::launch_mesh_angle_defect_bwd(vertices, faces, vf_offsets, vf_corners, ddefect, B, V, F, dvertices, s);
+    });
+}
+
+// ---- self-intersection count (include/icn_isect.h): the sizes of the measure entries, and a cap on the quadratic work -----------
+int icn_mesh_self_intersect(const float* vertices, const int32_t* faces, int B, int V, int F, int32_t* hits, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!vertices || !faces || !hits) throw std::invalid_argument("icn_mesh_self_intersect: null pointer");
+        check_measure_sizes("icn_mesh_self_intersect", B, V, F);
+        if (F > ICN_SELF_INTERSECT_MAX_FACES) throw std::invalid_argument("icn_mesh_self_intersect: bad sizes");
+        icn::launch_mesh_self_intersect(vertices, faces, B, V, F, hits, s);
     });
 }
 

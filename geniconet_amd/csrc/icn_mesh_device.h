@@ -1,4 +1,4 @@
-// Device code shared by the mesh kernels of icn_loss.hip, icn_sample.hip, icn_measure.hip, icn_curvature.hip and icn_gauss.hip: 3-vectors, the
+// Device code shared by the mesh kernels of icn_loss.hip, icn_sample.hip, icn_measure.hip, icn_curvature.hip, icn_gauss.hip and icn_isect.hip: 3-vectors, the
 // incident face of a per-vertex gather, the pixel <-> vertex rule of the icosahedral grid, fixed-order block reductions, the tiled block scan and the per-record vertex scatter's record set.
 // Everything here is inlined into its callers; every sum has a fixed order (bit-identical run to run).
 #pragma once
