@@ -104,44 +104,35 @@ SIGNATURES = {
     'icn_table_upconv': (ctypes.c_long, [ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_size_t, _f32p, ctypes.c_size_t, _intp], COUNT),
 }
 
-# entry points added since the icn.h freeze at ABI 9: include/icn_ext.h one to one (checked by tests/test_abi_ext.py), same
-# conventions, same library
-SIGNATURES_EXT = {
-    'icn_face_normal_agree_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4, PLAIN),
-    'icn_face_normal_agree_fwd': (ctypes.c_int, ([_c_float_p] * 3 + [ctypes.c_int] * 2) * 2 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
-    'icn_face_normal_agree_bwd': (ctypes.c_int, ([_c_float_p] * 3 + [ctypes.c_int] * 2) * 2 + [ctypes.c_int] * 3 + [_c_float_p] * 3
-                                  + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
-}
-
-# surface area and enclosed volume of meshes: include/icn_measure.h one to one (checked by tests/test_abi_measure.py), same
-# conventions, same library
-SIGNATURES_MEASURE = {
-    'icn_mesh_measure_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 3, PLAIN),
-    'icn_mesh_measure_fwd': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 3 + [_c_float_p] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
-    'icn_mesh_measure_bwd': (ctypes.c_int, [_c_float_p] * 6 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
-}
-
-# cotangent Laplacian and Willmore energy of meshes: include/icn_curvature.h one to one (checked by tests/test_abi_curvature.py), same
-# conventions, same library
-SIGNATURES_CURV = {
-    'icn_mesh_cotlap_fwd': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 3 + [_c_float_p] * 2 + [ctypes.c_void_p], RC),
-    'icn_mesh_cotlap_bwd': (ctypes.c_int, [_c_float_p] * 6 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
-    'icn_mesh_willmore_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 3, PLAIN),
-    'icn_mesh_willmore_fwd': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 3 + [_c_float_p] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
-    'icn_mesh_willmore_bwd': (ctypes.c_int, [_c_float_p] * 7 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
-}
-
-# angle defect (integrated Gaussian curvature) of meshes: include/icn_gauss.h one to one (checked by tests/test_abi_gauss.py), same
-# conventions, same library
-SIGNATURES_GAUSS = {
-    'icn_mesh_angle_defect_fwd': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
-    'icn_mesh_angle_defect_bwd': (ctypes.c_int, [_c_float_p] * 5 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
-}
-
-# self-intersection count of meshes: include/icn_isect.h one to one (checked by tests/test_abi_isect.py), same conventions, same
-# library
-SIGNATURES_ISECT = {
-    'icn_mesh_self_intersect': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
+# entry points added since the icn.h freeze at ABI 9, by the header of include/ that declares them: each mirrors its header one to
+# one (checked by tests/test_abi_mesh.py and tests/test_abi_ext.py), same conventions, same library.  A new header is one more key here: lib() binds it and
+# source_files() hashes it.
+EXTENSION_HEADERS = {
+    'icn_ext.h': {                     # normal agreement of two sampled surfaces
+        'icn_face_normal_agree_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4, PLAIN),
+        'icn_face_normal_agree_fwd': (ctypes.c_int, ([_c_float_p] * 3 + [ctypes.c_int] * 2) * 2 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
+        'icn_face_normal_agree_bwd': (ctypes.c_int, ([_c_float_p] * 3 + [ctypes.c_int] * 2) * 2 + [ctypes.c_int] * 3 + [_c_float_p] * 3
+                                      + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+    },
+    'icn_measure.h': {                 # surface area and enclosed volume of meshes
+        'icn_mesh_measure_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 3, PLAIN),
+        'icn_mesh_measure_fwd': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 3 + [_c_float_p] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+        'icn_mesh_measure_bwd': (ctypes.c_int, [_c_float_p] * 6 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
+    },
+    'icn_curvature.h': {               # cotangent Laplacian and Willmore energy of meshes
+        'icn_mesh_cotlap_fwd': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 3 + [_c_float_p] * 2 + [ctypes.c_void_p], RC),
+        'icn_mesh_cotlap_bwd': (ctypes.c_int, [_c_float_p] * 6 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
+        'icn_mesh_willmore_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 3, PLAIN),
+        'icn_mesh_willmore_fwd': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 3 + [_c_float_p] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+        'icn_mesh_willmore_bwd': (ctypes.c_int, [_c_float_p] * 7 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+    },
+    'icn_gauss.h': {                   # angle defect (integrated Gaussian curvature) of meshes
+        'icn_mesh_angle_defect_fwd': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
+        'icn_mesh_angle_defect_bwd': (ctypes.c_int, [_c_float_p] * 5 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
+    },
+    'icn_isect.h': {                   # self-intersection count of meshes
+        'icn_mesh_self_intersect': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
+    },
 }
 
 
@@ -178,8 +169,7 @@ def lib():
                 '(or `make -C geniconet_amd/csrc`).' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
         checked = types.SimpleNamespace()
-        for name, (res, args, reply) in (list(SIGNATURES.items()) + list(SIGNATURES_EXT.items()) + list(SIGNATURES_MEASURE.items())
-                                         + list(SIGNATURES_CURV.items()) + list(SIGNATURES_GAUSS.items()) + list(SIGNATURES_ISECT.items())):
+        for name, (res, args, reply) in [item for table in (SIGNATURES, *EXTENSION_HEADERS.values()) for item in table.items()]:
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             fn = handle[name]            # a function object of its own (handle.name is cached, handle[name] is not)
@@ -241,15 +231,20 @@ def set_arith(mode):
     return {0: 'f32', 1: 'bf16x3'}[api().icn_set_arith(ARITH_MODES[mode])]
 
 
-def source_sha256():
-    """sha256 over the kernel / library sources under csrc/, include/icn.h, include/icn_ext.h, include/icn_measure.h, include/icn_curvature.h, include/icn_gauss.h and include/icn_isect.h (names + contents, sorted): identifies the code a
-    profile was measured on (tools/profile_summary.py stores it, bench.py refuses a profile of other sources)."""
+def source_files():
+    """The files source_sha256() hashes, sorted: the kernel / library sources under csrc/, include/icn.h and every header of
+    EXTENSION_HEADERS."""
     import glob
+    headers = [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('icn.h', *EXTENSION_HEADERS)]
+    return sorted([f for pattern in ('*.hip', '*.h', '*.cpp') for f in glob.glob(os.path.join(_HERE, 'csrc', pattern))] + headers)
+
+
+def source_sha256():
+    """sha256 over source_files() (names + contents): identifies the code a profile was measured on (tools/profile_summary.py stores
+    it, bench.py refuses a profile of other sources)."""
     import hashlib
     h = hashlib.sha256()
-    files = sorted(glob.glob(os.path.join(_HERE, 'csrc', '*.hip')) + glob.glob(os.path.join(_HERE, 'csrc', '*.h'))
-                   + glob.glob(os.path.join(_HERE, 'csrc', '*.cpp')) + [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('icn.h', 'icn_ext.h', 'icn_measure.h', 'icn_curvature.h', 'icn_gauss.h', 'icn_isect.h')])
-    for f in files:
+    for f in source_files():
         h.update(os.path.basename(f).encode() + b'\0')
         h.update(open(f, 'rb').read())
     return h.hexdigest()

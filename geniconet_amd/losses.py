@@ -562,6 +562,10 @@ class Surface_Loss(torch.nn.Module):
         self.last_p2m = self.last_m2p = self.last_reg = self.last_loss_total = self.last_normal = 0
         self.last_volume = self.last_area = self.last_willmore = self.last_gauss = 0
 
+    def _vertex_face_table(self, device):
+        """The incidence table of the ico faces (the ico_vf_* buffers) on `device`."""
+        return tuple(t if t.device == device else t.to(device) for t in (self.ico_vf_offsets, self.ico_vf_corners))
+
     def _draw_uniforms(self, B, device):
         """The (2, B, S, 3) uniforms of one forward, from the generator seeded with sample_seed on the first forward's device."""
         if self._sample_generator is None or self._sample_generator.device != device:
@@ -608,7 +612,7 @@ class Surface_Loss(torch.nn.Module):
         self.last_volume = self.last_area = 0
         if self.factor_volume != 0 or self.factor_area != 0:                  # one forward serves both; a backward term per factor
             from .metrics import _mesh_area_volume_unchecked
-            table = tuple(t if t.device == out.device else t.to(out.device) for t in (self.ico_vf_offsets, self.ico_vf_corners))
+            table = self._vertex_face_table(out.device)
             area_out, vol_out = _mesh_area_volume_unchecked(out, faces, table)
             with torch.no_grad():
                 area_ref, vol_ref = _mesh_area_volume_unchecked(ref, faces)
@@ -623,14 +627,14 @@ class Surface_Loss(torch.nn.Module):
         self.last_willmore = 0
         if self.factor_willmore != 0:
             from .metrics import _willmore_energy_unchecked
-            table = tuple(t if t.device == out.device else t.to(out.device) for t in (self.ico_vf_offsets, self.ico_vf_corners))
+            table = self._vertex_face_table(out.device)
             l_w = _willmore_energy_unchecked(out, faces, table).mean()
             loss = loss + self.factor_willmore * l_w
             self.last_willmore = l_w.detach()
         self.last_gauss = 0
         if self.factor_gauss != 0:
             from .metrics import _angle_defect_unchecked
-            table = tuple(t if t.device == out.device else t.to(out.device) for t in (self.ico_vf_offsets, self.ico_vf_corners))
+            table = self._vertex_face_table(out.device)
             defect_out = _angle_defect_unchecked(out, faces, table)
             with torch.no_grad():
                 defect_ref = _angle_defect_unchecked(ref, faces, table)

@@ -61,6 +61,12 @@ import torch
 from . import _lib
 
 
+def _on_hip_path(vertices):
+    """Whether the mesh operators on `vertices` run on the HIP kernels: ROCm fp32 tensors, unless ICN_NO_HIP_LOSS=1."""
+    from . import losses
+    return not losses._NO_HIP_LOSS and vertices.is_cuda and vertices.dtype == torch.float32
+
+
 def _closest_on_triangles(p, a, b, c):
     """Squared distance + region of the closest point on triangles (a, b, c) for points p; all (..., 3), broadcastable.
     Region tests of Ericson, Real-Time Collision Detection 5.1.5 (Voronoi regions of the triangle's features), with the three
@@ -150,10 +156,64 @@ _MAX_GRID_Y = 65535
 
 
 def _batch_slices(B):
-    """(b0, nb) slices of a batch of B meshes: the batch index of the mesh kernels is gridDim.y, at most _MAX_GRID_Y per launch.
-    A caller's workspace is sized once for the largest slice, min(B, _MAX_GRID_Y), and reused in stream order."""
+    """(b0, nb) slices of a batch of B meshes: the batch index of the mesh kernels is gridDim.y, at most _MAX_GRID_Y per launch."""
     for b0 in range(0, B, _MAX_GRID_Y):
         yield b0, min(_MAX_GRID_Y, B - b0)
+
+
+_NB = object()                     # in the arguments of _launch: the mesh count of the slice, where the entry takes B
+
+
+class _per_mesh:
+    """Marks an argument of _launch as a contiguous (B, ...) tensor with one row per mesh, or None: a slice passes the address of
+    its first mesh, None stays null."""
+    __slots__ = ('tensor',)
+
+    def __init__(self, tensor):
+        self.tensor = tensor
+
+
+def _batch_of(args):
+    """The first per-mesh tensor among the arguments of _launch: its shape[0] is the batch, its device the call's."""
+    return next(a.tensor for a in args if isinstance(a, _per_mesh) and a.tensor is not None)
+
+
+def _slice_arguments(L, args, workspace=None):
+    """The marshalling of _launch, on tensors of any device -> (the C arguments of every slice of _batch_slices, ws_bytes).  Of args,
+    a _per_mesh tensor becomes the address of the slice's first mesh, any other tensor its address (a table the batch shares), _NB
+    the slice's mesh count; None is a null pointer and numbers pass as they are.  workspace = (query entry of L, its sizes after B)
+    is asked once, for the largest slice, min(B, _MAX_GRID_Y); ws_bytes is None without one."""
+    B = _batch_of(args).shape[0]
+    ws_bytes = getattr(L, workspace[0])(min(B, _MAX_GRID_Y), *workspace[1:]) if workspace else None
+
+    def argument(a, b0, nb):
+        if isinstance(a, _per_mesh):
+            t = a.tensor
+            return None if t is None else (t[b0:] if b0 else t).data_ptr()
+        return nb if a is _NB else a.data_ptr() if torch.is_tensor(a) else a
+    return [tuple(argument(a, b0, nb) for a in args) for b0, nb in _batch_slices(B)], ws_bytes
+
+
+def _launch(entry, *args, workspace=None):
+    """One call into the library per slice of the batch, on the device and the current stream of the per-mesh tensors: `entry` with
+    args in ABI order (see _slice_arguments), then, with workspace = (query entry, its sizes after B), a scratch buffer of that
+    size and its size -- one buffer, reused by the slices in stream order -- then the stream."""
+    L = _lib.api()
+    device = _batch_of(args).device
+    calls, ws_bytes = _slice_arguments(L, args, workspace)
+    tail = ()
+    if workspace:
+        ws = _lib.workspace(ws_bytes, device)
+        tail = (ws.data_ptr(), ws_bytes)
+    fn = getattr(L, entry)
+    with torch.cuda.device(device):
+        for call in calls:
+            fn(*call, *tail, _lib.stream())
+
+
+def _upstream(grad):
+    """An upstream gradient as the kernels read it (contiguous fp32); None, an output nobody differentiated, stays None."""
+    return None if grad is None else grad.contiguous().to(torch.float32)
 
 
 _SEARCHES = ('brute', 'grid')
@@ -167,25 +227,16 @@ def _check_search(search):
 def _hip_point_to_mesh(pts, vts, f32, search='brute'):
     """icn_point_to_mesh (search 'brute') or icn_point_to_mesh_grid ('grid') on contiguous fp32 ROCm tensors and int32 faces
     -> (dist, face int32, kind)."""
-    L = _lib.api()
     B, P, _ = pts.shape
     V, F = vts.shape[1], f32.shape[0]
     dist = torch.empty(B, P, dtype=torch.float32, device=pts.device)
     face = torch.empty(B, P, dtype=torch.int32, device=pts.device)
     kind = torch.empty(B, P, dtype=torch.int32, device=pts.device)
-    ws, ws_bytes = None, 0
-    with torch.cuda.device(pts.device):
-        for b0, nb in _batch_slices(B):
-            if search == 'grid':
-                if ws is None:
-                    ws_bytes = L.icn_point_to_mesh_grid_workspace_bytes(min(B, _MAX_GRID_Y), P, V, F)
-                    ws = _lib.workspace(ws_bytes, pts.device)
-                L.icn_point_to_mesh_grid(pts[b0:].data_ptr(), vts[b0:].data_ptr(), f32.data_ptr(), nb, P, V, F,
-                                         dist[b0:].data_ptr(), face[b0:].data_ptr(), kind[b0:].data_ptr(), ws.data_ptr(),
-                                         ws_bytes, _lib.stream())
-                continue
-            L.icn_point_to_mesh(pts[b0:].data_ptr(), vts[b0:].data_ptr(), f32.data_ptr(), nb, P, V, F,
-                                dist[b0:].data_ptr(), face[b0:].data_ptr(), kind[b0:].data_ptr(), _lib.stream())
+    args = (_per_mesh(pts), _per_mesh(vts), f32, _NB, P, V, F, _per_mesh(dist), _per_mesh(face), _per_mesh(kind))
+    if search == 'grid':
+        _launch('icn_point_to_mesh_grid', *args, workspace=('icn_point_to_mesh_grid_workspace_bytes', P, V, F))
+    else:
+        _launch('icn_point_to_mesh', *args)
     return dist, face, kind
 
 
@@ -207,21 +258,16 @@ class _PointToMeshFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, ddist, _gface, _gkind):
-        L = _lib.api()
         pts, vts, f32, face, kind = ctx.saved_tensors
-        (B, P, _), V, F = pts.shape, vts.shape[1], f32.shape[0]
-        up = ddist.contiguous().to(torch.float32)
+        P, V, F = pts.shape[1], vts.shape[1], f32.shape[0]
         dpts = torch.empty_like(pts) if ctx.needs_input_grad[0] else None
         dvts = torch.empty_like(vts) if ctx.needs_input_grad[1] else None
-        ws_bytes = L.icn_point_to_mesh_bwd_workspace_bytes(min(B, _MAX_GRID_Y), P, V, F) if dvts is not None else 0
-        ws = _lib.workspace(ws_bytes, pts.device) if ws_bytes else None
-        with torch.cuda.device(pts.device):
-            for b0, nb in _batch_slices(B):
-                L.icn_point_to_mesh_bwd(pts[b0:].data_ptr(), vts[b0:].data_ptr(), f32.data_ptr(), face[b0:].data_ptr(),
-                                        kind[b0:].data_ptr(), up[b0:].data_ptr(), nb, P, V, F,
-                                        dpts[b0:].data_ptr() if dpts is not None else None,
-                                        dvts[b0:].data_ptr() if dvts is not None else None,
-                                        ws.data_ptr() if ws is not None else None, ws_bytes, _lib.stream())
+        args = (_per_mesh(pts), _per_mesh(vts), f32, _per_mesh(face), _per_mesh(kind), _per_mesh(_upstream(ddist)), _NB, P, V, F,
+                _per_mesh(dpts), _per_mesh(dvts))
+        if dvts is not None:                                                              # only the vertex gradient needs scratch
+            _launch('icn_point_to_mesh_bwd', *args, workspace=('icn_point_to_mesh_bwd_workspace_bytes', P, V, F))
+        else:
+            _launch('icn_point_to_mesh_bwd', *args, None, 0)
         return dpts, dvts, None, None
 
 
@@ -297,14 +343,10 @@ def _torch_face_normal_agreement(vertices_a, faces_a, face_a, vertices_b, faces_
 
 def _hip_face_normal_agreement(va, fa32, face_a, vb, fb32, face_b, oriented):
     """icn_face_normal_agree_fwd on contiguous fp32 ROCm vertices, int32 face tables and int32 (B, S) face ids -> t (B, S)."""
-    L = _lib.api()
-    (B, S), Va, Vb, Fa, Fb = face_a.shape, va.shape[1], vb.shape[1], fa32.shape[0], fb32.shape[0]
+    B, S = face_a.shape
     t = torch.empty(B, S, dtype=torch.float32, device=va.device)
-    with torch.cuda.device(va.device):
-        for b0, nb in _batch_slices(B):
-            L.icn_face_normal_agree_fwd(va[b0:].data_ptr(), fa32.data_ptr(), face_a[b0:].data_ptr(), Va, Fa, vb[b0:].data_ptr(),
-                                        fb32.data_ptr(), face_b[b0:].data_ptr(), Vb, Fb, nb, S, int(oriented), t[b0:].data_ptr(),
-                                        _lib.stream())
+    _launch('icn_face_normal_agree_fwd', _per_mesh(va), fa32, _per_mesh(face_a), va.shape[1], fa32.shape[0],
+            _per_mesh(vb), fb32, _per_mesh(face_b), vb.shape[1], fb32.shape[0], _NB, S, int(oriented), _per_mesh(t))
     return t
 
 
@@ -323,22 +365,15 @@ class _FaceNormalAgreementFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dt):
-        L = _lib.api()
         va, fa32, ia, vb, fb32, ib = ctx.saved_tensors
-        (B, S), Va, Vb, Fa, Fb = ia.shape, va.shape[1], vb.shape[1], fa32.shape[0], fb32.shape[0]
-        up = dt.contiguous().to(torch.float32)
+        S, Va, Vb = ia.shape[1], va.shape[1], vb.shape[1]
         dva = torch.empty_like(va) if ctx.needs_input_grad[0] else None
         dvb = torch.empty_like(vb) if ctx.needs_input_grad[3] else None
         if dva is None and dvb is None:
             return (None,) * 7
-        ws_bytes = L.icn_face_normal_agree_bwd_workspace_bytes(min(B, _MAX_GRID_Y), S, Va, Vb)
-        ws = _lib.workspace(ws_bytes, va.device)
-        with torch.cuda.device(va.device):
-            for b0, nb in _batch_slices(B):
-                L.icn_face_normal_agree_bwd(va[b0:].data_ptr(), fa32.data_ptr(), ia[b0:].data_ptr(), Va, Fa, vb[b0:].data_ptr(),
-                                            fb32.data_ptr(), ib[b0:].data_ptr(), Vb, Fb, nb, S, ctx.oriented, up[b0:].data_ptr(),
-                                            dva[b0:].data_ptr() if dva is not None else None,
-                                            dvb[b0:].data_ptr() if dvb is not None else None, ws.data_ptr(), ws_bytes, _lib.stream())
+        _launch('icn_face_normal_agree_bwd', _per_mesh(va), fa32, _per_mesh(ia), Va, fa32.shape[0], _per_mesh(vb), fb32, _per_mesh(ib),
+                Vb, fb32.shape[0], _NB, S, ctx.oriented, _per_mesh(_upstream(dt)), _per_mesh(dva), _per_mesh(dvb),
+                workspace=('icn_face_normal_agree_bwd_workspace_bytes', S, Va, Vb))
         return dva, None, None, dvb, None, None, None
 
 
@@ -346,8 +381,7 @@ def _face_normal_agreement_unchecked(vertices_a, fa32, face_a, vertices_b, fb32,
     """face_normal_agreement without its argument checks and without a host synchronisation, for callers that validated once
     (losses.Surface_Loss): fa32 / fb32 are int32 (F, 3) tensors on the vertices' device, F >= 1; face_a / face_b (B, S) integer
     tensors there.  Ids out of range are safe on either path: such a sample is unresolved (t = 1, no gradient)."""
-    from . import losses
-    if (not losses._NO_HIP_LOSS and vertices_a.is_cuda and vertices_a.dtype == torch.float32 and vertices_b.dtype == torch.float32):
+    if _on_hip_path(vertices_a) and vertices_b.dtype == torch.float32:
         if torch.is_grad_enabled() and (vertices_a.requires_grad or vertices_b.requires_grad):
             return _FaceNormalAgreementFn.apply(vertices_a, fa32, face_a, vertices_b, fb32, face_b, bool(oriented))
         return _hip_face_normal_agreement(vertices_a.detach().contiguous(), fa32, face_a.to(torch.int32).contiguous(),
@@ -447,61 +481,79 @@ def _torch_mesh_area_volume(vertices, faces):
 
 def _hip_mesh_area_volume(vts, f32):
     """icn_mesh_measure_fwd on contiguous fp32 ROCm vertices and an int32 face table -> (area (B,), volume (B,))."""
-    L = _lib.api()
     B, V, F = vts.shape[0], vts.shape[1], f32.shape[0]
     area = torch.empty(B, dtype=torch.float32, device=vts.device)
     volume = torch.empty(B, dtype=torch.float32, device=vts.device)
-    ws_bytes = L.icn_mesh_measure_workspace_bytes(min(B, _MAX_GRID_Y), V, F)
-    ws = _lib.workspace(ws_bytes, vts.device)
-    with torch.cuda.device(vts.device):
-        for b0, nb in _batch_slices(B):
-            L.icn_mesh_measure_fwd(vts[b0:].data_ptr(), f32.data_ptr(), nb, V, F, area[b0:].data_ptr(), volume[b0:].data_ptr(),
-                                   ws.data_ptr(), ws_bytes, _lib.stream())
+    _launch('icn_mesh_measure_fwd', _per_mesh(vts), f32, _NB, V, F, _per_mesh(area), _per_mesh(volume),
+            workspace=('icn_mesh_measure_workspace_bytes', V, F))
     return area, volume
 
 
-class _MeshMeasureFn(torch.autograd.Function):
-    """mesh_area_volume on the HIP path (icn_mesh_measure_fwd / _bwd in include/icn_measure.h).  The backward is one gather over the
-    vertex -> corner incidence table (built here when the caller passed none), summed in a fixed order: bit-identical run to run.
-    An output nobody differentiates sends no gradient and its term is skipped."""
+class _VertexGatherFn(torch.autograd.Function):
+    """mesh_area_volume, cotangent_laplacian and angle_defect on the HIP path: hip_forward(vts, f32, offsets, corners) gives the
+    outputs, and the backward entries (icn_mesh_measure_bwd, icn_mesh_cotlap_bwd, icn_mesh_angle_defect_bwd) share one argument
+    list -- vertices, the three tables, one upstream per output, sizes, dvertices -- and one method: a gather over the vertex -> corner
+    incidence table (built in the backward when the caller passed none), summed in a fixed order: bit-identical run to run.  An
+    output nobody differentiates sends no gradient and its term is skipped; when none arrives at all, nothing is launched if
+    skip_unused, else the entry writes zeros."""
 
     @staticmethod
-    def forward(ctx, vertices, f32, offsets, corners):
+    def forward(ctx, vertices, f32, offsets, corners, hip_forward, backward_entry, skip_unused):
         vts = vertices.contiguous()
         ctx.save_for_backward(vts, f32, offsets, corners)
         ctx.set_materialize_grads(False)
-        return _hip_mesh_area_volume(vts, f32)
+        ctx.backward_entry, ctx.skip_unused = backward_entry, skip_unused
+        return hip_forward(vts, f32, offsets, corners)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, darea, dvolume):
-        L = _lib.api()
+    def backward(ctx, *upstreams):
+        if ctx.skip_unused and all(u is None for u in upstreams):
+            return (None,) * 7
         vts, f32, offsets, corners = ctx.saved_tensors
-        B, V, F = vts.shape[0], vts.shape[1], f32.shape[0]
+        V, F = vts.shape[1], f32.shape[0]
         if offsets is None:
             offsets, corners = vertex_face_table(f32, V)
-        da = darea.contiguous().to(torch.float32) if darea is not None else None
-        dv = dvolume.contiguous().to(torch.float32) if dvolume is not None else None
         dvts = torch.empty_like(vts)
-        with torch.cuda.device(vts.device):
-            for b0, nb in _batch_slices(B):
-                L.icn_mesh_measure_bwd(vts[b0:].data_ptr(), f32.data_ptr(), offsets.data_ptr(), corners.data_ptr(),
-                                       da[b0:].data_ptr() if da is not None else None,
-                                       dv[b0:].data_ptr() if dv is not None else None, nb, V, F, dvts[b0:].data_ptr(), _lib.stream())
-        return dvts, None, None, None
+        _launch(ctx.backward_entry, _per_mesh(vts), f32, offsets, corners, *(_per_mesh(_upstream(u)) for u in upstreams), _NB, V, F,
+                _per_mesh(dvts))
+        return (dvts,) + (None,) * 6
 
 
 def _mesh_area_volume_unchecked(vertices, f32, table=None):
     """mesh_area_volume without its argument checks and without a host synchronisation, for callers that validated once
     (losses.Surface_Loss): f32 is an int32 (F, 3) tensor on the vertices' device, F >= 1; table = vertex_face_table(f32, V) on that
     device, or None (built in the backward).  A vertex id out of range is safe on either path: that face contributes nothing."""
-    from . import losses
-    if not losses._NO_HIP_LOSS and vertices.is_cuda and vertices.dtype == torch.float32:
+    if _on_hip_path(vertices):
         if torch.is_grad_enabled() and vertices.requires_grad:
             offsets, corners = table if table is not None else (None, None)
-            return _MeshMeasureFn.apply(vertices, f32, offsets, corners)
+            return _VertexGatherFn.apply(vertices, f32, offsets, corners, lambda vts, faces, *_: _hip_mesh_area_volume(vts, faces),
+                                         'icn_mesh_measure_bwd', False)
         return _hip_mesh_area_volume(vertices.detach().contiguous(), f32)
     return _torch_mesh_area_volume(vertices, f32)
+
+
+def _check_mesh_arguments(who, vertices, faces, table):
+    """The argument checks of the mesh operators for `who`: shapes (ValueError), face ids against V with one read-back (IndexError),
+    the table's shapes -> (int32 faces on the vertices' device, the table there or None)."""
+    if vertices.dim() != 3 or vertices.shape[-1] != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1 or not vertices.is_floating_point():
+        raise ValueError('%s: expected floating-point vertices (B, V, 3), got %s' % (who, tuple(vertices.shape)))
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1 or faces.is_floating_point() or faces.dtype == torch.bool:
+        raise ValueError('%s: expected integer faces (F, 3) with F >= 1, got %s' % (who, tuple(faces.shape)))
+    V, F = vertices.shape[1], faces.shape[0]
+    if 3 * F > 0x7fffffff:
+        raise ValueError('%s: %d faces: 3 F must fit an int32' % (who, F))
+    dev = vertices.device
+    if table is not None:
+        if (not isinstance(table, (tuple, list)) or len(table) != 2 or any(not torch.is_tensor(x) or x.dtype != torch.int32 for x in table)
+                or tuple(table[0].shape) != (V + 1,) or tuple(table[1].shape) != (3 * F,)):
+            raise ValueError('%s: table must be vertex_face_table(faces, %d): int32 tensors (%d,) and (%d,)' % (who, V, V + 1, 3 * F))
+        table = tuple(x.to(dev).contiguous() for x in table)
+    f32 = faces.to(device=dev, dtype=torch.int32).contiguous()
+    lo, hi = (int(x) for x in f32.aminmax())
+    if lo < 0 or hi >= V:
+        raise IndexError('%s: faces index [%d, %d] but there are %d vertices' % (who, lo, hi, V))
+    return f32, table
 
 
 def mesh_area_volume(vertices, faces, table=None):
@@ -526,24 +578,7 @@ def mesh_area_volume(vertices, faces, table=None):
     order without atomics (bit-identical run to run, an exact zero at a vertex no face references).  ICN_NO_HIP_LOSS=1, CPU
     tensors and other dtypes take the torch formulation through autograd.
     Shapes are checked (ValueError); face ids against V with one read-back (IndexError)."""
-    who = 'mesh_area_volume'
-    if vertices.dim() != 3 or vertices.shape[-1] != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1 or not vertices.is_floating_point():
-        raise ValueError('%s: expected floating-point vertices (B, V, 3), got %s' % (who, tuple(vertices.shape)))
-    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1 or faces.is_floating_point() or faces.dtype == torch.bool:
-        raise ValueError('%s: expected integer faces (F, 3) with F >= 1, got %s' % (who, tuple(faces.shape)))
-    V, F = vertices.shape[1], faces.shape[0]
-    if 3 * F > 0x7fffffff:
-        raise ValueError('%s: %d faces: 3 F must fit an int32' % (who, F))
-    dev = vertices.device
-    if table is not None:
-        if (not isinstance(table, (tuple, list)) or len(table) != 2 or any(not torch.is_tensor(x) or x.dtype != torch.int32 for x in table)
-                or tuple(table[0].shape) != (V + 1,) or tuple(table[1].shape) != (3 * F,)):
-            raise ValueError('%s: table must be vertex_face_table(faces, %d): int32 tensors (%d,) and (%d,)' % (who, V, V + 1, 3 * F))
-        table = tuple(x.to(dev).contiguous() for x in table)
-    f32 = faces.to(device=dev, dtype=torch.int32).contiguous()
-    lo, hi = (int(x) for x in f32.aminmax())
-    if lo < 0 or hi >= V:
-        raise IndexError('%s: faces index [%d, %d] but there are %d vertices' % (who, lo, hi, V))
+    f32, table = _check_mesh_arguments('mesh_area_volume', vertices, faces, table)
     return _mesh_area_volume_unchecked(vertices, f32, table)
 
 
@@ -600,67 +635,36 @@ def _torch_willmore_energy(vertices, faces):
     return _willmore_from(*_torch_cotangent_laplacian(vertices, faces))
 
 
-def _hip_curvature(vts, f32, offsets, corners, energy):
-    """icn_mesh_cotlap_fwd (energy False) or icn_mesh_willmore_fwd on contiguous fp32 ROCm vertices, an int32 face table and its
-    incidence table -> (lap (B, V, 3), varea (B, V), energy (B,) or None)."""
-    L = _lib.api()
+def _hip_cotangent_laplacian(vts, f32, offsets, corners):
+    """icn_mesh_cotlap_fwd on contiguous fp32 ROCm vertices, an int32 face table and its incidence table -> (lap (B, V, 3), varea
+    (B, V))."""
     B, V, F = vts.shape[0], vts.shape[1], f32.shape[0]
     lap = torch.empty_like(vts)
     varea = torch.empty(B, V, dtype=torch.float32, device=vts.device)
-    tables = (f32.data_ptr(), offsets.data_ptr(), corners.data_ptr())
-    with torch.cuda.device(vts.device):
-        if not energy:
-            for b0, nb in _batch_slices(B):
-                L.icn_mesh_cotlap_fwd(vts[b0:].data_ptr(), *tables, nb, V, F, lap[b0:].data_ptr(), varea[b0:].data_ptr(), _lib.stream())
-            return lap, varea, None
-        out = torch.empty(B, dtype=torch.float32, device=vts.device)
-        ws_bytes = L.icn_mesh_willmore_workspace_bytes(min(B, _MAX_GRID_Y), V, F)
-        ws = _lib.workspace(ws_bytes, vts.device)
-        for b0, nb in _batch_slices(B):
-            L.icn_mesh_willmore_fwd(vts[b0:].data_ptr(), *tables, nb, V, F, lap[b0:].data_ptr(), varea[b0:].data_ptr(),
-                                    out[b0:].data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream())
-    return lap, varea, out
+    _launch('icn_mesh_cotlap_fwd', _per_mesh(vts), f32, offsets, corners, _NB, V, F, _per_mesh(lap), _per_mesh(varea))
+    return lap, varea
 
 
-class _CotLapFn(torch.autograd.Function):
-    """cotangent_laplacian on the HIP path (icn_mesh_cotlap_fwd / _bwd in include/icn_curvature.h): both directions are one gather
-    over the vertex -> corner incidence table, summed in a fixed order: bit-identical run to run.  An output nobody differentiates
-    sends no gradient and its term is skipped; with neither nothing is launched."""
-
-    @staticmethod
-    def forward(ctx, vertices, f32, offsets, corners):
-        vts = vertices.contiguous()
-        ctx.save_for_backward(vts, f32, offsets, corners)
-        ctx.set_materialize_grads(False)
-        return _hip_curvature(vts, f32, offsets, corners, False)[:2]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dlap, dvarea):
-        if dlap is None and dvarea is None:
-            return None, None, None, None
-        L = _lib.api()
-        vts, f32, offsets, corners = ctx.saved_tensors
-        B, V, F = vts.shape[0], vts.shape[1], f32.shape[0]
-        dl = dlap.contiguous().to(torch.float32) if dlap is not None else None
-        da = dvarea.contiguous().to(torch.float32) if dvarea is not None else None
-        dvts = torch.empty_like(vts)
-        with torch.cuda.device(vts.device):
-            for b0, nb in _batch_slices(B):
-                L.icn_mesh_cotlap_bwd(vts[b0:].data_ptr(), f32.data_ptr(), offsets.data_ptr(), corners.data_ptr(),
-                                      dl[b0:].data_ptr() if dl is not None else None,
-                                      da[b0:].data_ptr() if da is not None else None, nb, V, F, dvts[b0:].data_ptr(), _lib.stream())
-        return dvts, None, None, None
+def _hip_willmore_energy(vts, f32, offsets, corners):
+    """icn_mesh_willmore_fwd, arguments as _hip_cotangent_laplacian -> (lap (B, V, 3), varea (B, V), energy (B,))."""
+    B, V, F = vts.shape[0], vts.shape[1], f32.shape[0]
+    lap = torch.empty_like(vts)
+    varea = torch.empty(B, V, dtype=torch.float32, device=vts.device)
+    energy = torch.empty(B, dtype=torch.float32, device=vts.device)
+    _launch('icn_mesh_willmore_fwd', _per_mesh(vts), f32, offsets, corners, _NB, V, F, _per_mesh(lap), _per_mesh(varea),
+            _per_mesh(energy), workspace=('icn_mesh_willmore_workspace_bytes', V, F))
+    return lap, varea, energy
 
 
 class _WillmoreFn(torch.autograd.Function):
     """willmore_energy on the HIP path (icn_mesh_willmore_fwd / _bwd in include/icn_curvature.h).  The forward keeps lap and varea for
-    the backward: the per-vertex upstreams, then the gather of icn_mesh_cotlap_bwd; a fixed order, bit-identical run to run."""
+    the backward: the per-vertex upstreams, then the gather of icn_mesh_cotlap_bwd; a fixed order, bit-identical run to run.  When no
+    gradient arrives nothing is launched."""
 
     @staticmethod
     def forward(ctx, vertices, f32, offsets, corners):
         vts = vertices.contiguous()
-        lap, varea, energy = _hip_curvature(vts, f32, offsets, corners, True)
+        lap, varea, energy = _hip_willmore_energy(vts, f32, offsets, corners)
         ctx.save_for_backward(vts, f32, offsets, corners, lap, varea)
         ctx.set_materialize_grads(False)
         return energy
@@ -670,24 +674,12 @@ class _WillmoreFn(torch.autograd.Function):
     def backward(ctx, denergy):
         if denergy is None:
             return None, None, None, None
-        L = _lib.api()
         vts, f32, offsets, corners, lap, varea = ctx.saved_tensors
-        B, V, F = vts.shape[0], vts.shape[1], f32.shape[0]
-        de = denergy.contiguous().to(torch.float32)
+        V, F = vts.shape[1], f32.shape[0]
         dvts = torch.empty_like(vts)
-        ws_bytes = L.icn_mesh_willmore_workspace_bytes(min(B, _MAX_GRID_Y), V, F)
-        ws = _lib.workspace(ws_bytes, vts.device)
-        with torch.cuda.device(vts.device):
-            for b0, nb in _batch_slices(B):
-                L.icn_mesh_willmore_bwd(vts[b0:].data_ptr(), f32.data_ptr(), offsets.data_ptr(), corners.data_ptr(), lap[b0:].data_ptr(),
-                                        varea[b0:].data_ptr(), de[b0:].data_ptr(), nb, V, F, dvts[b0:].data_ptr(), ws.data_ptr(),
-                                        ws_bytes, _lib.stream())
+        _launch('icn_mesh_willmore_bwd', _per_mesh(vts), f32, offsets, corners, _per_mesh(lap), _per_mesh(varea),
+                _per_mesh(_upstream(denergy)), _NB, V, F, _per_mesh(dvts), workspace=('icn_mesh_willmore_workspace_bytes', V, F))
         return dvts, None, None, None
-
-
-def _on_hip_path(vertices):
-    from . import losses
-    return not losses._NO_HIP_LOSS and vertices.is_cuda and vertices.dtype == torch.float32
 
 
 def _cotangent_laplacian_unchecked(vertices, f32, table=None):
@@ -697,8 +689,8 @@ def _cotangent_laplacian_unchecked(vertices, f32, table=None):
     if _on_hip_path(vertices):
         offsets, corners = table if table is not None else vertex_face_table(f32, vertices.shape[1])
         if torch.is_grad_enabled() and vertices.requires_grad:
-            return _CotLapFn.apply(vertices, f32, offsets, corners)
-        return _hip_curvature(vertices.detach().contiguous(), f32, offsets, corners, False)[:2]
+            return _VertexGatherFn.apply(vertices, f32, offsets, corners, _hip_cotangent_laplacian, 'icn_mesh_cotlap_bwd', True)
+        return _hip_cotangent_laplacian(vertices.detach().contiguous(), f32, offsets, corners)
     return _torch_cotangent_laplacian(vertices, f32)
 
 
@@ -709,31 +701,8 @@ def _willmore_energy_unchecked(vertices, f32, table=None):
         offsets, corners = table if table is not None else vertex_face_table(f32, vertices.shape[1])
         if torch.is_grad_enabled() and vertices.requires_grad:
             return _WillmoreFn.apply(vertices, f32, offsets, corners)
-        return _hip_curvature(vertices.detach().contiguous(), f32, offsets, corners, True)[2]
+        return _hip_willmore_energy(vertices.detach().contiguous(), f32, offsets, corners)[2]
     return _torch_willmore_energy(vertices, f32)
-
-
-def _check_mesh_arguments(who, vertices, faces, table):
-    """The argument checks of mesh_area_volume for `who`: shapes (ValueError), face ids against V with one read-back (IndexError), the
-    table's shapes -> (int32 faces on the vertices' device, the table there or None)."""
-    if vertices.dim() != 3 or vertices.shape[-1] != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1 or not vertices.is_floating_point():
-        raise ValueError('%s: expected floating-point vertices (B, V, 3), got %s' % (who, tuple(vertices.shape)))
-    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1 or faces.is_floating_point() or faces.dtype == torch.bool:
-        raise ValueError('%s: expected integer faces (F, 3) with F >= 1, got %s' % (who, tuple(faces.shape)))
-    V, F = vertices.shape[1], faces.shape[0]
-    if 3 * F > 0x7fffffff:
-        raise ValueError('%s: %d faces: 3 F must fit an int32' % (who, F))
-    dev = vertices.device
-    if table is not None:
-        if (not isinstance(table, (tuple, list)) or len(table) != 2 or any(not torch.is_tensor(x) or x.dtype != torch.int32 for x in table)
-                or tuple(table[0].shape) != (V + 1,) or tuple(table[1].shape) != (3 * F,)):
-            raise ValueError('%s: table must be vertex_face_table(faces, %d): int32 tensors (%d,) and (%d,)' % (who, V, V + 1, 3 * F))
-        table = tuple(x.to(dev).contiguous() for x in table)
-    f32 = faces.to(device=dev, dtype=torch.int32).contiguous()
-    lo, hi = (int(x) for x in f32.aminmax())
-    if lo < 0 or hi >= V:
-        raise IndexError('%s: faces index [%d, %d] but there are %d vertices' % (who, lo, hi, V))
-    return f32, table
 
 
 def cotangent_laplacian(vertices, faces, table=None):
@@ -811,43 +780,10 @@ def _torch_angle_defect(vertices, faces):
 
 def _hip_angle_defect(vts, f32, offsets, corners):
     """icn_mesh_angle_defect_fwd on contiguous fp32 ROCm vertices, an int32 face table and its incidence table -> defect (B, V)."""
-    L = _lib.api()
     B, V, F = vts.shape[0], vts.shape[1], f32.shape[0]
     defect = torch.empty(B, V, dtype=torch.float32, device=vts.device)
-    with torch.cuda.device(vts.device):
-        for b0, nb in _batch_slices(B):
-            L.icn_mesh_angle_defect_fwd(vts[b0:].data_ptr(), f32.data_ptr(), offsets.data_ptr(), corners.data_ptr(), nb, V, F,
-                                        defect[b0:].data_ptr(), _lib.stream())
+    _launch('icn_mesh_angle_defect_fwd', _per_mesh(vts), f32, offsets, corners, _NB, V, F, _per_mesh(defect))
     return defect
-
-
-class _AngleDefectFn(torch.autograd.Function):
-    """angle_defect on the HIP path (icn_mesh_angle_defect_fwd / _bwd in include/icn_gauss.h): both directions are one gather over the
-    vertex -> corner incidence table in double, summed in a fixed order: bit-identical run to run.  When no gradient arrives
-    nothing is launched."""
-
-    @staticmethod
-    def forward(ctx, vertices, f32, offsets, corners):
-        vts = vertices.contiguous()
-        ctx.save_for_backward(vts, f32, offsets, corners)
-        ctx.set_materialize_grads(False)
-        return _hip_angle_defect(vts, f32, offsets, corners)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, ddefect):
-        if ddefect is None:
-            return None, None, None, None
-        L = _lib.api()
-        vts, f32, offsets, corners = ctx.saved_tensors
-        B, V, F = vts.shape[0], vts.shape[1], f32.shape[0]
-        dd = ddefect.contiguous().to(torch.float32)
-        dvts = torch.empty_like(vts)
-        with torch.cuda.device(vts.device):
-            for b0, nb in _batch_slices(B):
-                L.icn_mesh_angle_defect_bwd(vts[b0:].data_ptr(), f32.data_ptr(), offsets.data_ptr(), corners.data_ptr(),
-                                            dd[b0:].data_ptr(), nb, V, F, dvts[b0:].data_ptr(), _lib.stream())
-        return dvts, None, None, None
 
 
 def _angle_defect_unchecked(vertices, f32, table=None):
@@ -856,7 +792,7 @@ def _angle_defect_unchecked(vertices, f32, table=None):
     if _on_hip_path(vertices):
         offsets, corners = table if table is not None else vertex_face_table(f32, vertices.shape[1])
         if torch.is_grad_enabled() and vertices.requires_grad:
-            return _AngleDefectFn.apply(vertices, f32, offsets, corners)
+            return _VertexGatherFn.apply(vertices, f32, offsets, corners, _hip_angle_defect, 'icn_mesh_angle_defect_bwd', True)
         return _hip_angle_defect(vertices.detach().contiguous(), f32, offsets, corners)
     return _torch_angle_defect(vertices, f32)
 
@@ -999,12 +935,9 @@ def _torch_self_intersections(vertices, faces, chunk=None):
 
 def _hip_self_intersections(vts, f32):
     """icn_mesh_self_intersect on contiguous fp32 ROCm vertices and an int32 face table -> hits (B, F) int32."""
-    L = _lib.api()
     B, V, F = vts.shape[0], vts.shape[1], f32.shape[0]
     hits = torch.empty(B, F, dtype=torch.int32, device=vts.device)
-    with torch.cuda.device(vts.device):
-        for b0, nb in _batch_slices(B):
-            L.icn_mesh_self_intersect(vts[b0:].data_ptr(), f32.data_ptr(), nb, V, F, hits[b0:].data_ptr(), _lib.stream())
+    _launch('icn_mesh_self_intersect', _per_mesh(vts), f32, _NB, V, F, _per_mesh(hits))
     return hits
 
 

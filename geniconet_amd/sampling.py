@@ -19,7 +19,8 @@ ROCm fp32 tensors run on the HIP kernels; CPU tensors, other dtypes and ICN_NO_H
 float64, searchsorted(..., right=True)), which computes areas, weights and points in the dtype of `vertices`."""
 import torch
 
-from . import _lib, metrics
+from . import metrics
+from .metrics import _NB, _launch, _per_mesh
 
 
 def _face_areas(vertices, f):
@@ -56,31 +57,21 @@ def _torch_sample(vertices, faces, u):
 
 def _hip_sample(vts, f32, u):
     """icn_mesh_sample_fwd on contiguous fp32 ROCm tensors and int32 faces -> (points, face int32, weights)."""
-    L = _lib.api()
     (B, V, _), S, F = vts.shape, u.shape[1], f32.shape[0]
     points = torch.empty(B, S, 3, dtype=torch.float32, device=vts.device)
     face = torch.empty(B, S, dtype=torch.int32, device=vts.device)
     weights = torch.empty(B, S, 3, dtype=torch.float32, device=vts.device)
-    ws_bytes = L.icn_mesh_sample_workspace_bytes(min(B, metrics._MAX_GRID_Y), S, V, F)
-    ws = _lib.workspace(ws_bytes, vts.device)
-    with torch.cuda.device(vts.device):
-        for b0, nb in metrics._batch_slices(B):
-            L.icn_mesh_sample_fwd(vts[b0:].data_ptr(), f32.data_ptr(), u[b0:].data_ptr(), nb, S, V, F, points[b0:].data_ptr(),
-                                  face[b0:].data_ptr(), weights[b0:].data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream())
+    _launch('icn_mesh_sample_fwd', _per_mesh(vts), f32, _per_mesh(u), _NB, S, V, F, _per_mesh(points), _per_mesh(face),
+            _per_mesh(weights), workspace=('icn_mesh_sample_workspace_bytes', S, V, F))
     return points, face, weights
 
 
 def _hip_sample_bwd(f32, face, weights, dpoints, V):
     """icn_mesh_sample_bwd -> dvertices (B, V, 3); face int32 (B, S), weights / dpoints contiguous fp32 (B, S, 3)."""
-    L = _lib.api()
     (B, S), F = face.shape, f32.shape[0]
     dvts = torch.empty(B, V, 3, dtype=torch.float32, device=face.device)
-    ws_bytes = L.icn_mesh_sample_bwd_workspace_bytes(min(B, metrics._MAX_GRID_Y), S, V, F)
-    ws = _lib.workspace(ws_bytes, face.device)
-    with torch.cuda.device(face.device):
-        for b0, nb in metrics._batch_slices(B):
-            L.icn_mesh_sample_bwd(f32.data_ptr(), face[b0:].data_ptr(), weights[b0:].data_ptr(), dpoints[b0:].data_ptr(), nb, S, V,
-                                  F, dvts[b0:].data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream())
+    _launch('icn_mesh_sample_bwd', f32, _per_mesh(face), _per_mesh(weights), _per_mesh(dpoints), _NB, S, V, F, _per_mesh(dvts),
+            workspace=('icn_mesh_sample_bwd_workspace_bytes', S, V, F))
     return dvts
 
 
@@ -107,8 +98,7 @@ def _sample_points_unchecked(vertices, f32, uniforms):
     """sample_points without its argument checks and without a host synchronisation, for callers that validated once
     (losses.Surface_Loss): f32 is an int32 (F, 3) tensor on the vertices' device, F >= 1, with indices in [0, V); uniforms (B, S, 3)
     on the same device.  -> (points, face int64, weights)."""
-    from . import losses
-    if (not losses._NO_HIP_LOSS and vertices.is_cuda and vertices.dtype == torch.float32 and uniforms.dtype == torch.float32):
+    if metrics._on_hip_path(vertices) and uniforms.dtype == torch.float32:
         if torch.is_grad_enabled() and vertices.requires_grad:
             return _SamplePointsFn.apply(vertices, f32, uniforms)
         points, face, weights = _hip_sample(vertices.detach().contiguous(), f32, uniforms.detach().contiguous())

@@ -79,9 +79,9 @@ def test_arithmetic_mode_and_build_flags_are_host_only():
 
 
 # ---- the binding against the header, prototype by prototype ---------------------------------------------------------------
-def declared_prototypes():
-    """name -> (return type, [argument declarations]) of every icn_* function include/icn.h declares."""
-    src = open(os.path.join(ROOT, 'include', 'icn.h')).read()
+def declared_prototypes(header='icn.h'):
+    """name -> (return type, [argument declarations]) of every icn_* function the header of include/ itself declares."""
+    src = open(os.path.join(ROOT, 'include', header)).read()
     src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
     src = '\n'.join(line for line in src.split('\n') if not line.lstrip().startswith('#'))
     protos = {}

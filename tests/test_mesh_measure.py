@@ -413,6 +413,30 @@ def test_hip_exact_zero_at_an_unreferenced_vertex():
     assert torch.equal(g[:, :-1].cpu(), _grad(c, 'both', torch.float32, 'cuda'))
 
 
+@pytest.mark.gpu
+def test_batch_slices_give_the_bits_of_one_launch(monkeypatch):
+    """B = 5 icospheres of one subdivision (V = 42, F = 80) in slices of 2 -- a full slice, a second full one at a non-zero offset and
+    a remainder -- against the one-launch result: the forward, and a backward in which only the volume is differentiated, so that the
+    darea upstream is null."""
+    f = torch.from_numpy(ico_ref.faces_from_lattice(1)).cuda()
+    v = torch.from_numpy(make_goldens.synthetic_np(5, 1, seed=31).astype(np.float32)).cuda()
+    assert v.shape == (5, 42, 3) and f.shape == (80, 3)
+    dvolume = torch.tensor([0.5, -1.25, 2.0, 0.75, -3.0], device='cuda')
+
+    def run():
+        x = v.clone().requires_grad_()
+        a, vol = metrics.mesh_area_volume(x, f)
+        g, = torch.autograd.grad((vol * dvolume).sum(), x)
+        return a.detach(), vol.detach(), g
+    assert metrics._MAX_GRID_Y == 65535
+    want = run()
+    assert len(set(want[0].tolist())) == len(set(want[1].tolist())) == 5 and bool((want[2].abs().sum((1, 2)) > 0).all())    # five different meshes
+    monkeypatch.setattr(metrics, '_MAX_GRID_Y', 2)
+    assert list(metrics._batch_slices(5)) == [(0, 2), (2, 2), (4, 1)]
+    for one_launch, sliced in zip(want, run()):
+        assert torch.equal(one_launch, sliced)
+
+
 def _unchecked(v, f32, term_weights, table=None):
     v = v.detach().clone().requires_grad_()
     a, vol = metrics._mesh_area_volume_unchecked(v, f32, table)

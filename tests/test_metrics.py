@@ -83,3 +83,25 @@ def test_face_indices_outside_the_vertex_list_raise_an_index_error():
         point_to_mesh_distance(pts, vts, torch.tensor([[-1, 2, 3]]))
     d, f, k = point_to_mesh_distance(pts, vts, torch.tensor([[0, 1, 2], [1, 2, 3]]))
     assert d.shape == (1, 5)
+
+
+def test_batch_slicing_marshals_addresses_counts_and_one_workspace_query(monkeypatch):
+    """metrics._slice_arguments, the marshalling of every call into the mesh entries, on CPU tensors against a recording stub: B = 5
+    in slices of 2 with one per-mesh tensor of row size 3, one table the batch shares and one optional tensor that is absent."""
+    class Stub:
+        asked = []
+
+        def query_bytes(self, B, V, F):
+            self.asked.append((B, V, F))
+            return 48 * B
+    rows, shared = torch.zeros(5, 3), torch.zeros(7, dtype=torch.int32)
+    monkeypatch.setattr(metrics, '_MAX_GRID_Y', 2)
+    calls, ws_bytes = metrics._slice_arguments(Stub(), (metrics._per_mesh(rows), shared, metrics._per_mesh(None), metrics._NB, 42, 80),
+                                               workspace=('query_bytes', 42, 80))
+    assert Stub.asked == [(2, 42, 80)] and ws_bytes == 96                    # asked once, for the largest slice: 2 meshes, not 5
+    assert rows.stride(0) == 3 and rows.element_size() == 4
+    assert calls == [(rows.data_ptr() + b0 * 3 * 4, shared.data_ptr(), None, nb, 42, 80) for b0, nb in ((0, 2), (2, 2), (4, 1))]
+    # without a workspace nothing is asked; one launch when the batch fits
+    monkeypatch.setattr(metrics, '_MAX_GRID_Y', 65535)
+    calls, ws_bytes = metrics._slice_arguments(Stub(), (metrics._per_mesh(None), metrics._per_mesh(rows), metrics._NB))
+    assert Stub.asked == [(2, 42, 80)] and ws_bytes is None and calls == [(None, rows.data_ptr(), 5)]

@@ -353,6 +353,25 @@ def test_hip_gradients_against_float64(S):
 
 
 @pytest.mark.gpu
+def test_batch_slices_give_the_bits_of_one_launch(monkeypatch):
+    """B = 5 pairs of r = 1 icospheres (42 / 80 on both sides), 16 samples, in slices of 2 -- a full slice, a second full one at a
+    non-zero offset and a remainder -- against the one-launch result: the forward, and a backward in which only side a requires a
+    gradient."""
+    (va, fa), (vb, fb) = _mesh(1, 5, batch=5), _mesh(1, 6, batch=5)
+    assert (va.shape, fa.shape, vb.shape, fb.shape) == ((5, 42, 3), (80, 3), (5, 42, 3), (80, 3))
+    gen = torch.Generator().manual_seed(7)
+    ia, ib = torch.randint(0, 80, (5, 16), generator=gen), torch.randint(0, 80, (5, 16), generator=gen)
+    c = dict(va=va, fa=fa, ia=ia, vb=vb, fb=fb, ib=ib, g=torch.rand((5, 16), generator=gen) + 0.5)
+    assert metrics._MAX_GRID_Y == 65535
+    t, ga, none_b = _hip_grads(c, (True, False))
+    assert none_b is None and bool((ga.abs().sum((1, 2)) > 0).all()) and len({tuple(row) for row in t.tolist()}) == 5
+    monkeypatch.setattr(metrics, '_MAX_GRID_Y', 2)
+    assert list(metrics._batch_slices(5)) == [(0, 2), (2, 2), (4, 1)]
+    t2, ga2, none_b = _hip_grads(c, (True, False))
+    assert none_b is None and torch.equal(t2, t) and torch.equal(ga2, ga)
+
+
+@pytest.mark.gpu
 def test_hip_known_answers_degenerate_faces_bad_ids_and_non_finite_vertices():
     _check_known_answers(torch.float32, 'cuda')
     _check_degenerate_faces(torch.float32, 'cuda')
