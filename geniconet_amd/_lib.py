@@ -135,6 +135,16 @@ EXTENSION_HEADERS = {
     },
 }
 
+# Headers added after tests/test_abi_mesh.py fixed the set of EXTENSION_HEADERS and the names in each: the same shape (header ->
+# {entry: (restype, argtypes, reply)}), the same conventions, the same library, and each mirrors its header one to one -- but each
+# header here has an ABI test file of its own (icn_sdf.h: tests/test_abi_sdf.py).  lib() binds these with the tables above in one
+# loop and source_files() hashes their headers too.
+LATER_HEADERS = {
+    'icn_sdf.h': {                     # sign of the point-to-mesh distance
+        'icn_point_to_mesh_sign': (ctypes.c_int, [_c_float_p] * 8 + [ctypes.c_int] * 4 + [_c_float_p, ctypes.c_void_p], RC),
+    },
+}
+
 
 class ProfileEntry(ctypes.Structure):
     _fields_ = [('kernel', ctypes.c_char_p), ('launches', ctypes.c_long), ('total_ms', ctypes.c_double),
@@ -169,7 +179,7 @@ def lib():
                 '(or `make -C geniconet_amd/csrc`).' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
         checked = types.SimpleNamespace()
-        for name, (res, args, reply) in [item for table in (SIGNATURES, *EXTENSION_HEADERS.values()) for item in table.items()]:
+        for name, (res, args, reply) in [item for table in (SIGNATURES, *EXTENSION_HEADERS.values(), *LATER_HEADERS.values()) for item in table.items()]:
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             fn = handle[name]            # a function object of its own (handle.name is cached, handle[name] is not)
@@ -233,9 +243,9 @@ def set_arith(mode):
 
 def source_files():
     """The files source_sha256() hashes, sorted: the kernel / library sources under csrc/, include/icn.h and every header of
-    EXTENSION_HEADERS."""
+    EXTENSION_HEADERS and LATER_HEADERS."""
     import glob
-    headers = [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('icn.h', *EXTENSION_HEADERS)]
+    headers = [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('icn.h', *EXTENSION_HEADERS, *LATER_HEADERS)]
     return sorted([f for pattern in ('*.hip', '*.h', '*.cpp') for f in glob.glob(os.path.join(_HERE, 'csrc', pattern))] + headers)
 
 

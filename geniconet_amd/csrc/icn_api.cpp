@@ -17,6 +17,7 @@
 #include "../../include/icn_curvature.h"
 #include "../../include/icn_gauss.h"
 #include "../../include/icn_isect.h"
+#include "../../include/icn_sdf.h"
 #include "../../include/icn_measure.h"
 #include "icn_geometry.h"
 #include "icn_launch.h"
@@ -793,7 +794,7 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_fnormal_agree_bwd_vertex",    // every ..._bwd_vertex: k_vertex_scatter, by its caller
                                             "k_mesh_measure_face", "k_mesh_measure_finish", "k_mesh_measure_bwd",
                                             "k_mesh_cotlap_fwd", "k_mesh_willmore_finish", "k_mesh_willmore_upstream", "k_mesh_cotlap_bwd",
-                                            "k_mesh_angle_defect_fwd", "k_mesh_angle_defect_bwd", "k_mesh_self_intersect"};
+                                            "k_mesh_angle_defect_fwd", "k_mesh_angle_defect_bwd", "k_mesh_self_intersect", "k_p2m_sign"};
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1560,6 +1561,20 @@ int icn_mesh_self_intersect(const float* vertices, const int32_t* faces, int B, 
         check_measure_sizes("icn_mesh_self_intersect", B, V, F);
         if (F > ICN_SELF_INTERSECT_MAX_FACES) throw std::invalid_argument("icn_mesh_self_intersect: bad sizes");
         icn::launch_mesh_self_intersect(vertices, faces, B, V, F, hits, s);
+    });
+}
+
+// ---- sign of the point-to-mesh distance (include/icn_sdf.h): the sizes of the point-to-mesh entries, and 3 F corners an int ---------
+int icn_point_to_mesh_sign(const float* points, const float* vertices, const int32_t* faces, const int32_t* adjacency,
+                           const int32_t* vf_offsets, const int32_t* vf_corners, const int32_t* face, const int32_t* kind, int B, int P,
+                           int V, int F, float* sign, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!points || !vertices || !faces || !adjacency || !vf_offsets || !vf_corners || !face || !kind || !sign)
+            throw std::invalid_argument("icn_point_to_mesh_sign: null pointer");
+        check_mesh_sizes("icn_point_to_mesh_sign", B, P, V, F);
+        check_measure_sizes("icn_point_to_mesh_sign", B, V, F);
+        icn::launch_point_to_mesh_sign(points, vertices, faces, adjacency, vf_offsets, vf_corners, face, kind, B, P, V, F, sign, s);
     });
 }
 

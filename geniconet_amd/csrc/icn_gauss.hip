@@ -27,40 +27,6 @@
 namespace icn {
 namespace {
 
-struct d3 { double x, y, z; };
-__device__ __forceinline__ d3 operator-(d3 a, d3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ d3 cross(d3 a, d3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ double dot(d3 a, d3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ d3 widened(const float* __restrict__ p) { return {(double)p[0], (double)p[1], (double)p[2]}; }
-
-// face_normal of icn_mesh_device.h in double: no contraction, so that a x a is exactly 0
-__device__ __forceinline__ d3 dnormal(d3 a, d3 b) {
-#pragma clang fp contract(off)
-    return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-
-// the vertex ids of corners k + 1 and k + 2 of an incident face (selects, not a runtime index into registers)
-__device__ __forceinline__ int next_id(const Incident& t) { return t.k == 0 ? t.id[1] : (t.k == 1 ? t.id[2] : t.id[0]); }
-__device__ __forceinline__ int after_id(const Incident& t) { return t.k == 0 ? t.id[2] : (t.k == 1 ? t.id[0] : t.id[1]); }
-
-// The face of `t` as thread j sees it: pj = vertex j = corner k, q1 / q2 the vertices of corners k + 1 / k + 2, and the normal of
-// corner 0 whichever corner j sits at, so that the three threads of a face agree on whether it is resolved.
-struct Corner {
-    d3 a, b, n;        // q1 - pj, q2 - pj, (v1 - v0) x (v2 - v0)
-    double nn;
-};
-
-__device__ __forceinline__ Corner corner(const float* __restrict__ v, const Incident& t, d3 pj) {
-    const int i1 = next_id(t), i2 = after_id(t);
-    const d3 q1 = widened(v + (size_t)i1 * 3), q2 = widened(v + (size_t)i2 * 3);
-    Corner c;
-    c.a = q1 - pj, c.b = q2 - pj;
-    // corner 0 of the face: (pj, q1, q2) for k = 0, (q2, pj, q1) for k = 1, (q1, q2, pj) for k = 2
-    c.n = t.k == 0 ? dnormal(c.a, c.b) : (t.k == 1 ? dnormal(pj - q2, q1 - q2) : dnormal(q2 - q1, pj - q1));
-    c.nn = c.n.x * c.n.x + c.n.y * c.n.y + c.n.z * c.n.z;
-    return c;
-}
-
 __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_angle_defect_fwd(const float* __restrict__ vts, const int32_t* __restrict__ faces,
                                                                        const int32_t* __restrict__ offsets,
                                                                        const int32_t* __restrict__ corners, int V, int F,

@@ -32,7 +32,6 @@ namespace {
 constexpr int ISECT_WORDS = 19;              // 9 coordinates, 3 ids, box lo / hi, valid: odd, so the fills are conflict-free
 constexpr int ISECT_ID = 9, ISECT_LO = 12, ISECT_HI = 15, ISECT_VALID = 18;
 
-struct d3 { double x, y, z; };
 __device__ __forceinline__ d3 widened(f3 p) { return {(double)p.x, (double)p.y, (double)p.z}; }
 __device__ __forceinline__ d3 pick(bool first, d3 a, d3 b) { return {first ? a.x : b.x, first ? a.y : b.y, first ? a.z : b.z}; }
 

@@ -290,6 +290,13 @@ void launch_mesh_angle_defect_bwd(const float* vts, const int32_t* faces, const 
 // through LDS tiles, fp32 box rejection, the exact tests in double.  One launch on s, no workspace; F <= 2^20 (checked by the entry).
 void launch_mesh_self_intersect(const float* vts, const int32_t* faces, int B, int V, int F, int32_t* hits, hipStream_t s);
 
+// sign of the point-to-mesh distance by the angle-weighted pseudonormal of the closest feature (icn_sdf.hip; include/icn_sdf.h): one
+// thread per (mesh, point) from the forward's (face, kind), the face adjacency (F, 3) and the incidence table, double arithmetic.  One
+// launch on s, no workspace; 3 F fits an int (checked by the entry).
+void launch_point_to_mesh_sign(const float* pts, const float* vts, const int32_t* faces, const int32_t* adjacency, const int32_t* offsets,
+                               const int32_t* corners, const int32_t* face, const int32_t* kind, int B, int P, int V, int F, float* sign,
+                               hipStream_t s);
+
 // developer routing flags (ICN_DEBUG / icn_set_debug_flags): 16 = convs on k_gather_gemm, 32 = wgrads on k_wgrad,
 // 128 = no stream-K, 256 = fault injection: every stream-K finisher reports its partners lost (tests of the failure path),
 // 512 = masked launches walk tiles b, b + G, ... instead of the balanced tile lists, 1024 = the sparse passes of the decoder-block
@@ -300,7 +307,7 @@ int debug_flags();
 int set_debug_flags(int flags);
 
 // ---- optional per-launch HIP-event timing of the MFMA kernels (bench.py's live roofline measurement) and of the
-// point-to-mesh, surface-sampling, normal-agreement, mesh-measure, mesh-curvature, angle-defect and self-intersection kernels ----------
+// point-to-mesh, surface-sampling, normal-agreement, mesh-measure, mesh-curvature, angle-defect, self-intersection and distance-sign kernels ----------
 enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA_64x64, PROF_GG_128x128, PROF_GG_128x64,
                 PROF_GG_64x128, PROF_GG_64x64, PROF_WGD_128x128, PROF_WGD_128x64, PROF_WGD_64x128, PROF_WGD_64x64, PROF_WG_128x128,
                 PROF_WG_128x64, PROF_WG_64x128, PROF_WG_64x64,
@@ -321,6 +328,7 @@ enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA
                 PROF_MESH_COTLAP_FWD, PROF_MESH_WILLMORE_FINISH, PROF_MESH_WILLMORE_UPSTREAM, PROF_MESH_COTLAP_BWD,   // cotangent Laplacian, Willmore energy
                 PROF_MESH_ANGLE_DEFECT_FWD, PROF_MESH_ANGLE_DEFECT_BWD,                             // angle defect (Gaussian curvature)
                 PROF_MESH_SELF_INTERSECT,                                                           // self-intersection count
+                PROF_P2M_SIGN,                                                                      // sign of the point-to-mesh distance
                 PROF_KINDS };
 extern const char* const PROF_NAMES[PROF_KINDS];
 void prof_mark_begin(int kind, double flops, hipStream_t s);   // no-ops unless profiling is on

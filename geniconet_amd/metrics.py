@@ -55,6 +55,14 @@ tests in double): the one figure here that is NOT unremarkable on a mesh that fo
 volume and curvature all stay finite there.  Integers, no gradient; the HIP path reproduces the float64 formulation exactly.
 self_intersection_ratio is the share of self-intersecting faces of one mesh, the figure the mesh-generation literature reports, to
 stand beside curvature_error, volume_error and compute_distance.
+
+signed_point_to_mesh_distance, contains and volumetric_iou (below) add the side to the distance: phi = sign sqrt(dist2), negative
+inside a closed mesh, the sign that of (p - q) . N with q the closest point the search found and N the angle-weighted pseudonormal
+of the feature q lies on -- the face normal, the sum of the two unit normals at an edge, the angle-weighted sum around a vertex
+(icn_point_to_mesh_sign, include/icn_sdf.h: one gather per point over signed_distance_tables, the face adjacency and
+vertex_face_table, in double; no second search, and the gradient is that of dist2 under a rescaled upstream).  contains is kaolin's
+check_sign; volumetric_iou is the intersection over union of the solids of one mesh pair on a lattice, to stand beside volume_error
+and compute_distance.  Its lattice points lie mostly far from the surface, where 'grid' falls back to the linear scan (above).
 """
 import torch
 
@@ -999,6 +1007,281 @@ def self_intersection_ratio(vertices, faces):
         raise ValueError('self_intersection_ratio: expected (V, 3) vertices, got %s' % (tuple(vertices.shape),))
     hits = self_intersections(vertices[None], faces)[1]
     return float((hits > 0).sum()) / hits.shape[1]
+
+
+# ---- signed distance, inside test and volumetric IoU ----------------------------------------------------------------------------------
+def _edge_twins(f32, V):
+    """(adjacency int32 (F, 3), report int64 (8,)) of a face list, without a host synchronisation.  Corner c = 3 f + e stands for the
+    directed edge e of face f, (faces[f][e], faces[f][(e + 1) % 3]); its key is a V + b, and adjacency[f][e] is the face of the lowest
+    corner whose key is the twin's, b V + a, or -1: the keys of all 3 F directed edges are sorted (stably, in int64) and the twin keys
+    searched in them.  An edge with a vertex id outside [0, V) has no key and no twin.  report = (lowest id, highest id, the number of
+    edges without a twin and the (a, b) of the first, the number of directed edges that occur again and the (a, b) of the first): what
+    the checked functions read back in one piece."""
+    f = f32.long()
+    a, b = f.reshape(-1), torch.roll(f, -1, 1).reshape(-1)                                # (no index list: that would be a copy to the device)
+    valid = (a >= 0) & (a < V) & (b >= 0) & (b < V)
+    key = torch.where(valid, a * V + b, torch.full_like(a, V * V))
+    twin = torch.where(valid, b * V + a, torch.full_like(a, -1))
+    ordered, corner = torch.sort(key, stable=True)
+    at = torch.searchsorted(ordered, twin).clamp(max=key.numel() - 1)
+    found = ordered[at] == twin
+    adjacency = torch.where(found, corner[at] // 3, torch.full_like(at, -1))
+    again = torch.zeros_like(valid)
+    again[1:] = (ordered[1:] == ordered[:-1]) & (ordered[1:] < V * V)
+    first_open = (~found).to(torch.int8).argmax().reshape(1)
+    first_again = corner.index_select(0, again.to(torch.int8).argmax().reshape(1))
+    lo, hi = f.aminmax()
+    report = torch.cat([lo.reshape(1), hi.reshape(1), (~found).sum().reshape(1), a.index_select(0, first_open), b.index_select(0, first_open),
+                        again.sum().reshape(1), a.index_select(0, first_again), b.index_select(0, first_again)])
+    return adjacency.reshape(-1, 3).to(torch.int32), report
+
+
+def signed_distance_tables(faces, num_vertices):
+    """(adjacency int32 (F, 3), offsets int32 (V + 1), corners int32 (3 F)) on the faces' device: what the sign of
+    signed_point_to_mesh_distance reads besides the face list, built once per face list without a host synchronisation.
+    adjacency[f][e] is the face that holds the directed edge opposite to edge e of f -- the face across edge (e, e + 1) of a
+    consistently wound mesh -- or -1 (see _edge_twins); (offsets, corners) is vertex_face_table(faces, num_vertices)."""
+    V = int(num_vertices)
+    offsets, corners = vertex_face_table(faces, V)                                        # checks faces and V
+    return (_edge_twins(faces, V)[0], offsets, corners)
+
+
+def _torch_point_to_mesh_sign(points, vertices, faces, face, kind, tables):
+    """The definition of the sign of signed_point_to_mesh_distance in torch: float64 whatever the inputs' dtype, sign (B, P) in
+    float64, -1 or +1.  Vectorised: every point evaluates the plane, the three segments and the vertex sum and selects by kind;
+    the vertex sum walks the incidence slices slot by slot in slice order, padded to the longest slice (one read-back of that
+    length: the HIP path has none)."""
+    from .losses import Mesh_Regularizer
+    adjacency, offsets, corners = tables
+    B, P, _ = points.shape
+    V, F = vertices.shape[1], faces.shape[0]
+    nc = 3 * F
+    p, v, ids_all = points.detach().double(), vertices.detach().double(), faces.long()
+    flat_ids = ids_all.reshape(-1)
+    face, kind = face.long(), kind.long()
+    rows = torch.arange(B, device=p.device)[:, None]
+
+    def resolved_normals(fid, ok):
+        """(the three vertices, n, |n|^2, usable) of faces fid (B, P) where ok: ids clamped before they index anything."""
+        ids = ids_all[fid.clamp(0, F - 1)]                                                # (B, P, 3)
+        ok = ok & (fid >= 0) & (fid < F) & ((ids >= 0) & (ids < V)).all(-1)
+        tri = v[rows[..., None], ids.clamp(0, V - 1)]                                     # (B, P, 3 corners, 3)
+        n = Mesh_Regularizer._face_normal(tri[:, :, 1] - tri[:, :, 0], tri[:, :, 2] - tri[:, :, 0])
+        return ids, tri, n, (n * n).sum(-1), ok
+
+    def unit(n, nn, use, w=None):
+        """w n / |n| where use and the normal is resolved (NaN counts), else 0."""
+        use = use & (nn != 0)
+        u = n / torch.where(use, nn, torch.ones_like(nn)).sqrt()[..., None]
+        if w is not None:
+            u = w[..., None] * u
+        return torch.where(use[..., None], u, torch.zeros_like(u))
+
+    def segment(up, uw):
+        den = (uw * uw).sum(-1)
+        t = torch.where(den != 0, (uw * up).sum(-1) / torch.where(den != 0, den, torch.ones_like(den)), torch.zeros_like(den))
+        t = torch.where(t > 0, torch.where(t < 1, t, torch.ones_like(t)), torch.zeros_like(t))
+        return up - uw * t[..., None]
+    ids, tri, n, nn, ok = resolved_normals(face, (kind >= 0) & (kind <= 6))
+    a, b, c = tri[:, :, 0], tri[:, :, 1], tri[:, :, 2]
+    ab, ac, ap = b - a, c - a, p - a
+    # kind 0: the plane
+    s = torch.where(nn != 0, (ap * n).sum(-1) / torch.where(nn != 0, nn, torch.ones_like(nn)), torch.zeros_like(nn))
+    d, N = n * s[..., None], n
+    # kind 4 / 5 / 6: the edge's segment, this face and the one across
+    edge = (kind - 4).clamp(0, 2)
+    g = torch.gather(adjacency.long()[face.clamp(0, F - 1)], 2, edge[..., None])[..., 0]
+    _, _, m, mm, g_ok = resolved_normals(g, kind >= 4)
+    N_edge = unit(n, nn, ok) + unit(m, mm, g_ok)
+    for k, dk in ((4, segment(ap, ab)), (5, segment(p - b, c - b)), (6, segment(ap, ac))):
+        d = torch.where((kind == k)[..., None], dk, d)
+    N = torch.where((kind >= 4)[..., None], N_edge, N)
+    # kind 1 / 2 / 3: the vertex, every resolved face of its slice by its angle
+    at_vertex = ok & (kind >= 1) & (kind <= 3)
+    local = (kind - 1).clamp(0, 2)
+    j = torch.gather(ids, 2, local[..., None])[..., 0].clamp(0, V - 1)                    # (B, P)
+    pj = torch.gather(tri, 2, local[..., None, None].expand(-1, -1, 1, 3))[:, :, 0]
+    lo, hi = offsets.long()[j].clamp(0, nc), offsets.long()[j + 1].clamp(0, nc)
+    longest = int(torch.where(at_vertex, hi - lo, torch.zeros_like(lo)).max()) if at_vertex.numel() else 0
+    N_vertex = torch.zeros_like(d)
+    for slot in range(longest):
+        entry = lo + slot
+        cid = corners.long()[entry.clamp(0, nc - 1)]
+        use = at_vertex & (entry < hi) & (cid >= 0) & (cid < nc)
+        use = use & (flat_ids[cid.clamp(0, nc - 1)] == j)
+        fid, k = cid.clamp(0, nc - 1) // 3, cid.clamp(0, nc - 1) % 3
+        fids, ftri, fn, fnn, use = resolved_normals(fid, use)
+        q1 = torch.gather(ftri, 2, ((k + 1) % 3)[..., None, None].expand(-1, -1, 1, 3))[:, :, 0]
+        q2 = torch.gather(ftri, 2, ((k + 2) % 3)[..., None, None].expand(-1, -1, 1, 3))[:, :, 0]
+        ea, eb = q1 - pj, q2 - pj
+        live = use & (fnn != 0)
+        theta = torch.atan2(torch.where(live, fnn, torch.ones_like(fnn)).sqrt(), (ea * eb).sum(-1))
+        N_vertex = N_vertex + unit(fn, fnn, use, theta)
+    d = torch.where(at_vertex[..., None], p - pj, d)
+    N = torch.where(at_vertex[..., None], N_vertex, N)
+    inside = ok & ((d * N).sum(-1) < 0)
+    return torch.where(inside, -torch.ones_like(nn), torch.ones_like(nn))
+
+
+def _hip_point_to_mesh_sign(pts, vts, f32, tables, face, kind):
+    """icn_point_to_mesh_sign on contiguous fp32 ROCm points and vertices, int32 faces, tables and (face, kind) -> sign (B, P) fp32."""
+    B, P, _ = pts.shape
+    V, F = vts.shape[1], f32.shape[0]
+    adjacency, offsets, corners = tables
+    sign = torch.empty(B, P, dtype=torch.float32, device=pts.device)
+    _launch('icn_point_to_mesh_sign', _per_mesh(pts), _per_mesh(vts), f32, adjacency, offsets, corners, _per_mesh(face), _per_mesh(kind),
+            _NB, P, V, F, _per_mesh(sign))
+    return sign
+
+
+class _SignedRootFn(torch.autograd.Function):
+    """phi = sign sqrt(dist2), differentiable in dist2 alone: the upstream g becomes g sign / (2 sqrt(dist2)), and 0 where dist2 == 0
+    (the subgradient on the surface, where the root has no derivative)."""
+
+    @staticmethod
+    def forward(ctx, dist2, sign):
+        root = dist2.sqrt()
+        ctx.save_for_backward(root, sign)
+        return sign * root
+
+    @staticmethod
+    def backward(ctx, g):
+        root, sign = ctx.saved_tensors
+        return torch.where(root == 0, torch.zeros_like(g), g * sign / (2 * root)), None
+
+
+def _signed_point_to_mesh_distance_unchecked(pointclouds, vertices, f32, tables, search='brute'):
+    """signed_point_to_mesh_distance without its argument checks, for callers that validated once: f32 is an int32 (F, 3) tensor on
+    the points' device, F >= 1, tables = signed_distance_tables(f32, V) there.  On the HIP path (ROCm fp32 points and vertices, unless
+    ICN_NO_HIP_LOSS=1) no host synchronisation; ids out of range in f32, the tables or (face, kind) are safe on either path (+1 or
+    skipped, as defined)."""
+    dist2, face, kind = _point_to_mesh_unchecked(pointclouds, vertices, f32, search)
+    with torch.no_grad():
+        if _on_hip_path(vertices) and pointclouds.is_cuda and pointclouds.dtype == torch.float32:
+            sign = _hip_point_to_mesh_sign(pointclouds.detach().contiguous(), vertices.detach().contiguous(), f32, tables,
+                                           face.to(torch.int32), kind)
+        else:
+            sign = _torch_point_to_mesh_sign(pointclouds, vertices, f32, face, kind, tables).to(dist2.dtype)
+    return _SignedRootFn.apply(dist2, sign), face, kind
+
+
+def _check_signed_distance_arguments(who, pointclouds, vertices, faces, search, tables):
+    """The argument checks of point_to_mesh_distance for `who`, F >= 1, and -- with the one read-back of the face ids -- that the
+    mesh is closed and manifold -> (int32 faces on the points' device, the tables there)."""
+    _check_search(search)
+    if pointclouds.dim() != 3 or vertices.dim() != 3 or pointclouds.shape[-1] != 3 or vertices.shape[-1] != 3:
+        raise ValueError('%s: expected (B, P, 3) points and (B, V, 3) vertices' % who)
+    if pointclouds.shape[0] != vertices.shape[0] or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError('%s: batch sizes differ or faces is not (F, 3)' % who)
+    if (pointclouds.shape[0] < 1 or pointclouds.shape[1] < 1 or vertices.shape[1] < 1 or faces.shape[0] < 1 or faces.is_floating_point()
+            or faces.dtype == torch.bool or pointclouds.dtype != vertices.dtype or pointclouds.device != vertices.device):
+        raise ValueError('%s: expected at least one mesh, point, vertex and face, integer faces, and points and vertices of one dtype '
+                         'and device' % who)
+    V, F = vertices.shape[1], faces.shape[0]
+    if 3 * F > 0x7fffffff:
+        raise ValueError('%s: %d faces: 3 F must fit an int32' % (who, F))
+    dev = pointclouds.device
+    f32 = faces.to(device=dev, dtype=torch.int32).contiguous()
+    if tables is not None:
+        if (not isinstance(tables, (tuple, list)) or len(tables) != 3 or any(not torch.is_tensor(x) or x.dtype != torch.int32 for x in tables)
+                or tuple(tables[0].shape) != (F, 3) or tuple(tables[1].shape) != (V + 1,) or tuple(tables[2].shape) != (3 * F,)):
+            raise ValueError('%s: tables must be signed_distance_tables(faces, %d): int32 tensors (%d, 3), (%d,) and (%d,)'
+                             % (who, V, F, V + 1, 3 * F))
+        tables = tuple(x.to(dev).contiguous() for x in tables)
+    adjacency, report = _edge_twins(f32, V)
+    lo, hi, n_open, a_open, b_open, n_again, a_again, b_again = report.tolist()           # the one read-back
+    if lo < 0 or hi >= V:
+        raise IndexError('%s: face indices span [%d, %d] but there are %d vertices' % (who, lo, hi, V))
+    if n_again:
+        raise ValueError('%s: the mesh is not manifold: the directed edge (%d, %d) belongs to more than one face (%d such edges); '
+                         'the sign needs a closed, consistently wound manifold' % (who, a_again, b_again, n_again))
+    if n_open:
+        raise ValueError('%s: the mesh is not closed: no face holds the edge (%d, %d), opposite to (%d, %d) (%d such edges); the sign '
+                         'needs a closed, consistently wound manifold' % (who, b_open, a_open, a_open, b_open, n_open))
+    if tables is None:
+        tables = (adjacency,) + vertex_face_table(f32, V)
+    return f32, tables
+
+
+def signed_point_to_mesh_distance(pointclouds, vertices, faces, search='brute', tables=None):
+    """(phi (B, P), face (B, P), kind (B, P)): the SIGNED distance of every point to the closed triangle mesh vertices (B, V, 3), faces
+    (F, 3) integer and shared by the batch -- negative inside, positive outside, |phi| = sqrt(dist2) of point_to_mesh_distance exactly,
+    with its (face, kind).  The sign is that of (p - q) . N, q the closest point the forward found and N the ANGLE-WEIGHTED
+    PSEUDONORMAL of the feature q lies on (Baerentzen & Aanaes 2005): for a closed mesh wound counter-clockwise seen from outside --
+    every mesh of this package -- it is exact for every point, whichever feature is the closest, at O(valence) per point on top of
+    the search (MI355X, I5 / batch 36, one point per vertex: k_p2m_sign 0.017 - 0.027 ms beside 0.023 ms for the angle-defect gather;
+    with search='grid' the whole signed distance of points 0.01 from the surface takes 0.55 ms, profiles/signed_distance.txt).
+
+    One definition for the HIP kernel (include/icn_sdf.h), the torch formulation and the tests.  All arithmetic from the inputs to the
+    one comparison is float64, whatever the dtype.  A face has n = (v1 - v0) x (v2 - v0) with every product of the cross product rounded
+    on its own, is RESOLVED iff |n|^2 != 0, and n^ = n / |n|.  For a point p with its face f and kind:
+        d = p - q, q recomputed from (f, kind) as the backward of point_to_mesh_distance does: the vertex; the clamped projection on
+            the edge's segment; the plane, d = n (ap . n / |n|^2)
+        N = n                    kind 0
+            n^_f + n^_g          kind 4 / 5 / 6, g = adjacency[f][kind - 4] the face across that edge (an unresolved face adds nothing;
+                                 without a g the edge takes n^_f alone)
+            sum theta n^         kind 1 / 2 / 3, over the resolved faces at vertex j = faces[f][kind - 1] in the order of j's slice of
+                                 vertex_face_table, theta = atan2(|n|, a . b) the face's angle at j (the corner of angle_defect)
+        sign = -1 iff d . N < 0, else +1;   phi = sign sqrt(dist2)
+    A point on the surface, a feature all of whose faces are unresolved and a NaN point give sign +1 (phi = NaN for the last).  Without
+    the angles -- the plain sum of the incident normals -- the sign is wrong near a vertex whose faces differ much in their angles
+    (tests/test_signed_distance.py: the spike).  Topology goes by vertex id: two vertices at one position are two vertices.
+    The sign means "inside" only for a CLOSED, consistently wound manifold whose closest feature was found correctly, so this function
+    checks, with the read-back that checks the face ids, that every directed edge has its opposite and none occurs twice, and raises
+    ValueError naming the first offending edge otherwise.  On a mesh that passes through itself (self_intersections) the sign is still
+    the one defined above, the side of the nearest sheet: a point in a fold-over counts as outside where the nearest sheet shows it
+    its front -- use it there as a local, not a global, statement.
+    tables = signed_distance_tables(faces, V): pass them when the face list is reused, else they are built here.  ROCm fp32 tensors run
+    the search on icn_point_to_mesh / icn_point_to_mesh_grid (`search`, as point_to_mesh_distance) and the sign on icn_point_to_mesh_sign,
+    one thread per point; CPU tensors, other dtypes and ICN_NO_HIP_LOSS=1 take the sign from the torch formulation.
+    Differentiable in the points and the vertices by composition: the sign is piecewise constant and carries no gradient, so the
+    gradient of phi is that of dist2 (icn_point_to_mesh_bwd on the HIP path) under the upstream g sign / (2 sqrt(dist2)), taken as 0
+    where dist2 == 0.  face and kind never carry one."""
+    f32, tables = _check_signed_distance_arguments('signed_point_to_mesh_distance', pointclouds, vertices, faces, search, tables)
+    return _signed_point_to_mesh_distance_unchecked(pointclouds, vertices, f32, tables, search)
+
+
+def contains(points, vertices, faces, search='brute', tables=None):
+    """bool (B, P): whether each point lies strictly inside its closed mesh, phi < 0 of signed_point_to_mesh_distance (arguments,
+    checks and paths as there; a NaN point is not inside).  Never requires grad."""
+    f32, tables = _check_signed_distance_arguments('contains', points, vertices, faces, search, tables)
+    with torch.no_grad():
+        return _signed_point_to_mesh_distance_unchecked(points, vertices, f32, tables, search)[0] < 0
+
+
+def volumetric_iou(outvertices, refvertices, faces, resolution=32, search='brute'):
+    """|A and B| / |A or B| of the solids two closed meshes enclose ((V, 3) tensors sharing `faces`), counted on a lattice, as a Python
+    float: the standard volumetric figure of a reconstruction, to stand beside volume_error, curvature_error, self_intersection_ratio
+    and compute_distance.  0 when no lattice point lies in either.
+    The lattice: [lo, hi] the joint bounding box of both meshes (one read-back), h = largest extent / resolution,
+    n_k = max(1, ceil(extent_k / h)) evaluated in float64 on the host, cell centres lo_k + (i + 1/2) h.  Both meshes go through
+    `contains` as one batch of two; the counts are taken on the device.  A cell is misclassified only if its centre is within
+    h sqrt(3) / 2 of the surface, so each volume is off by at most sqrt(3) area h.
+    What it costs: n_0 n_1 n_2 points per mesh, up to resolution^3, each through the closest-triangle search -- and the lattice points
+    deep inside or far outside are exactly the regime where search='grid' gives up its walk and scans all triangles (module docstring),
+    so 'brute' is the default: on an MI355X one I5 pair (20 480 faces) takes 11 ms at resolution 32 and 21 ms at 64 with 'brute', 20 and 23 ms with
+    'grid' (profiles/signed_distance.txt from tools/time_signed_distance.py).  A
+    voxeliser that counts ray parities per lattice column would be the next step; it is not part of this module."""
+    who = 'volumetric_iou'
+    if outvertices.dim() != 2 or refvertices.dim() != 2 or outvertices.shape != refvertices.shape or outvertices.shape[-1] != 3:
+        raise ValueError('%s: expected two (V, 3) vertex tensors of one shape, got %s and %s'
+                         % (who, tuple(outvertices.shape), tuple(refvertices.shape)))
+    if int(resolution) < 1:
+        raise ValueError('%s: resolution must be positive, got %r' % (who, resolution))
+    both = torch.stack([outvertices, refvertices.to(device=outvertices.device, dtype=outvertices.dtype)]).detach()
+    lo, hi = (x.double() for x in (both.amin((0, 1)), both.amax((0, 1))))
+    box = torch.stack([lo, hi]).tolist()                                                  # one read-back
+    extent = [box[1][k] - box[0][k] for k in range(3)]
+    if not all(e == e and abs(e) != float('inf') for e in extent) or max(extent) <= 0:
+        raise ValueError('%s: the meshes have no finite bounding box of positive extent' % who)
+    import math
+    h = max(extent) / int(resolution)
+    counts = [max(1, math.ceil(e / h)) for e in extent]
+    axes = [box[0][k] + (torch.arange(counts[k], dtype=torch.float64, device=both.device) + 0.5) * h for k in range(3)]
+    centres = torch.stack(torch.meshgrid(*axes, indexing='ij'), -1).reshape(1, -1, 3).to(both.dtype)
+    inside = contains(centres.expand(2, -1, -1).contiguous(), both, faces, search=search)
+    n_and, n_or = torch.stack([(inside[0] & inside[1]).sum(), (inside[0] | inside[1]).sum()]).tolist()
+    return n_and / n_or if n_or else 0.0
 
 
 def output2vertices(subdivisions, output):
