@@ -1754,7 +1754,9 @@ int icn_bn_relu_bwd(const float* dy, const float* a, const float* b, const float
 }
 
 // ---- fused 1x1 head + tanh ------------------------------------------------------------------------------------
-size_t icn_head_workspace_floats(int M, int Cin) { return (M < 1 || Cin < 1) ? 0 : (size_t)icn::head_chunks(M) * 4 * (Cin + 4); }
+size_t icn_head_workspace_floats(int M, int Cin) {
+    return (M < 1 || Cin < 1) ? 0 : (size_t)icn::head_chunks(M) * 4 * (Cin + 4) * (icn::head_sums_in_double(M) ? 2 : 1);
+}
 
 int icn_head_fwd(const float* x, const float* w, const float* bias, float* y, int M, int Cin, int Cout, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -441,35 +441,49 @@ __global__ __launch_bounds__(256) void k_head_fwd(const float* __restrict__ x, c
 }
 
 // g = dy * (1 - y^2);  dx = g @ W;  partial[chunk][o][Cin] = sum_rows g[o] * x,  partial_b[chunk][o] = sum_rows g[o]
-template <int LPR>
+// ACC = the type of g and of the parameter-gradient sums up to the chunk partials (k_head_reduce adds the chunks in double either
+// way).  In fp32 every term carries the roundings of y^2, 1 - y^2, dy * (.) and g * x.  Over the rows of a training step they average
+// out (dw within 0.6 u of sum |term|, bar 2), over a few rows they do not: 2.2 - 3.1 u at M <= 17, 1.8 - 2.0 u at M = 63 / 65, 0.3 u at
+// M = 1000 (tests/test_gpu_streaming_edges.py).  So below HEAD_F64_ROWS rows ACC is double, like the BatchNorm sums above, and dw / db
+// are rounded once; from there on ACC is float and the pass is the one it always was, bit for bit.
+constexpr int HEAD_F64_ROWS = 1024;
+template <typename ACC> struct HeadAcc;
+template <> struct HeadAcc<float> { using v4 = f32x4; static __device__ __forceinline__ v4 of(f32x4 v) { return v; } };
+template <> struct HeadAcc<double> { using v4 = f64x4; static __device__ __forceinline__ v4 of(f32x4 v) { return to_d(v); } };
+
+template <int LPR, typename ACC>
 __global__ __launch_bounds__(256) void k_head_bwd(const float* __restrict__ dy, const float* __restrict__ y,
                                                    const float* __restrict__ x, const float* __restrict__ w,
-                                                   float* __restrict__ dx, float* __restrict__ partial, int M, int Cout,
+                                                   float* __restrict__ dx, ACC* __restrict__ partial, int M, int Cout,
                                                    int rows_per_block) {
+    using acc4 = typename HeadAcc<ACC>::v4;
     constexpr int Cin = LPR * 4, RPB = 256 / LPR;
-    __shared__ f32x4 red[HEAD_MAX_OUT][256];
-    __shared__ float redb[HEAD_MAX_OUT][256];
+    __shared__ acc4 red[HEAD_MAX_OUT][256];
+    __shared__ ACC redb[HEAD_MAX_OUT][256];
     const int sub = threadIdx.x % LPR, rloc = threadIdx.x / LPR;
-    f32x4 wv[HEAD_MAX_OUT], dwv[HEAD_MAX_OUT];
-    float dbv[HEAD_MAX_OUT];
+    f32x4 wv[HEAD_MAX_OUT];
+    acc4 dwv[HEAD_MAX_OUT];
+    ACC dbv[HEAD_MAX_OUT];
 #pragma unroll
     for (int o = 0; o < HEAD_MAX_OUT; ++o) {
         wv[o] = o < Cout ? ldv(w + o * Cin + 4 * sub) : f32x4{0.f, 0.f, 0.f, 0.f};
-        dwv[o] = f32x4{0.f, 0.f, 0.f, 0.f};
-        dbv[o] = 0.f;
+        dwv[o] = acc4{0, 0, 0, 0};
+        dbv[o] = 0;
     }
     const int r0 = blockIdx.x * rows_per_block, r1 = min(M, r0 + rows_per_block);
     for (int r = r0 + rloc; r < r1; r += RPB) {
         const f32x4 xv = ldv(x + (size_t)r * Cin + 4 * sub);
+        const acc4 xa = HeadAcc<ACC>::of(xv);
         f32x4 dxa = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int o = 0; o < HEAD_MAX_OUT; ++o) {
             if (o < Cout) {
-                const float yy = y[(size_t)r * Cout + o];
-                const float g = dy[(size_t)r * Cout + o] * (1.f - yy * yy);
+                const ACC yy = y[(size_t)r * Cout + o];
+                const ACC ga = (ACC)dy[(size_t)r * Cout + o] * ((ACC)1 - yy * yy);
+                const float g = (float)ga;
                 dxa += g * wv[o];
-                dwv[o] += g * xv;
-                dbv[o] += g;
+                dwv[o] += ga * xa;
+                dbv[o] += ga;
             }
         }
         if (dx) stv(dx + (size_t)r * Cin + 4 * sub, dxa);
@@ -479,11 +493,11 @@ __global__ __launch_bounds__(256) void k_head_bwd(const float* __restrict__ dy, 
     __syncthreads();
     if (rloc == 0) {
         for (int o = 0; o < Cout; ++o) {
-            f32x4 t = red[o][sub];
+            acc4 t = red[o][sub];
             for (int q = 1; q < RPB; ++q) t += red[o][q * LPR + sub];
-            stv(partial + ((size_t)blockIdx.x * HEAD_MAX_OUT + o) * (Cin + 4) + 4 * sub, t);
+            *reinterpret_cast<acc4*>(partial + ((size_t)blockIdx.x * HEAD_MAX_OUT + o) * (Cin + 4) + 4 * sub) = t;
             if (sub == 0) {
-                float tb = 0.f;
+                ACC tb = 0;
                 for (int q = 0; q < RPB; ++q) tb += redb[o][q * LPR];
                 partial[((size_t)blockIdx.x * HEAD_MAX_OUT + o) * (Cin + 4) + Cin] = tb;
             }
@@ -493,7 +507,8 @@ __global__ __launch_bounds__(256) void k_head_bwd(const float* __restrict__ dy, 
 
 // dw[o][c] = sum_chunks partial[chunk][o][c];  db[o] = sum_chunks partial[chunk][o][Cin]     (row stride Cin + 4)
 // One wave per output element: lanes stride over the chunks (independent loads), then a fixed butterfly (deterministic).
-__global__ __launch_bounds__(256) void k_head_reduce(const float* __restrict__ partial, int chunks, int Cin, int Cout,
+template <typename ACC>
+__global__ __launch_bounds__(256) void k_head_reduce(const ACC* __restrict__ partial, int chunks, int Cin, int Cout,
                                                       float* __restrict__ dw, float* __restrict__ db) {
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -513,6 +528,7 @@ bool head_supported(int Cin, int Cout) {
     return Cout >= 1 && Cout <= HEAD_MAX_OUT && (Cin == 16 || Cin == 32 || Cin == 64 || Cin == 128 || Cin == 256);
 }
 int head_chunks(int M) { return std::min(1024, (M + 63) / 64); }   // 4 blocks per CU; the reduce walks the chunks
+bool head_sums_in_double(int M) { return M < HEAD_F64_ROWS; }
 
 #define ICN_HEAD_DISPATCH(KERNEL, ...)                                                  \
     switch (Cin) {                                                                      \
@@ -529,11 +545,25 @@ void launch_head_fwd(const float* x, const float* w, const float* bias, float* y
     ICN_HEAD_DISPATCH(k_head_fwd, dim3(blocks), dim3(256), 0, s, x, w, bias, y, M, Cout)
 }
 
+template <typename ACC>
+static void head_bwd(const float* dy, const float* y, const float* x, const float* w, float* dx, float* dw, float* db, ACC* ws, int M,
+                     int Cin, int Cout, hipStream_t s) {
+    const int chunks = head_chunks(M), rows = (M + chunks - 1) / chunks;
+    const dim3 grid(chunks), block(256);
+    switch (Cin) {
+        case 16: hipLaunchKernelGGL((k_head_bwd<4, ACC>), grid, block, 0, s, dy, y, x, w, dx, ws, M, Cout, rows); break;
+        case 32: hipLaunchKernelGGL((k_head_bwd<8, ACC>), grid, block, 0, s, dy, y, x, w, dx, ws, M, Cout, rows); break;
+        case 64: hipLaunchKernelGGL((k_head_bwd<16, ACC>), grid, block, 0, s, dy, y, x, w, dx, ws, M, Cout, rows); break;
+        case 128: hipLaunchKernelGGL((k_head_bwd<32, ACC>), grid, block, 0, s, dy, y, x, w, dx, ws, M, Cout, rows); break;
+        default: hipLaunchKernelGGL((k_head_bwd<64, ACC>), grid, block, 0, s, dy, y, x, w, dx, ws, M, Cout, rows); break;
+    }
+    hipLaunchKernelGGL(k_head_reduce<ACC>, dim3((Cout * (Cin + 1) + 3) / 4), block, 0, s, ws, chunks, Cin, Cout, dw, db);
+}
+
 void launch_head_bwd(const float* dy, const float* y, const float* x, const float* w, float* dx, float* dw, float* db, float* ws,
                      int M, int Cin, int Cout, hipStream_t s) {
-    const int chunks = head_chunks(M), rows = (M + chunks - 1) / chunks;
-    ICN_HEAD_DISPATCH(k_head_bwd, dim3(chunks), dim3(256), 0, s, dy, y, x, w, dx, ws, M, Cout, rows)
-    hipLaunchKernelGGL(k_head_reduce, dim3((Cout * (Cin + 1) + 3) / 4), dim3(256), 0, s, ws, chunks, Cin, Cout, dw, db);
+    if (head_sums_in_double(M)) head_bwd<double>(dy, y, x, w, dx, dw, db, reinterpret_cast<double*>(ws), M, Cin, Cout, s);
+    else head_bwd<float>(dy, y, x, w, dx, dw, db, ws, M, Cin, Cout, s);
 }
 #undef ICN_HEAD_DISPATCH
 

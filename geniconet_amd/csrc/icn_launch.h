@@ -184,9 +184,10 @@ void launch_bn_relu_bwd(const float* dy, const float* a, const float* b, const f
                         const float* ba, const float* gb, const float* bb, float* da, float* db, float* sums, float* ws, int M, int C,
                         float* dbeta_a, float* dgamma_a, float* dbeta_b, float* dgamma_b, hipStream_t s);   // parameter gradients (nullable)
 
-// ---- fused 1x1 head + tanh (icn_bn.hip); ws = head_chunks(M) * 4 * (Cin + 4) floats
+// ---- fused 1x1 head + tanh (icn_bn.hip); ws = head_chunks(M) * 4 * (Cin + 4) floats, or as many doubles where head_sums_in_double(M)
 bool head_supported(int Cin, int Cout);
 int head_chunks(int M);
+bool head_sums_in_double(int M);
 void launch_head_fwd(const float* x, const float* w, const float* bias, float* y, int M, int Cin, int Cout, hipStream_t s);
 void launch_head_bwd(const float* dy, const float* y, const float* x, const float* w, float* dx, float* dw, float* db, float* ws,
                      int M, int Cin, int Cout, hipStream_t s);

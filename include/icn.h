@@ -154,7 +154,8 @@ int icn_bn_relu_bwd(const float* dy, const float* a, const float* b, const float
 
 /* Fused output head  y = tanh(x W^T + b)  (reference models.py:151-154: Conv2d(64, 3, 1x1) + Tanh).
  * x (M, Cin) channels-last rows, w (Cout, Cin), Cin in {16,32,64,128,256}, Cout <= 4; y (M, Cout).
- * icn_head_bwd: dx (may be NULL), dw (Cout, Cin), db (Cout); ws >= icn_head_workspace_floats(M, Cin) floats. */
+ * icn_head_bwd: dx (may be NULL), dw (Cout, Cin), db (Cout); ws >= icn_head_workspace_floats(M, Cin) floats, 8-byte aligned
+ * (below 1024 rows the partial sums in it are doubles). */
 size_t icn_head_workspace_floats(int M, int Cin);
 int icn_head_fwd(const float* x, const float* w, const float* bias, float* y, int M, int Cin, int Cout, void* stream);
 int icn_head_bwd(const float* dy, const float* y, const float* x, const float* w, float* dx, float* dw, float* db, float* ws,

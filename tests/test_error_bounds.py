@@ -164,3 +164,89 @@ def test_production_case_list_covers_the_three_configurations():
 def test_a_dropped_term_stays_detectable_at_production_sum_lengths(case):
     for out, n in eb.n_terms(*case).items():
         assert eb.detectable(n, out), (out, n, 1.0 / (n * eb.U), 4 * eb.bar(out))
+
+
+# ---- the streaming kernels off the production shapes (tests/test_gpu_streaming_edges.py) ------------------------------------------
+# Each bound A is validated before any GPU run: an fp32 restatement of the kernel's arithmetic must stay under a quarter of RHO_MAX
+# (y, dx, KLD, reparameterisation) or half of BN_STAT_MAX (statistics, affine gradients).  Measured here: BatchNorm y 2.6, dx 2.8,
+# dgamma 1.0, dbeta 1.0, mean 1.1, var 2.4, at most 0.22 % of the ReLU pattern flipped; KLD value 0.7, dmu 2.5, dlogvar 2.3;
+# reparameterisation z 1.2, dlogvar 1.3.
+def test_batchnorm_edge_case_list_covers_every_width_family_and_form():
+    cases = eb.bn_edge_cases()
+    assert 36 <= len(cases) <= 44
+    for C in eb.BN_EDGE_C:
+        mine = [c for c in cases if c[1] == C]
+        assert {c[0] for c in mine} >= set(eb.BN_EDGE_M)
+        assert {c[3] for c in mine} == {0, 1, 2} and {c[2] for c in mine} == {False, True}
+    for C in (4, 32):
+        assert {c[2] for c in cases if c[:2] == (eb.BN_EMPTY_CHUNK_M, C)} == {False, True}
+    assert max(c[0] * c[1] for c in cases) <= 1.1e6
+    chunks, rows = eb.bn_chunking(eb.BN_EMPTY_CHUNK_M)
+    assert chunks == 512 and (chunks - 1) * rows >= eb.BN_EMPTY_CHUNK_M          # the last chunk starts past the last row
+    for M, C, _, _ in cases:                        # C < 64: the forward's 4 rows per iteration x stripes exceed a chunk's rows
+        if C <= 32:
+            assert 4 * 256 // (C // 4) > eb.bn_chunking(M)[1]
+
+
+@pytest.mark.parametrize('case', eb.bn_edge_cases(), ids=str)
+def test_batchnorm_fp32_restatement_stays_well_inside_the_edge_bars(case):
+    xs, gammas, betas, gy = eb.bn_edge_inputs(case)
+    m = eb.bn_edge_measure(eb.bn_restatement_f32(xs, gammas, betas, gy), xs, gammas, betas, gy)
+    assert m.pop('flips_inside')
+    assert m.pop('flip_share') <= eb.BN_FLIP_SHARE_MAX / 2
+    for name, v in m.items():
+        bar = eb.bn_edge_bar(name)
+        assert v <= (bar / 4 if bar == eb.RHO_MAX else bar / 2), (name, v)
+
+
+def test_batchnorm_edge_bars_flag_a_row_added_twice():
+    """What a broken row clamp of the statistics pass would do: the last row of a chunk enters the sums a second time."""
+    case = (63, 8, False, 0)
+    xs, gammas, betas, gy = eb.bn_edge_inputs(case)
+    twice = [torch.cat([xs[0], xs[0][-1:]])]
+    good = eb.bn_restatement_f32(xs, gammas, betas, gy)
+    bad = eb.bn_restatement_f32(twice, gammas, betas, torch.cat([gy, gy[-1:]]))
+    for k in ('rm0', 'rv0'):
+        good[k] = bad[k]
+    m = eb.bn_edge_measure(good, xs, gammas, betas, gy)
+    assert m['mean0'] >= 4 * eb.BN_STAT_MAX and m['var0'] >= 4 * eb.BN_STAT_MAX, m
+
+
+@pytest.mark.parametrize('family', eb.KLD_FAMILIES)
+@pytest.mark.parametrize('shape', eb.KLD_EDGE_SHAPES, ids=str)
+def test_kld_and_reparam_fp32_restatement_stays_under_a_quarter_of_the_bar(shape, family):
+    import numpy as np
+    mu, lv, eps, g = eb.kld_edge_inputs(shape, family)
+    up = float(np.float32(eb.KLD_UPSTREAM))
+    for (ref, A), got in ((eb.kld_oracle(mu, lv, up), eb.kld_restatement_f32(mu, lv, up)),
+                          (eb.reparam_oracle(mu, lv, eps, g), eb.reparam_restatement_f32(mu, lv, eps, g))):
+        for k in ref:
+            assert eb.rho(np.asarray(got[k]), np.asarray(ref[k]), np.asarray(A[k])) <= eb.RHO_MAX / 4, k
+
+
+def test_kld_edge_shapes_have_the_element_counts_of_the_kernel_edges():
+    import math
+    assert [math.prod(s) for s in eb.KLD_EDGE_SHAPES] == [1, 255, 256, 257, 1024 * 256 + 1]
+
+
+def test_adam_restatement_is_adam():
+    """Three steps of adam_reference_f32 against torch's Adam in float64, within the tolerances of tests/test_optim.py."""
+    import numpy as np
+    for wd in (0.0, 0.01):
+        g = torch.Generator().manual_seed(11)
+        p = torch.randn(4099, generator=g)
+        ref = p.double().clone().requires_grad_()
+        oref = torch.optim.Adam([ref], lr=1e-3, weight_decay=wd)
+        P, Mo, V = p.numpy().copy(), np.zeros(4099, np.float32), np.zeros(4099, np.float32)
+        for step in range(3):
+            lr = 1e-3 * (1 + step)
+            oref.param_groups[0]['lr'] = lr
+            grad = (torch.randn(4099, generator=g) * 10.0 ** (step - 2))
+            ref.grad = grad.double()
+            oref.step()
+            P, Mo, V = eb.adam_reference_f32(P, grad.numpy(), Mo, V, lr, 0.9, 0.999, 1e-8, wd, step + 1)
+            assert P.dtype == Mo.dtype == V.dtype == np.float32
+            assert torch.allclose(torch.from_numpy(P).double(), ref.detach(), rtol=2e-6, atol=1e-7), step
+            for got, k in ((Mo, 'exp_avg'), (V, 'exp_avg_sq')):
+                want = oref.state[ref][k]
+                assert torch.allclose(torch.from_numpy(got).double(), want, rtol=2e-6, atol=3e-7 * float(want.abs().max())), (step, k)

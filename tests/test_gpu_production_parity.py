@@ -83,12 +83,12 @@ def _op(case):
     if kind == 'pair':
         return lambda x, w0, b0, w1, b1: (ico_ref.ico_conv(x, w0, b0, r, stride, 'average'),
                                           ico_ref.ico_conv(x, w1, b1, r, stride, 'average'))
-    if kind == 'upconv':
-        def up(x, w0, b0, w1, b1):
-            u = ico_ref.ico_upsample(x, r, 'average')
-            return ico_ref.ico_conv(u, w0, b0, r + 1, 1, 'average'), ico_ref.ico_conv(u, w1, b1, r + 1, 1, 'average')
-        return up
-    return lambda x, w0, b0: (torch.nn.functional.conv2d(x, w0[..., None], b0),)       # the head's 1x1 part
+    assert kind == 'upconv', kind                       # (the head: error_bounds.head_oracle)
+
+    def up(x, w0, b0, w1, b1):
+        u = ico_ref.ico_upsample(x, r, 'average')
+        return ico_ref.ico_conv(u, w0, b0, r + 1, 1, 'average'), ico_ref.ico_conv(u, w1, b1, r + 1, 1, 'average')
+    return up
 
 
 def _named(case, x, ws, bs):
@@ -100,10 +100,11 @@ def _named(case, x, ws, bs):
 
 def _run_gpu(case, x, ws, bs, gys):
     """The step's own entry point for this operator, forward + backward; the head returns tanh(z) as 'y0'."""
-    from geniconet_amd import fused
     from geniconet_amd.ico_conv import (ico_conv, ico_conv_pair, ico_conv_pair_supported, ico_upconv_pair,
                                         ico_upconv_pair_supported)
     kind, r, stride = case[:3]
+    if kind == 'head':
+        return eb.head_run(x, ws[0], bs[0], gys[0])
     xg = x.cuda().contiguous(memory_format=CL).requires_grad_(kind != 'stem')
     wg = [w.cuda().requires_grad_() for w in ws]
     bg = [b.cuda().requires_grad_() for b in bs]
@@ -112,15 +113,9 @@ def _run_gpu(case, x, ws, bs, gys):
     elif kind == 'pair':
         assert ico_conv_pair_supported(xg, wg[0], wg[1], r, stride)
         ys = ico_conv_pair(xg, wg[0], bg[0], wg[1], bg[1], r, stride, 'average')
-    elif kind == 'upconv':
+    else:
         assert ico_upconv_pair_supported(xg, wg[0], wg[1], r)
         ys = ico_upconv_pair(xg, wg[0], bg[0], wg[1], bg[1], r, 'average')
-    else:
-        seq = torch.nn.Sequential(torch.nn.Conv2d(case[3], case[4], kernel_size=1), torch.nn.Tanh()).cuda()
-        seq[0].weight, seq[0].bias = torch.nn.Parameter(wg[0].detach()[..., None]), torch.nn.Parameter(bg[0].detach())
-        assert fused.can_fuse_head(xg, seq)
-        ys = (fused.head(xg, seq),)
-        wg, bg = [seq[0].weight], [seq[0].bias]
     torch.autograd.backward(ys, [g.cuda() for g in gys])
     out = {'y%d' % i: y.detach().cpu() for i, y in enumerate(ys)}
     if kind != 'stem':
@@ -134,18 +129,12 @@ def _run_gpu(case, x, ws, bs, gys):
 def _measure(case, got, gys, oracle):
     """{output: (rho, rel-L2)} against the oracle (ref, A); for the head: y = tanh(z) in float64, its gradients through the linear
     oracle with the kernel's own dz = gy (1 - y^2)."""
-    if case[0] != 'head':
+    if case[0] == 'head':
+        x, ws, bs, _ = _inputs(case)
+        ref, A = eb.head_oracle(x, ws[0], bs[0], gys[0], got['y0'])
+    else:
         ref, A = oracle
-        return {k: (eb.rho(got[k], ref[k], A[k]), rel_l2(got[k].numpy(), ref[k].numpy())) for k in ref}
-    x, ws, bs, _ = _inputs(case)
-    y = got['y0'].double()
-    gz = gys[0].double() * (1 - y * y)
-    ref, A = eb.oracle_and_bound(_op(case), _named(case, x, ws, bs), [gz])
-    t = torch.tanh(ref['y0'])
-    out = {'y0': (eb.rho(got['y0'], t, (1 - t * t) * A['y0'].double() + t.abs()), rel_l2(got['y0'].numpy(), t.numpy()))}
-    for k in ('dx', 'dw0', 'db0'):
-        out[k] = (eb.rho(got[k], ref[k], A[k]), rel_l2(got[k].numpy(), ref[k].numpy()))
-    return out
+    return {k: (eb.rho(got[k], ref[k], A[k]), rel_l2(got[k].numpy(), ref[k].numpy())) for k in ref}
 
 
 @pytest.mark.parametrize('case', CONV, ids=_cid)
@@ -184,28 +173,7 @@ def _bn_inputs(case, dual):
     return xs, gammas, betas, rm0, rv0, gy
 
 
-def _bn_run(xs, gammas, betas, rm0, rv0, gy, momentum):
-    """fused.bn_relu / bn_add_relu on (1, C, M, 1) channels_last tensors, i.e. the kernels' (M, C) rows."""
-    from geniconet_amd import fused
-    M, C = gy.shape
-    as4 = lambda t: t.t().reshape(1, C, M, 1).cuda().contiguous(memory_format=CL)
-    bns = []
-    for g_, b_, m_, v_ in zip(gammas, betas, rm0, rv0):
-        bn = torch.nn.BatchNorm2d(C, momentum=momentum).cuda().train()
-        with torch.no_grad():
-            bn.weight.copy_(g_); bn.bias.copy_(b_); bn.running_mean.copy_(m_); bn.running_var.copy_(v_)
-        bns.append(bn)
-    ins = [as4(x).requires_grad_() for x in xs]
-    assert fused.can_fuse(ins[0], *bns)
-    y = fused.bn_relu(ins[0], bns[0]) if len(xs) == 1 else fused.bn_add_relu(ins[0], bns[0], ins[1], bns[1])
-    y.backward(as4(gy))
-    rows = lambda t: t.detach().reshape(C, M).t().cpu().double()
-    out = {'y': rows(y)}
-    for i, (a, bn) in enumerate(zip(ins, bns)):
-        out['dx%d' % i] = rows(a.grad)
-        out['dgamma%d' % i], out['dbeta%d' % i] = bn.weight.grad.cpu().double(), bn.bias.grad.cpu().double()
-        out['rm%d' % i], out['rv%d' % i] = bn.running_mean.cpu().double(), bn.running_var.cpu().double()
-    return out
+_bn_run = eb.bn_run
 
 
 @pytest.mark.parametrize('case', BNS, ids=_cid)
