@@ -146,6 +146,17 @@ LATER_HEADERS = {
 }
 
 
+# Every header after those: the same shape, conventions and library, bound in the same loop of lib() and hashed by source_files().
+# This table ends the chain of tables: NO TEST MAY FIX ITS KEY SET.  A new header is one more key here and one more ABI test file that
+# names only its own header (icn_voxel.h: tests/test_abi_voxel.py), so adding a header never needs another table.
+UNPINNED_HEADERS = {
+    'icn_voxel.h': {                   # solid voxelisation by ray parity
+        'icn_mesh_voxelize': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_double] * 4 + [ctypes.c_int] * 3
+                              + [ctypes.c_void_p, ctypes.c_void_p], RC),
+    },
+}
+
+
 class ProfileEntry(ctypes.Structure):
     _fields_ = [('kernel', ctypes.c_char_p), ('launches', ctypes.c_long), ('total_ms', ctypes.c_double),
                 ('total_flops', ctypes.c_double)]
@@ -179,7 +190,7 @@ def lib():
                 '(or `make -C geniconet_amd/csrc`).' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
         checked = types.SimpleNamespace()
-        for name, (res, args, reply) in [item for table in (SIGNATURES, *EXTENSION_HEADERS.values(), *LATER_HEADERS.values()) for item in table.items()]:
+        for name, (res, args, reply) in [item for table in (SIGNATURES, *EXTENSION_HEADERS.values(), *LATER_HEADERS.values(), *UNPINNED_HEADERS.values()) for item in table.items()]:
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             fn = handle[name]            # a function object of its own (handle.name is cached, handle[name] is not)
@@ -243,9 +254,9 @@ def set_arith(mode):
 
 def source_files():
     """The files source_sha256() hashes, sorted: the kernel / library sources under csrc/, include/icn.h and every header of
-    EXTENSION_HEADERS and LATER_HEADERS."""
+    EXTENSION_HEADERS, LATER_HEADERS and UNPINNED_HEADERS."""
     import glob
-    headers = [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('icn.h', *EXTENSION_HEADERS, *LATER_HEADERS)]
+    headers = [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('icn.h', *EXTENSION_HEADERS, *LATER_HEADERS, *UNPINNED_HEADERS)]
     return sorted([f for pattern in ('*.hip', '*.h', '*.cpp') for f in glob.glob(os.path.join(_HERE, 'csrc', pattern))] + headers)
 
 

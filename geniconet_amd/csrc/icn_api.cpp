@@ -18,6 +18,7 @@
 #include "../../include/icn_gauss.h"
 #include "../../include/icn_isect.h"
 #include "../../include/icn_sdf.h"
+#include "../../include/icn_voxel.h"
 #include "../../include/icn_measure.h"
 #include "icn_geometry.h"
 #include "icn_launch.h"
@@ -794,7 +795,8 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_fnormal_agree_bwd_vertex",    // every ..._bwd_vertex: k_vertex_scatter, by its caller
                                             "k_mesh_measure_face", "k_mesh_measure_finish", "k_mesh_measure_bwd",
                                             "k_mesh_cotlap_fwd", "k_mesh_willmore_finish", "k_mesh_willmore_upstream", "k_mesh_cotlap_bwd",
-                                            "k_mesh_angle_defect_fwd", "k_mesh_angle_defect_bwd", "k_mesh_self_intersect", "k_p2m_sign"};
+                                            "k_mesh_angle_defect_fwd", "k_mesh_angle_defect_bwd", "k_mesh_self_intersect", "k_p2m_sign",
+                                            "k_mesh_voxelize"};
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1575,6 +1577,21 @@ int icn_point_to_mesh_sign(const float* points, const float* vertices, const int
         check_mesh_sizes("icn_point_to_mesh_sign", B, P, V, F);
         check_measure_sizes("icn_point_to_mesh_sign", B, V, F);
         icn::launch_point_to_mesh_sign(points, vertices, faces, adjacency, vf_offsets, vf_corners, face, kind, B, P, V, F, sign, s);
+    });
+}
+
+// ---- solid voxelisation by ray parity (include/icn_voxel.h): the sizes of the measure entries, and a lattice ---------------------------
+static_assert(ICN_VOXEL_MAX_DEPTH == icn::VOXEL_MAX_DEPTH, "the kernel's parity words hold ICN_VOXEL_MAX_DEPTH bits");
+int icn_mesh_voxelize(const float* vertices, const int32_t* faces, int B, int V, int F, double origin_x, double origin_y, double origin_z,
+                      double spacing, int n0, int n1, int n2, uint8_t* occupancy, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!vertices || !faces || !occupancy) throw std::invalid_argument("icn_mesh_voxelize: null pointer");
+        check_measure_sizes("icn_mesh_voxelize", B, V, F);
+        if (n0 < 1 || n0 > ICN_VOXEL_MAX_DEPTH || n1 < 1 || n1 > ICN_VOXEL_MAX_SIDE || n2 < 1 || n2 > ICN_VOXEL_MAX_SIDE ||
+            !std::isfinite(origin_x) || !std::isfinite(origin_y) || !std::isfinite(origin_z) || !std::isfinite(spacing) || !(spacing > 0.0))
+            throw std::invalid_argument("icn_mesh_voxelize: bad sizes");
+        icn::launch_mesh_voxelize(vertices, faces, B, V, F, origin_x, origin_y, origin_z, spacing, n0, n1, n2, occupancy, s);
     });
 }
 

@@ -298,6 +298,13 @@ void launch_point_to_mesh_sign(const float* pts, const float* vts, const int32_t
                                const int32_t* corners, const int32_t* face, const int32_t* kind, int B, int P, int V, int F, float* sign,
                                hipStream_t s);
 
+// solid voxelisation by ray parity (icn_voxel.hip; include/icn_voxel.h): one thread per lattice column (j, k) against the faces of its
+// mesh through culled LDS tiles, double arithmetic, n0 parity bits per column.  One launch on s, no workspace; n0 <= VOXEL_MAX_DEPTH,
+// n1, n2 <= 4096 (checked by the entry: the tiles of columns fit gridDim.x).
+constexpr int VOXEL_MAX_DEPTH = 512;
+void launch_mesh_voxelize(const float* vts, const int32_t* faces, int B, int V, int F, double ox, double oy, double oz, double h, int n0,
+                          int n1, int n2, uint8_t* occ, hipStream_t s);
+
 // developer routing flags (ICN_DEBUG / icn_set_debug_flags): 16 = convs on k_gather_gemm, 32 = wgrads on k_wgrad,
 // 128 = no stream-K, 256 = fault injection: every stream-K finisher reports its partners lost (tests of the failure path),
 // 512 = masked launches walk tiles b, b + G, ... instead of the balanced tile lists, 1024 = the sparse passes of the decoder-block
@@ -308,7 +315,7 @@ int debug_flags();
 int set_debug_flags(int flags);
 
 // ---- optional per-launch HIP-event timing of the MFMA kernels (bench.py's live roofline measurement) and of the
-// point-to-mesh, surface-sampling, normal-agreement, mesh-measure, mesh-curvature, angle-defect, self-intersection and distance-sign kernels ----------
+// point-to-mesh, surface-sampling, normal-agreement, mesh-measure, mesh-curvature, angle-defect, self-intersection, distance-sign and voxelisation kernels ----------
 enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA_64x64, PROF_GG_128x128, PROF_GG_128x64,
                 PROF_GG_64x128, PROF_GG_64x64, PROF_WGD_128x128, PROF_WGD_128x64, PROF_WGD_64x128, PROF_WGD_64x64, PROF_WG_128x128,
                 PROF_WG_128x64, PROF_WG_64x128, PROF_WG_64x64,
@@ -330,6 +337,7 @@ enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA
                 PROF_MESH_ANGLE_DEFECT_FWD, PROF_MESH_ANGLE_DEFECT_BWD,                             // angle defect (Gaussian curvature)
                 PROF_MESH_SELF_INTERSECT,                                                           // self-intersection count
                 PROF_P2M_SIGN,                                                                      // sign of the point-to-mesh distance
+                PROF_MESH_VOXELIZE,                                                                 // solid voxelisation by ray parity
                 PROF_KINDS };
 extern const char* const PROF_NAMES[PROF_KINDS];
 void prof_mark_begin(int kind, double flops, hipStream_t s);   // no-ops unless profiling is on

@@ -63,6 +63,15 @@ of the feature q lies on -- the face normal, the sum of the two unit normals at 
 vertex_face_table, in double; no second search, and the gradient is that of dist2 under a rescaled upstream).  contains is kaolin's
 check_sign; volumetric_iou is the intersection over union of the solids of one mesh pair on a lattice, to stand beside volume_error
 and compute_distance.  Its lattice points lie mostly far from the surface, where 'grid' falls back to the linear scan (above).
+
+voxel_lattice, voxelize and volumetric_iou(method='voxel') (below) fill a lattice without any search: rays along axis 0, one per
+lattice column, and a cell is inside iff an odd number of faces cross its column at or before it (icn_mesh_voxelize, include/
+icn_voxel.h: one thread per column against the faces of its mesh, which pass through LDS tiles culled against the workgroup's tile of
+columns; double arithmetic with a symbolic perturbation, so every column crosses a closed mesh an even number of times whatever lies
+on an edge or a vertex; n0 parity bits per column and one prefix XOR, no atomics).  It visits each (column, face) pair once where
+contains visits each (cell, face) pair, it needs no adjacency table, and it is right for any closed mesh whatever its winding: the
+occupancy grid that the reference's users otherwise take from kaolin.  Bools, no gradient; the HIP path reproduces the float64
+formulation byte for byte.
 """
 import torch
 
@@ -1249,19 +1258,11 @@ def contains(points, vertices, faces, search='brute', tables=None):
         return _signed_point_to_mesh_distance_unchecked(points, vertices, f32, tables, search)[0] < 0
 
 
-def volumetric_iou(outvertices, refvertices, faces, resolution=32, search='brute'):
-    """|A and B| / |A or B| of the solids two closed meshes enclose ((V, 3) tensors sharing `faces`), counted on a lattice, as a Python
-    float: the standard volumetric figure of a reconstruction, to stand beside volume_error, curvature_error, self_intersection_ratio
-    and compute_distance.  0 when no lattice point lies in either.
-    The lattice: [lo, hi] the joint bounding box of both meshes (one read-back), h = largest extent / resolution,
-    n_k = max(1, ceil(extent_k / h)) evaluated in float64 on the host, cell centres lo_k + (i + 1/2) h.  Both meshes go through
-    `contains` as one batch of two; the counts are taken on the device.  A cell is misclassified only if its centre is within
-    h sqrt(3) / 2 of the surface, so each volume is off by at most sqrt(3) area h.
-    What it costs: n_0 n_1 n_2 points per mesh, up to resolution^3, each through the closest-triangle search -- and the lattice points
-    deep inside or far outside are exactly the regime where search='grid' gives up its walk and scans all triangles (module docstring),
-    so 'brute' is the default: on an MI355X one I5 pair (20 480 faces) takes 11 ms at resolution 32 and 21 ms at 64 with 'brute', 20 and 23 ms with
-    'grid' (profiles/signed_distance.txt from tools/time_signed_distance.py).  A
-    voxeliser that counts ray parities per lattice column would be the next step; it is not part of this module."""
+def voxel_lattice(outvertices, refvertices, resolution):
+    """(origin, spacing, counts) of the lattice volumetric_iou counts on, for two (V, 3) vertex tensors of one shape: [lo, hi] the joint
+    bounding box of both meshes (one read-back), origin = lo as three Python floats, spacing h = largest extent / resolution,
+    counts n_k = max(1, ceil(extent_k / h)), all evaluated in float64 on the host.  Cell (i, j, k) has its centre at
+    origin + ((i, j, k) + 1/2) h.  ValueError for other shapes, resolution < 1 or a box that is not finite or has no extent."""
     who = 'volumetric_iou'
     if outvertices.dim() != 2 or refvertices.dim() != 2 or outvertices.shape != refvertices.shape or outvertices.shape[-1] != 3:
         raise ValueError('%s: expected two (V, 3) vertex tensors of one shape, got %s and %s'
@@ -1276,10 +1277,197 @@ def volumetric_iou(outvertices, refvertices, faces, resolution=32, search='brute
         raise ValueError('%s: the meshes have no finite bounding box of positive extent' % who)
     import math
     h = max(extent) / int(resolution)
-    counts = [max(1, math.ceil(e / h)) for e in extent]
-    axes = [box[0][k] + (torch.arange(counts[k], dtype=torch.float64, device=both.device) + 0.5) * h for k in range(3)]
-    centres = torch.stack(torch.meshgrid(*axes, indexing='ij'), -1).reshape(1, -1, 3).to(both.dtype)
-    inside = contains(centres.expand(2, -1, -1).contiguous(), both, faces, search=search)
+    return tuple(box[0]), h, tuple(max(1, math.ceil(e / h)) for e in extent)
+
+
+# ---- solid voxelisation by ray parity --------------------------------------------------------------------------------------------------
+_VOXEL_MAX_DEPTH, _VOXEL_MAX_SIDE = 512, 4096                                             # ICN_VOXEL_MAX_DEPTH / _SIDE of include/icn_voxel.h
+
+
+def _torch_voxelize(vertices, faces, origin, spacing, counts, cells=1 << 20):
+    """The definition of voxelize in torch: float64 on the vertices as stored, every product and sum an operation of its own, in the
+    order of include/icn_voxel.h -> bool (B, n0, n1, n2).  Chunked over the faces so that one intermediate holds about `cells`
+    (mesh, column, face) triples; ids are clamped before they index anything and non-finite values meet only masked arithmetic."""
+    B, V = vertices.shape[0], vertices.shape[1]
+    n0, n1, n2 = (int(n) for n in counts)
+    (ox, oy, oz), h = (float(o) for o in origin), float(spacing)
+    dev = vertices.device
+    v, ids = vertices.detach().double(), faces.long()
+    F, C = ids.shape[0], n1 * n2
+    py = (oy + (torch.arange(n1, dtype=torch.float64, device=dev) + 0.5) * h)[:, None].expand(n1, n2).reshape(1, C, 1)
+    pz = (oz + (torch.arange(n2, dtype=torch.float64, device=dev) + 0.5) * h)[None, :].expand(n1, n2).reshape(1, C, 1)
+    flips = torch.zeros(B, C, n0 + 1, dtype=torch.int32, device=dev)                      # crossings by k0; slot n0 is behind the lattice
+    step = max(1, cells // (B * C))
+    for lo in range(0, F, step):
+        f = ids[lo:lo + step]                                                             # (c, 3)
+        tri = v[:, f.clamp(0, V - 1)]                                                     # (B, c, 3 corners, 3)
+        ok = ((f >= 0) & (f < V)).all(-1)[None] & torch.isfinite(tri).all(-1).all(-1)     # (B, c)
+        x, y, z = (tri[..., k][:, None] for k in range(3))                                # (B, 1, c, 3 corners)
+        covered = (ok[:, None] & (y.amin(-1) <= py) & (py <= y.amax(-1)) & (z.amin(-1) <= pz) & (pz <= z.amax(-1)))      # (B, C, c): tested
+        s, positive, negative = [], covered, covered
+        for e in range(3):                                                                # the edge opposite vertex e: u -> w
+            u, w = (e + 1) % 3, (e + 2) % 3
+            as_given = f[:, u] < f[:, w]                                                  # (c,): else the ends are swapped
+            ay, az = torch.where(as_given, y[..., u], y[..., w]), torch.where(as_given, z[..., u], z[..., w])
+            by, bz = torch.where(as_given, y[..., w], y[..., u]), torch.where(as_given, z[..., w], z[..., u])
+            dy, dz = by - ay, bz - az
+            value = dy * (pz - az) - dz * (py - ay)                                       # (B, C, c)
+            t = torch.sign(value)
+            t = torch.where(t == 0, torch.sign(-dz), t)
+            t = torch.where(t == 0, torch.sign(dy), t)
+            s.append(torch.where(as_given, value, -value))
+            t = torch.where(as_given, t, -t)
+            positive, negative = positive & (t > 0), negative & (t < 0)
+        covered = positive | negative
+        depth = (s[0] * x[..., 0] + s[1] * x[..., 1] + s[2] * x[..., 2]) / (s[0] + s[1] + s[2])
+        tau = (depth - ox) / h - 0.5
+        covered = covered & torch.isfinite(tau)
+        k0 = torch.where(covered, torch.ceil(tau).clamp(0, n0), torch.full_like(tau, n0)).long()
+        flips.scatter_add_(2, k0, covered.to(torch.int32))
+    inside = (flips[..., :n0].cumsum(2) & 1).bool()                                       # (B, C, n0)
+    return inside.permute(0, 2, 1).reshape(B, n0, n1, n2)
+
+
+def _hip_voxelize(vts, f32, origin, spacing, counts):
+    """icn_mesh_voxelize on contiguous fp32 ROCm vertices and an int32 face table -> bool (B, n0, n1, n2)."""
+    B, V, F = vts.shape[0], vts.shape[1], f32.shape[0]
+    n0, n1, n2 = (int(n) for n in counts)
+    occupancy = torch.empty(B, n0, n1, n2, dtype=torch.uint8, device=vts.device)
+    _launch('icn_mesh_voxelize', _per_mesh(vts), f32, _NB, V, F, *(float(o) for o in origin), float(spacing), n0, n1, n2,
+            _per_mesh(occupancy))
+    return occupancy.view(torch.bool)                                                     # bytes 0 / 1, each written once
+
+
+def _voxelize_unchecked(vertices, f32, origin, spacing, counts):
+    """voxelize without its argument checks and without a host synchronisation, for callers that validated once: f32 is an int32
+    (F, 3) tensor on the vertices' device, F >= 1; origin three floats, spacing a positive float, counts three positive ints -- on the
+    HIP path within (512, 4096, 4096), else the entry refuses them.  A vertex id out of range or a non-finite vertex is safe on either
+    path: that face is not tested.  A mesh that is not closed gives what the definition gives: whole columns wrong."""
+    if _on_hip_path(vertices):
+        return _hip_voxelize(vertices.detach().contiguous(), f32, origin, spacing, counts)
+    return _torch_voxelize(vertices, f32, origin, spacing, counts)
+
+
+def _odd_edges(f32, V):
+    """report int64 (5,) of a face list, without a host synchronisation: (lowest id, highest id, the number of undirected edges that
+    belong to an odd number of faces, the (a, b), a < b, of the first of them in the order of a V + b).  The three edges of every
+    face are keyed by their sorted ends and the keys sorted; an edge from a vertex to itself has no extent and is left out."""
+    f = f32.long()
+    a, b = f.reshape(-1), torch.roll(f, -1, 1).reshape(-1)
+    low, high = torch.minimum(a, b), torch.maximum(a, b)
+    key = torch.where(low != high, low * V + high, torch.full_like(low, -1))              # -1: left out, sorted to the front
+    ordered, _ = torch.sort(key)
+    at = torch.arange(ordered.numel(), device=ordered.device)
+    first = torch.ones_like(ordered, dtype=torch.bool)
+    first[1:] = ordered[1:] != ordered[:-1]
+    last = torch.ones_like(first)
+    last[:-1] = first[1:]
+    start = torch.where(first, at, torch.zeros_like(at)).cummax(0)[0]                      # where each element's run begins
+    odd = last & ((at - start) % 2 == 0) & (ordered >= 0)                                 # the run's last element has an even rank
+    where = ordered.index_select(0, odd.to(torch.int8).argmax().reshape(1))
+    lo, hi = f.aminmax()
+    return torch.cat([lo.reshape(1), hi.reshape(1), odd.sum().reshape(1), where // V, where % V])
+
+
+def voxelize(vertices, faces, origin, spacing, counts):
+    """bool (B, n0, n1, n2): for every cell of a lattice whether its centre lies inside the closed triangle mesh vertices (B, V, 3),
+    faces (F, 3) integer and shared by the batch.  Cell (i, j, k) has its centre at origin + ((i, j, k) + 1/2) spacing; origin is
+    three floats, spacing a positive float, counts = (n0, n1, n2) (voxel_lattice gives all three for a mesh pair).  kaolin's
+    trianglemeshes_to_voxelgrids followed by a fill, as one exact operation.  Never requires grad.
+
+    One definition for the HIP kernel (include/icn_voxel.h), the torch formulation and the tests.  Rays run along axis 0 and the mesh
+    is projected onto (y, z); a column is (j, k) with p = (py, pz), py = origin[1] + (j + 0.5) h, pz likewise.  All arithmetic is
+    float64 on the vertices as stored, every product and sum rounded on its own, in exactly the order written:
+        a face is TESTED for a column iff its ids lie in [0, V), its nine coordinates are finite, and lo_y <= py <= hi_y and
+            lo_z <= pz <= hi_z against the minimum / maximum of its vertices -- part of the definition, not a filter
+        the value of a directed edge u -> w, on (a, b) = (u, w) if id_u < id_w, else (w, u):
+            s = (b.y - a.y) (pz - a.z) - (b.z - a.z) (py - a.y);  t = sign(s), if 0 sign(-(b.z - a.z)), if still 0 sign(b.y - a.y)
+            (the symbolic perturbation p + (eps, eps^2)), both negated if the ends were swapped: the two faces of an edge evaluate one
+            expression and get opposite values
+        the face COVERS the column iff t > 0 for its three edges or t < 0 for all three
+        its crossing, from the raw values s0, s1, s2 of the edges opposite vertices 0, 1, 2:
+            x = (s0 v0.x + s1 v1.x + s2 v2.x) / (s0 + s1 + s2),  tau = (x - origin[0]) / h - 0.5, dropped if not finite,
+            k0 = clamp(ceil(tau), 0, n0)
+        cell i of the column is occupied iff the number of crossings with k0 <= i is odd.
+    So a centre exactly on the surface counts the low side as inside ([0, 1) on every axis), the winding of the faces plays no part
+    (where contains needs a consistently wound mesh), a mesh that passes through itself gets the XOR fill, and a face with
+    coincident vertices, a non-finite vertex or (in the unchecked form) an id out of range contributes nothing.  On a mesh that is NOT
+    CLOSED a column through the hole is wrong for its whole length, so this function checks, with the read-back that checks the face
+    ids, that every undirected edge belongs to an even number of faces and raises ValueError naming the first that does not.
+    ROCm fp32 tensors run on icn_mesh_voxelize: one thread per (mesh, column) in 16 x 16 tiles of columns, the faces staged through
+    LDS and culled against the tile's box while they are staged, n0 <= 512 parity bits per column, n1, n2 <= 4096; no atomics,
+    bit-identical run to run and equal to the float64 formulation byte for byte.  ICN_NO_HIP_LOSS=1, CPU tensors and other dtypes
+    take that formulation in torch (_torch_voxelize), chunked over the faces.
+    Shapes, the lattice and the closedness are checked (ValueError); face ids against V in the same read-back (IndexError)."""
+    who = 'voxelize'
+    if vertices.dim() != 3 or vertices.shape[-1] != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1 or not vertices.is_floating_point():
+        raise ValueError('%s: expected floating-point vertices (B, V, 3), got %s' % (who, tuple(vertices.shape)))
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1 or faces.is_floating_point() or faces.dtype == torch.bool:
+        raise ValueError('%s: expected integer faces (F, 3) with F >= 1, got %s' % (who, tuple(faces.shape)))
+    V, F = vertices.shape[1], faces.shape[0]
+    if 3 * F > 0x7fffffff:
+        raise ValueError('%s: %d faces: 3 F must fit an int32' % (who, F))
+    try:
+        origin, spacing = tuple(float(o) for o in origin), float(spacing)
+        if any(int(n) != n for n in counts):
+            raise ValueError
+        counts = tuple(int(n) for n in counts)
+    except (TypeError, ValueError):
+        raise ValueError('%s: origin must be three numbers, spacing a number and counts three integers' % who)
+    finite = all(x == x and abs(x) != float('inf') for x in origin + (spacing,))
+    if len(origin) != 3 or len(counts) != 3 or not finite or not spacing > 0 or min(counts) < 1:
+        raise ValueError('%s: expected a finite origin of three numbers, a finite spacing > 0 and three counts >= 1, got %r, %r, %r'
+                         % (who, origin, spacing, counts))
+    if _on_hip_path(vertices) and (counts[0] > _VOXEL_MAX_DEPTH or max(counts[1:]) > _VOXEL_MAX_SIDE):
+        raise ValueError('%s: counts %r: the HIP path takes at most (%d, %d, %d)'
+                         % (who, counts, _VOXEL_MAX_DEPTH, _VOXEL_MAX_SIDE, _VOXEL_MAX_SIDE))
+    f32 = faces.to(device=vertices.device, dtype=torch.int32).contiguous()
+    lo, hi, n_odd, a, b = _odd_edges(f32, V).tolist()                                     # the one read-back
+    if lo < 0 or hi >= V:
+        raise IndexError('%s: faces index [%d, %d] but there are %d vertices' % (who, lo, hi, V))
+    if n_odd:
+        raise ValueError('%s: the mesh is not closed: the edge (%d, %d) belongs to an odd number of faces (%d such edges); a ray '
+                         'through the hole would be wrong for its whole length' % (who, a, b, n_odd))
+    with torch.no_grad():
+        return _voxelize_unchecked(vertices, f32, origin, spacing, counts)
+
+
+_IOU_METHODS = ('search', 'voxel')
+
+
+def volumetric_iou(outvertices, refvertices, faces, resolution=32, search='brute', method='search'):
+    """|A and B| / |A or B| of the solids two closed meshes enclose ((V, 3) tensors sharing `faces`), counted on a lattice, as a Python
+    float: the standard volumetric figure of a reconstruction, to stand beside volume_error, curvature_error, self_intersection_ratio
+    and compute_distance.  0 when no lattice point lies in either.
+    The lattice is voxel_lattice(outvertices, refvertices, resolution): [lo, hi] the joint bounding box of both meshes (one
+    read-back), h = largest extent / resolution, n_k = max(1, ceil(extent_k / h)) evaluated in float64 on the host, cell centres
+    lo_k + (i + 1/2) h.  A cell is misclassified only if its centre is within h sqrt(3) / 2 of the surface, so each volume is off by
+    at most sqrt(3) area h.
+    method='search' (the default): both meshes go through `contains` as one batch of two; the counts are taken on the device.  That is
+    n_0 n_1 n_2 points per mesh, up to resolution^3, each through the closest-triangle search -- and the lattice points deep inside or
+    far outside are exactly the regime where search='grid' gives up its walk and scans all triangles (module docstring), so 'brute'
+    is the default `search`: on an MI355X one I5 pair (20 480 faces) takes 11 ms at resolution 32 and 21 ms at 64 with 'brute', 20
+    and 23 ms with 'grid' (profiles/signed_distance.txt from tools/time_signed_distance.py).  The sign needs a consistently wound
+    mesh.
+    method='voxel': both meshes go through `voxelize` on that lattice as one batch of two, the counts are taken on the device with
+    one read-back; `search` plays no part.  One ray per lattice column instead of one search per cell, right for any closed mesh
+    whatever its winding, and resolution up to 512 on the HIP path.  On an MI355X the same I5 pair takes 1.4 ms at resolution 32 and
+    1.2 ms at 64, 7.5 and 17.6 times faster than 'search' with 'brute' in the same process and the same IoU to every printed digit,
+    and 0.94 / 0.88 ms at 128 / 256 -- host time throughout: the kernel fills 128^3 cells for a batch of 36 in 1.10 ms, beside 8.55 ms
+    for k_mesh_self_intersect on the same meshes, and 7.61 ms without its tile culling (profiles/voxelize.txt from
+    tools/time_voxelize.py).  The default stays 'search'."""
+    who = 'volumetric_iou'
+    if method not in _IOU_METHODS:
+        raise ValueError('%s: method must be one of %s, got %r' % (who, _IOU_METHODS, method))
+    _check_search(search)
+    origin, h, counts = voxel_lattice(outvertices, refvertices, resolution)
+    both = torch.stack([outvertices, refvertices.to(device=outvertices.device, dtype=outvertices.dtype)]).detach()
+    if method == 'voxel':
+        inside = voxelize(both, faces, origin, h, counts).reshape(2, -1)
+    else:
+        axes = [origin[k] + (torch.arange(counts[k], dtype=torch.float64, device=both.device) + 0.5) * h for k in range(3)]
+        centres = torch.stack(torch.meshgrid(*axes, indexing='ij'), -1).reshape(1, -1, 3).to(both.dtype)
+        inside = contains(centres.expand(2, -1, -1).contiguous(), both, faces, search=search)
     n_and, n_or = torch.stack([(inside[0] & inside[1]).sum(), (inside[0] | inside[1]).sum()]).tolist()
     return n_and / n_or if n_or else 0.0
 

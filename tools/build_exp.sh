@@ -12,6 +12,6 @@ for n in "$@"; do
 done
 wait
 for n in "$@"; do
-  /opt/rocm/bin/hipcc $FLAGS -shared -o build_exp/libicn_exp$n.so build_exp/icn_kernels_$n.o build/icn_api.o build/icn_geometry.o build/icn_bn.o build/icn_loss.o build/icn_sample.o build/icn_measure.o build/icn_curvature.o build/icn_gauss.o build/icn_isect.o build/icn_sdf.o build/icn_optim.o
+  /opt/rocm/bin/hipcc $FLAGS -shared -o build_exp/libicn_exp$n.so build_exp/icn_kernels_$n.o build/icn_api.o build/icn_geometry.o build/icn_bn.o build/icn_loss.o build/icn_sample.o build/icn_measure.o build/icn_curvature.o build/icn_gauss.o build/icn_isect.o build/icn_sdf.o build/icn_voxel.o build/icn_optim.o
 done
 ls -la build_exp/*.so
