@@ -148,11 +148,17 @@ LATER_HEADERS = {
 
 # Every header after those: the same shape, conventions and library, bound in the same loop of lib() and hashed by source_files().
 # This table ends the chain of tables: NO TEST MAY FIX ITS KEY SET.  A new header is one more key here and one more ABI test file that
-# names only its own header (icn_voxel.h: tests/test_abi_voxel.py), so adding a header never needs another table.
+# names only its own header (icn_voxel.h: tests/test_abi_voxel.py, icn_raycast.h: tests/test_abi_raycast.py), so adding a header never needs another table.
 UNPINNED_HEADERS = {
     'icn_voxel.h': {                   # solid voxelisation by ray parity
         'icn_mesh_voxelize': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_double] * 4 + [ctypes.c_int] * 3
                               + [ctypes.c_void_p, ctypes.c_void_p], RC),
+    },
+    'icn_raycast.h': {                 # ray casting: first hit and crossing count per ray, and the backward of the depth
+        'icn_mesh_raycast': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 4 + [_c_float_p] * 3 + [ctypes.c_void_p], RC),
+        'icn_mesh_raycast_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 3, PLAIN),
+        'icn_mesh_raycast_bwd': (ctypes.c_int, [_c_float_p] * 6 + [ctypes.c_int] * 4 + [_c_float_p] * 3
+                                 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
     },
 }
 

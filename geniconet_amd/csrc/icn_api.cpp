@@ -19,6 +19,7 @@
 #include "../../include/icn_isect.h"
 #include "../../include/icn_sdf.h"
 #include "../../include/icn_voxel.h"
+#include "../../include/icn_raycast.h"
 #include "../../include/icn_measure.h"
 #include "icn_geometry.h"
 #include "icn_launch.h"
@@ -796,7 +797,8 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_mesh_measure_face", "k_mesh_measure_finish", "k_mesh_measure_bwd",
                                             "k_mesh_cotlap_fwd", "k_mesh_willmore_finish", "k_mesh_willmore_upstream", "k_mesh_cotlap_bwd",
                                             "k_mesh_angle_defect_fwd", "k_mesh_angle_defect_bwd", "k_mesh_self_intersect", "k_p2m_sign",
-                                            "k_mesh_voxelize"};
+                                            "k_mesh_voxelize",
+                                            "k_mesh_raycast", "k_mesh_raycast_bwd_record", "k_mesh_raycast_bwd_vertex"};
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1592,6 +1594,42 @@ int icn_mesh_voxelize(const float* vertices, const int32_t* faces, int B, int V,
             !std::isfinite(origin_x) || !std::isfinite(origin_y) || !std::isfinite(origin_z) || !std::isfinite(spacing) || !(spacing > 0.0))
             throw std::invalid_argument("icn_mesh_voxelize: bad sizes");
         icn::launch_mesh_voxelize(vertices, faces, B, V, F, origin_x, origin_y, origin_z, spacing, n0, n1, n2, occupancy, s);
+    });
+}
+
+// ---- ray casting (include/icn_raycast.h): the sizes of the measure entries, and a ray count whose three values per ray fit an int ------
+namespace {
+bool raycast_rays_ok(int B, int R, int V) { return mesh_sizes_ok(B, R, V, 1) && R <= 0x7fffffff / 3; }
+}  // namespace
+
+int icn_mesh_raycast(const float* origins, const float* directions, const float* vertices, const int32_t* faces, int B, int R, int V, int F,
+                     float* depth, int32_t* face, int32_t* count, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!origins || !directions || !vertices || !faces || !depth || !face || !count)
+            throw std::invalid_argument("icn_mesh_raycast: null pointer");
+        check_measure_sizes("icn_mesh_raycast", B, V, F);
+        if (!raycast_rays_ok(B, R, V)) throw std::invalid_argument("icn_mesh_raycast: bad sizes");
+        icn::launch_mesh_raycast(origins, directions, vertices, faces, B, R, V, F, depth, face, count, s);
+    });
+}
+
+size_t icn_mesh_raycast_bwd_workspace_bytes(int B, int R, int V) {
+    return raycast_rays_ok(B, R, V) ? icn::vertex_records_bytes((size_t)B * R) : 0;
+}
+
+int icn_mesh_raycast_bwd(const float* origins, const float* directions, const float* vertices, const int32_t* faces, const int32_t* face,
+                         const float* ddepth, int B, int R, int V, int F, float* dorigins, float* ddirections, float* dvertices, void* ws,
+                         size_t ws_bytes, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return guarded([&] {                                             // (not `launched`: the early way out touches no device)
+        if (!origins || !directions || !vertices || !faces || !face || !ddepth) throw std::invalid_argument("icn_mesh_raycast_bwd: null pointer");
+        check_measure_sizes("icn_mesh_raycast_bwd", B, V, F);
+        if (!raycast_rays_ok(B, R, V)) throw std::invalid_argument("icn_mesh_raycast_bwd: bad sizes");
+        if (!dorigins && !ddirections && !dvertices) return;         // no gradient asked for
+        if (dvertices) check_workspace("icn_mesh_raycast_bwd", ws, ws_bytes, icn::vertex_records_bytes((size_t)B * R));
+        icn::launch_mesh_raycast_bwd(origins, directions, vertices, faces, face, ddepth, B, R, V, F, dorigins, ddirections, dvertices, ws, s);
+        ICN_HIP(hipGetLastError());
     });
 }
 

@@ -305,6 +305,15 @@ constexpr int VOXEL_MAX_DEPTH = 512;
 void launch_mesh_voxelize(const float* vts, const int32_t* faces, int B, int V, int F, double ox, double oy, double oz, double h, int n0,
                           int n1, int n2, uint8_t* occ, hipStream_t s);
 
+// ray casting (icn_raycast.hip; include/icn_raycast.h): one thread per (mesh, ray) against the faces of its mesh through LDS tiles,
+// double arithmetic: first hit (depth, face) and crossing count per ray.  One launch on s, no workspace.
+void launch_mesh_raycast(const float* org, const float* dir, const float* vts, const int32_t* faces, int B, int R, int V, int F, float* depth,
+                         int32_t* face, int32_t* count, hipStream_t s);
+// its backward at the forward's face choice: dorg / ddir (B, R, 3) and / or dvts (B, V, 3), each may be null (not all three); ws (only
+// read when dvts is wanted): vertex_records_bytes(B * R) bytes, 16-byte aligned.  One launch, then launch_vertex_scatter for dvts.
+void launch_mesh_raycast_bwd(const float* org, const float* dir, const float* vts, const int32_t* faces, const int32_t* face,
+                             const float* ddepth, int B, int R, int V, int F, float* dorg, float* ddir, float* dvts, void* ws, hipStream_t s);
+
 // developer routing flags (ICN_DEBUG / icn_set_debug_flags): 16 = convs on k_gather_gemm, 32 = wgrads on k_wgrad,
 // 128 = no stream-K, 256 = fault injection: every stream-K finisher reports its partners lost (tests of the failure path),
 // 512 = masked launches walk tiles b, b + G, ... instead of the balanced tile lists, 1024 = the sparse passes of the decoder-block
@@ -315,7 +324,7 @@ int debug_flags();
 int set_debug_flags(int flags);
 
 // ---- optional per-launch HIP-event timing of the MFMA kernels (bench.py's live roofline measurement) and of the
-// point-to-mesh, surface-sampling, normal-agreement, mesh-measure, mesh-curvature, angle-defect, self-intersection, distance-sign and voxelisation kernels ----------
+// point-to-mesh, surface-sampling, normal-agreement, mesh-measure, mesh-curvature, angle-defect, self-intersection, distance-sign, voxelisation and ray-casting kernels ----------
 enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA_64x64, PROF_GG_128x128, PROF_GG_128x64,
                 PROF_GG_64x128, PROF_GG_64x64, PROF_WGD_128x128, PROF_WGD_128x64, PROF_WGD_64x128, PROF_WGD_64x64, PROF_WG_128x128,
                 PROF_WG_128x64, PROF_WG_64x128, PROF_WG_64x64,
@@ -338,6 +347,7 @@ enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA
                 PROF_MESH_SELF_INTERSECT,                                                           // self-intersection count
                 PROF_P2M_SIGN,                                                                      // sign of the point-to-mesh distance
                 PROF_MESH_VOXELIZE,                                                                 // solid voxelisation by ray parity
+                PROF_MESH_RAYCAST, PROF_MESH_RAYCAST_BWD_RECORD, PROF_MESH_RAYCAST_BWD_VERTEX,      // ray casting and its backward
                 PROF_KINDS };
 extern const char* const PROF_NAMES[PROF_KINDS];
 void prof_mark_begin(int kind, double flops, hipStream_t s);   // no-ops unless profiling is on

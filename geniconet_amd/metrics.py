@@ -72,6 +72,14 @@ on an edge or a vertex; n0 parity bits per column and one prefix XOR, no atomics
 contains visits each (cell, face) pair, it needs no adjacency table, and it is right for any closed mesh whatever its winding: the
 occupancy grid that the reference's users otherwise take from kaolin.  Bools, no gradient; the HIP path reproduces the float64
 formulation byte for byte.
+
+ray_cast, contains_by_parity, depth_map and silhouette_iou (below) answer the general query: where a given ray first meets a mesh,
+on which face, and how many faces it crosses (icn_mesh_raycast, include/icn_raycast.h: one thread per ray against the faces of its
+mesh through LDS tiles, the same symbolic perturbation in double, so that exactly one of the two faces of an edge claims a ray
+through it; an fp32 filter proved to change nothing in front).  The parity of the count is an inside test from any direction that
+needs no consistent winding; the depth is differentiable in vertices, origins and directions (icn_mesh_raycast_bwd: one record per
+ray, then the vertex scatter); depth_map renders orthographic depth images and silhouettes, and silhouette_iou is the 2-D mask IoU
+of one mesh pair over seven views, to stand beside volumetric_iou.  The HIP path reproduces the float64 formulation bit for bit.
 """
 import torch
 
@@ -1470,6 +1478,377 @@ def volumetric_iou(outvertices, refvertices, faces, resolution=32, search='brute
         inside = contains(centres.expand(2, -1, -1).contiguous(), both, faces, search=search)
     n_and, n_or = torch.stack([(inside[0] & inside[1]).sum(), (inside[0] | inside[1]).sum()]).tolist()
     return n_and / n_or if n_or else 0.0
+
+
+# ---- ray casting ------------------------------------------------------------------------------------------------------------------------
+_RAY_CAST_CHUNK = 1 << 18          # (mesh, ray, face) triples the torch formulation holds at once: about 2 MiB per temporary
+
+
+def _ray_edge(swapped, pu, pw, d):
+    """(s, tau) of the directed edge u -> w of include/icn_raycast.h: pu, pw (..., 3) the ends less the origin, d (..., 3) the
+    direction, `swapped` where id_u < id_w does not hold.  Every product and sum is a torch operation of its own."""
+    a, b = torch.where(swapped[..., None], pw, pu), torch.where(swapped[..., None], pu, pw)
+    ax, ay, az = a.unbind(-1)
+    bx, by, bz = b.unbind(-1)
+    nx, ny, nz = ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx
+    s = (d[..., 0] * nx + d[..., 1] * ny) + d[..., 2] * nz
+    tau = torch.sign(s)
+    for n in (nx, ny, nz):
+        tau = torch.where(tau == 0, torch.sign(n), tau)
+    return torch.where(swapped, -s, s), torch.where(swapped, -tau, tau)
+
+
+def _ray_parameter(ids, tri, o, d):
+    """(t, covers) of rays against faces by the definition: ids (..., 3) integer, tri (..., 3 corners, 3) float64, o and d (..., 3)
+    float64, all broadcastable."""
+    p = tri - o[..., None, :]
+    s, positive, negative = [], True, True
+    for e in range(3):                                                                    # the edge opposite vertex e: u -> w
+        u, w = (e + 1) % 3, (e + 2) % 3
+        value, tau = _ray_edge(~(ids[..., u] < ids[..., w]), p[..., u, :], p[..., w, :], d)
+        s.append(value)
+        positive, negative = (tau > 0) & positive, (tau < 0) & negative
+    c = [(p[..., k, 0] * d[..., 0] + p[..., k, 1] * d[..., 1]) + p[..., k, 2] * d[..., 2] for k in range(3)]
+    dd = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    return ((s[0] * c[0] + s[1] * c[1]) + s[2] * c[2]) / (((s[0] + s[1]) + s[2]) * dd), positive | negative
+
+
+def _torch_ray_cast(origins, directions, vertices, faces, chunk=_RAY_CAST_CHUNK):
+    """The definition of ray_cast in torch: float64 on the values as stored, every product and sum an operation of its own, in the
+    order of include/icn_raycast.h -> (depth (B, R) in the vertices' dtype, face int64, count int32).  Chunked over the faces so that
+    one intermediate holds about `chunk` (mesh, ray, face) triples; ids are clamped before they index anything and non-finite values
+    meet only masked arithmetic.  Differentiable in vertices, origins and directions by evaluating t once more on the chosen face."""
+    B, V = vertices.shape[0], vertices.shape[1]
+    R, dev = origins.shape[1], vertices.device
+    ids_all = faces.long()
+    F = ids_all.shape[0]
+    with torch.no_grad():
+        v, o, d = vertices.detach().double(), origins.detach().double(), directions.detach().double()
+        live = torch.isfinite(o).all(-1) & torch.isfinite(d).all(-1) & (d != 0).any(-1)                                  # (B, R)
+        o, d = (torch.where(live[..., None], x, torch.zeros_like(x))[:, :, None] for x in (o, d))                        # (B, R, 1, 3)
+        best = torch.full((B, R), float('inf'), dtype=torch.float64, device=dev)
+        face = torch.full((B, R), -1, dtype=torch.int64, device=dev)
+        count = torch.zeros(B, R, dtype=torch.int32, device=dev)
+        step = max(1, chunk // (B * R))
+        for lo in range(0, F, step):
+            ids = ids_all[lo:lo + step]                                                                                   # (c, 3)
+            tri = v[:, ids.clamp(0, V - 1)]                                                                               # (B, c, 3, 3)
+            tested = ((ids >= 0) & (ids < V)).all(-1)[None] & torch.isfinite(tri).all(-1).all(-1)                         # (B, c)
+            tri = torch.where(tested[..., None, None], tri, torch.zeros_like(tri))
+            t, covers = _ray_parameter(ids, tri[:, None], o, d)                                                           # (B, R, c)
+            hit = covers & tested[:, None] & live[..., None] & torch.isfinite(t) & (t > 0)
+            count += hit.sum(-1, dtype=torch.int32)
+            t = torch.where(hit, t, torch.full_like(t, float('inf')))
+            nearest = t.amin(-1)                                                                                          # (B, R)
+            index = torch.arange(lo, lo + ids.shape[0], device=dev).expand_as(t)
+            first = torch.where(hit & (t == nearest[..., None]), index, torch.full_like(index, F)).amin(-1)              # the lowest index
+            take = (first < F) & (nearest < best)                                                                         # earlier chunks win ties
+            best, face = torch.where(take, nearest, best), torch.where(take, first, face)
+    found = face >= 0
+    if not (torch.is_grad_enabled() and (vertices.requires_grad or origins.requires_grad or directions.requires_grad)):
+        return torch.where(found, best, torch.full_like(best, float('inf'))).to(vertices.dtype), face, count
+    # once more on the chosen face, with autograd: the same operations on the same values, so the same t; rays without a hit run on
+    # harmless constants and are masked out on either side, so that neither they nor their gradients can be NaN
+    ids = ids_all[face.clamp(0)]                                                                                          # (B, R, 3)
+    tri = torch.gather(vertices.double(), 1, ids.reshape(B, R * 3, 1).expand(-1, -1, 3)).reshape(B, R, 3, 3)
+    tri = torch.where(found[..., None, None], tri, torch.eye(3, dtype=torch.float64, device=dev))
+    o = torch.where(found[..., None], origins.double(), torch.zeros(3, dtype=torch.float64, device=dev))
+    d = torch.where(found[..., None], directions.double(), torch.ones(3, dtype=torch.float64, device=dev))
+    t, _ = _ray_parameter(ids, tri, o, d)
+    return torch.where(found, t, torch.full_like(t, float('inf'))).to(vertices.dtype), face, count
+
+
+def _hip_ray_cast(org, dirs, vts, f32):
+    """icn_mesh_raycast on contiguous fp32 ROCm tensors and an int32 face table -> (depth fp32, face int32, count int32)."""
+    B, R = org.shape[0], org.shape[1]
+    V, F = vts.shape[1], f32.shape[0]
+    depth = torch.empty(B, R, dtype=torch.float32, device=vts.device)
+    face = torch.empty(B, R, dtype=torch.int32, device=vts.device)
+    count = torch.empty(B, R, dtype=torch.int32, device=vts.device)
+    _launch('icn_mesh_raycast', _per_mesh(org), _per_mesh(dirs), _per_mesh(vts), f32, _NB, R, V, F, _per_mesh(depth), _per_mesh(face),
+            _per_mesh(count))
+    return depth, face, count
+
+
+class _RayCastFn(torch.autograd.Function):
+    """ray_cast on the HIP path with a gradient (icn_mesh_raycast / icn_mesh_raycast_bwd in include/icn_raycast.h): the gradient of the
+    depth at the forward's face choice, G = ddepth n / (n . d), w_k G to the face's vertices, -G to the origin, -t G to the direction;
+    the vertex gradient is summed in a fixed order (bit-identical run to run).  Only the gradients autograd asks for are computed."""
+
+    @staticmethod
+    def forward(ctx, origins, directions, vertices, f32):
+        org, dirs, vts = origins.contiguous(), directions.contiguous(), vertices.contiguous()
+        depth, face, count = _hip_ray_cast(org, dirs, vts, f32)
+        ctx.save_for_backward(org, dirs, vts, f32, face)
+        face64 = face.long()
+        ctx.mark_non_differentiable(face64, count)
+        return depth, face64, count
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, ddepth, _gface, _gcount):
+        org, dirs, vts, f32, face = ctx.saved_tensors
+        R, V, F = org.shape[1], vts.shape[1], f32.shape[0]
+        dorg = torch.empty_like(org) if ctx.needs_input_grad[0] else None
+        ddir = torch.empty_like(dirs) if ctx.needs_input_grad[1] else None
+        dvts = torch.empty_like(vts) if ctx.needs_input_grad[2] else None
+        args = (_per_mesh(org), _per_mesh(dirs), _per_mesh(vts), f32, _per_mesh(face), _per_mesh(_upstream(ddepth)), _NB, R, V, F,
+                _per_mesh(dorg), _per_mesh(ddir), _per_mesh(dvts))
+        if dvts is not None:                                                              # only the vertex gradient needs scratch
+            _launch('icn_mesh_raycast_bwd', *args, workspace=('icn_mesh_raycast_bwd_workspace_bytes', R, V))
+        else:
+            _launch('icn_mesh_raycast_bwd', *args, None, 0)
+        return dorg, ddir, dvts, None
+
+
+def _ray_cast_unchecked(origins, directions, vertices, f32):
+    """ray_cast without its argument checks and without a host synchronisation, for callers that validated once: origins and
+    directions (B, R, 3) of the vertices' dtype and device, f32 an int32 (F, 3) tensor there, F >= 1.  A vertex id out of range or a
+    non-finite vertex is safe on either path: that face is not tested."""
+    if _on_hip_path(vertices) and origins.dtype == torch.float32 and directions.dtype == torch.float32:
+        if torch.is_grad_enabled() and (origins.requires_grad or directions.requires_grad or vertices.requires_grad):
+            return _RayCastFn.apply(origins, directions, vertices, f32)
+        depth, face, count = _hip_ray_cast(origins.detach().contiguous(), directions.detach().contiguous(), vertices.detach().contiguous(), f32)
+        return depth, face.long(), count
+    return _torch_ray_cast(origins, directions, vertices, f32)
+
+
+def _check_ray_mesh(who, vertices, faces):
+    """The shape checks of a mesh batch for ray_cast and its callers -> the int32 face table on the vertices' device.  ValueError."""
+    if vertices.dim() != 3 or vertices.shape[-1] != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1 or not vertices.is_floating_point():
+        raise ValueError('%s: expected floating-point vertices (B, V, 3), got %s' % (who, tuple(vertices.shape)))
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1 or faces.is_floating_point() or faces.dtype == torch.bool:
+        raise ValueError('%s: expected integer faces (F, 3) with F >= 1, got %s' % (who, tuple(faces.shape)))
+    if 3 * faces.shape[0] > 0x7fffffff:
+        raise ValueError('%s: %d faces: 3 F must fit an int32' % (who, faces.shape[0]))
+    return faces.to(device=vertices.device, dtype=torch.int32).contiguous()
+
+
+def _check_face_ids(who, f32, V):
+    """IndexError unless the ids of the face table lie in [0, V): one read-back."""
+    lo, hi = torch.stack(f32.aminmax()).tolist()
+    if lo < 0 or hi >= V:
+        raise IndexError('%s: faces index [%d, %d] but there are %d vertices' % (who, lo, hi, V))
+
+
+def _check_ray_arguments(who, rays, vertices, faces, names):
+    """The shape checks of ray_cast and its callers -> the rays as (B, R, 3) tensors of the vertices' dtype and device (rays (R, 3)
+    are shared by the batch), the int32 face table and V.  ValueError."""
+    f32, B = _check_ray_mesh(who, vertices, faces), vertices.shape[0]
+    out = []
+    for name, x in zip(names, rays):
+        if not torch.is_tensor(x) or not x.is_floating_point() or x.dim() not in (2, 3) or x.shape[-1] != 3 or x.shape[-2] < 1 or \
+                (x.dim() == 3 and x.shape[0] != B):
+            raise ValueError('%s: expected floating-point %s (R, 3) or (%d, R, 3) with R >= 1, got %s'
+                             % (who, name, B, tuple(x.shape) if torch.is_tensor(x) else type(x).__name__))
+        x = x.to(device=vertices.device, dtype=vertices.dtype)
+        out.append(x if x.dim() == 3 else x[None].expand(B, -1, -1))
+    if len({x.shape[1] for x in out}) != 1:
+        raise ValueError('%s: %s differ in their ray counts: %s' % (who, ' and '.join(names), [tuple(x.shape) for x in out]))
+    if 3 * out[0].shape[1] > 0x7fffffff:
+        raise ValueError('%s: %d rays: 3 R must fit an int32' % (who, out[0].shape[1]))
+    return out, f32, vertices.shape[1]
+
+
+def ray_cast(origins, directions, vertices, faces):
+    """(depth (B, R), face (B, R) int64, count (B, R) int32): where each ray origins + t directions, t > 0, first meets the triangle
+    mesh vertices (B, V, 3), faces (F, 3) integer and shared by the batch, which face that is (-1: none) and how many faces the ray
+    crosses.  origins and directions are (B, R, 3), or (R, 3) shared by the batch; a direction need not be a unit vector and depth
+    is in units of its length, +inf for a miss.  The query under depth maps and silhouettes (depth_map, silhouette_iou), visibility
+    tests and an inside test from any direction (contains_by_parity).  depth is differentiable in vertices, origins and directions
+    at the face it chose; face and count never carry a gradient.
+
+    One definition for the HIP kernel (include/icn_raycast.h), the torch formulation and the tests.  All arithmetic is float64 on the
+    values as stored, every product and sum rounded on its own, in exactly the order written:
+        a ray is LIVE iff its six values are finite and d != (0, 0, 0); a ray that is not answers a miss (+inf, -1, 0)
+        a face is TESTED iff its ids lie in [0, V) and its nine coordinates are finite; p_k = v_k - o
+        the value of a directed edge u -> w, on (a, b) = (p_u, p_w) if id_u < id_w, else (p_w, p_u):
+            N = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x);  s = (d.x N.x + d.y N.y) + d.z N.z;
+            tau = sign(s), if 0 sign(N.x), if still 0 sign(N.y), if still 0 sign(N.z) (the symbolic perturbation
+            d + (eps, eps^2, eps^3)), both negated if the ends were swapped: the two faces of an edge evaluate one expression and get
+            opposite values; a face with a repeated id gets tau = 0 on that edge
+        the face COVERS the ray iff tau > 0 for its three edges or tau < 0 for all three
+        its parameter, from the raw values s0, s1, s2 of the edges opposite vertices 0, 1, 2:
+            c_k = (p_k.x d.x + p_k.y d.y) + p_k.z d.z,  S = (s0 + s1) + s2,  dd = (d.x d.x + d.y d.y) + d.z d.z,
+            t = ((s0 c0 + s1 c1) + s2 c2) / (S dd)
+        a HIT is a covering face whose t is finite and > 0
+        count = the number of hits; face = the hit of smallest t, the lowest face index among equal t; depth = that t rounded once to
+        the vertices' dtype.  A t beyond that dtype rounds to +inf while face >= 0: the face is what tells a hit.
+    So on a closed mesh the parity of count is the inside test of the origin whatever the winding of the faces (where contains needs a
+    consistently wound mesh), a mesh that passes through itself gets the XOR, an origin exactly on the surface does not count that
+    surface, and a face with coincident vertices, a non-finite vertex or (in the unchecked form) an id out of range is never hit.  A
+    NaN never comes out.
+    The gradient, at the chosen face: with n = (v1 - v0) x (v2 - v0), G = ddepth n / (n . d), d/dv_k = (s_k / S) G, d/do = -G,
+    d/dd = -t G; nothing where there is no hit.
+    ROCm fp32 tensors run on icn_mesh_raycast: one thread per (mesh, ray), the faces staged through LDS, an fp32 filter that skips a
+    face only where it is proved not to cover the ray (csrc/icn_raycast.hip) in front of the double arithmetic, no atomics,
+    bit-identical run to run and equal to the float64 formulation bit for bit; the backward is
+    icn_mesh_raycast_bwd, one record per ray and a vertex scatter in a fixed order.  ICN_NO_HIP_LOSS=1, CPU tensors and other dtypes
+    take the definition in torch (_torch_ray_cast), chunked over the faces, with autograd.
+    Shapes are checked (ValueError) and the face ids against V with one read-back (IndexError)."""
+    who = 'ray_cast'
+    (origins, directions), f32, V = _check_ray_arguments(who, (origins, directions), vertices, faces, ('origins', 'directions'))
+    _check_face_ids(who, f32, V)                                                          # the one read-back
+    return _ray_cast_unchecked(origins, directions, vertices, f32)
+
+
+def contains_by_parity(points, vertices, faces, direction=(1.0, 0.0, 0.0)):
+    """bool (B, P): whether each point of points (B, P, 3) or (P, 3) lies inside its closed mesh, by the parity of ray_cast's count
+    along `direction` (three numbers, not all zero; one ray per point).  Right whatever the winding of the faces, where `contains`
+    needs a consistent one, and needs no table; a point exactly on the surface does not count that surface, and a NaN point is not
+    inside.  On a mesh that is NOT CLOSED a ray through the hole is wrong, so this function checks, with the read-back that checks the
+    face ids, that every undirected edge belongs to an even number of faces (ValueError, as voxelize).  Never requires grad."""
+    who = 'contains_by_parity'
+    try:
+        direction = tuple(float(x) for x in direction)
+    except (TypeError, ValueError):
+        raise ValueError('%s: direction must be three numbers' % who)
+    if len(direction) != 3 or not all(x == x and abs(x) != float('inf') for x in direction) or not any(direction):
+        raise ValueError('%s: direction must be three finite numbers, not all zero, got %r' % (who, direction))
+    (points,), f32, V = _check_ray_arguments(who, (points,), vertices, faces, ('points',))
+    lo, hi, n_odd, a, b = _odd_edges(f32, V).tolist()                                     # the one read-back
+    if lo < 0 or hi >= V:
+        raise IndexError('%s: faces index [%d, %d] but there are %d vertices' % (who, lo, hi, V))
+    if n_odd:
+        raise ValueError('%s: the mesh is not closed: the edge (%d, %d) belongs to an odd number of faces (%d such edges); a ray '
+                         'through the hole would be wrong' % (who, a, b, n_odd))
+    with torch.no_grad():
+        d = torch.tensor(direction, dtype=torch.float64).to(device=points.device, dtype=points.dtype).expand_as(points)
+        return (_ray_cast_unchecked(points.detach(), d, vertices, f32)[2] & 1).bool()
+
+
+_AXES = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
+
+
+def _view_basis(view, who='depth_map'):
+    """(w, e1, e2) of an orthographic view as tuples of Python floats: w the unit view direction, e1 = normalize(w x a) with a the
+    coordinate axis of w's smallest |component| (the first on ties), e2 = w x e1.  ValueError unless view is three finite numbers
+    with a length."""
+    import math
+    try:
+        w = tuple(float(x) for x in view)
+    except (TypeError, ValueError):
+        raise ValueError('%s: a view must be three numbers, got %r' % (who, view))
+    length = math.sqrt(sum(x * x for x in w)) if len(w) == 3 else 0.0
+    if len(w) != 3 or not (length > 0 and length != float('inf')):
+        raise ValueError('%s: a view must be three finite numbers, not all zero, got %r' % (who, view))
+    w = tuple(x / length for x in w)
+    a = _AXES[min(range(3), key=lambda k: (abs(w[k]), k))]
+
+    def cross(p, q):
+        return (p[1] * q[2] - p[2] * q[1], p[2] * q[0] - p[0] * q[2], p[0] * q[1] - p[1] * q[0])
+    e1 = cross(w, a)
+    length = math.sqrt(sum(x * x for x in e1))
+    e1 = tuple(x / length for x in e1)
+    return w, e1, cross(w, e1)
+
+
+def _frame_of_box(who, lo, hi):
+    """(centre, rho) of a bounding box given as two lists of three Python floats: its midpoint and its half-diagonal, in float64 on the
+    host.  ValueError unless the box is finite and has an extent."""
+    import math
+    centre = tuple((lo[k] + hi[k]) / 2 for k in range(3))
+    rho = math.sqrt(sum((hi[k] - lo[k]) ** 2 for k in range(3))) / 2
+    if not all(c == c and abs(c) != float('inf') for c in centre + (rho,)) or rho <= 0:
+        raise ValueError('%s: the meshes have no finite bounding box of positive extent' % who)
+    return centre, rho
+
+
+def _joint_frame(vertices, who='depth_map'):
+    """(centre, rho) of a batch of meshes: the midpoint and the half-diagonal of their joint bounding box (one read-back)."""
+    v = vertices.detach()
+    lo, hi = torch.stack([v.amin((0, 1)).double(), v.amax((0, 1)).double()]).tolist()     # one read-back
+    return _frame_of_box(who, lo, hi)
+
+
+def _pixel_rays(view, resolution, frame, like):
+    """(origins (H W, 3), direction (3,)) of depth_map's pixels as tensors of like's dtype and device: evaluated in float64 on the
+    host's values, rounded once."""
+    w, e1, e2 = _view_basis(view)
+    (centre, rho), n = frame, int(resolution)
+    h = 2 * rho / n
+    at = (torch.arange(n, dtype=torch.float64) + 0.5) * h - rho                            # (i + 1/2) h - rho
+    base = torch.tensor(centre, dtype=torch.float64) - 2 * rho * torch.tensor(w, dtype=torch.float64)
+    origins = (base + at[:, None, None] * torch.tensor(e1, dtype=torch.float64)) + at[None, :, None] * torch.tensor(e2, dtype=torch.float64)
+    return origins.reshape(n * n, 3).to(device=like.device, dtype=like.dtype), torch.tensor(w, dtype=torch.float64).to(device=like.device, dtype=like.dtype)
+
+
+def _check_view_arguments(resolution, frame, who='depth_map'):
+    try:
+        whole = int(resolution) == resolution and int(resolution) >= 1
+    except (TypeError, ValueError):
+        whole = False
+    if not whole:
+        raise ValueError('%s: resolution must be a positive integer, got %r' % (who, resolution))
+    if frame is not None:
+        try:
+            centre, rho = frame
+            frame = tuple(float(c) for c in centre), float(rho)
+        except (TypeError, ValueError):
+            raise ValueError('%s: frame must be (centre of three numbers, rho), got %r' % (who, frame))
+        if len(frame[0]) != 3 or not all(c == c and abs(c) != float('inf') for c in frame[0] + (frame[1],)) or frame[1] <= 0:
+            raise ValueError('%s: frame must be a finite centre of three numbers and a finite rho > 0, got %r' % (who, frame))
+    return frame
+
+
+def depth_map(vertices, faces, view, resolution, frame=None):
+    """(depth (B, H, W), mask (B, H, W) bool), H = W = resolution: the orthographic depth image of every mesh of vertices (B, V, 3),
+    faces (F, 3), seen along `view` (three numbers; w is its unit vector).  The image plane is spanned by e1 = normalize(w x a), a the
+    coordinate axis of w's smallest |component| (the first on ties), and e2 = w x e1.  frame = (centre, rho) places it: a square of
+    side 2 rho about centre; the default is the midpoint and the half-diagonal of the joint bounding box of the batch (one read-back),
+    which holds every mesh from every view.  Pixel (i, j) casts the ray of direction w from
+        centre + ((i + 1/2) h - rho) e1 + ((j + 1/2) h - rho) e2 - 2 rho w,    h = 2 rho / resolution
+    -- evaluated in float64 on the host's values and rounded once to the vertices' dtype -- through ray_cast: depth is its depth (the
+    distance from that plane, 2 rho in front of centre; +inf where nothing is hit), mask = face >= 0, the silhouette.  depth is
+    differentiable in the vertices.  Checks as ray_cast, with its read-back."""
+    frame = _check_view_arguments(resolution, frame)
+    f32 = _check_ray_mesh('depth_map', vertices, faces)
+    _check_face_ids('depth_map', f32, vertices.shape[1])
+    return _depth_map_unchecked(vertices, f32, view, int(resolution), frame if frame is not None else _joint_frame(vertices))
+
+
+def _depth_map_unchecked(vertices, f32, view, resolution, frame):
+    """depth_map after its checks: no read-back of its own."""
+    B = vertices.shape[0]
+    origins, w = _pixel_rays(view, resolution, frame, vertices)
+    depth, face, _ = _ray_cast_unchecked(origins[None].expand(B, -1, -1), w.expand(B, origins.shape[0], 3), vertices, f32)
+    return depth.reshape(B, resolution, resolution), (face >= 0).reshape(B, resolution, resolution)
+
+
+SILHOUETTE_VIEWS = _AXES + ((1.0, 1.0, 1.0), (1.0, 1.0, -1.0), (1.0, -1.0, 1.0), (1.0, -1.0, -1.0))
+
+
+def silhouette_iou(outvertices, refvertices, faces, resolution=64, views=None):
+    """The mean over `views` of |A and B| / |A or B| of the silhouettes of two meshes ((V, 3) tensors sharing `faces`), as a Python
+    float: the standard image-space figure of a reconstruction, to stand beside volumetric_iou, and the one that can be compared with
+    a photograph.  Each view is an orthographic depth_map of both meshes as one batch of two on a shared frame, the midpoint and
+    half-diagonal of their joint bounding box (one read-back for the frame and the face ids); the masks are counted on the device and
+    all counts come back in one read-back.  A view in which neither mesh is seen counts 0.  The default views are the three coordinate
+    axes and the four body diagonals; the opposite directions would give the mirror images and the same figures.  The meshes need not
+    be closed and their winding plays no part."""
+    who = 'silhouette_iou'
+    if outvertices.dim() != 2 or refvertices.dim() != 2 or outvertices.shape != refvertices.shape or outvertices.shape[-1] != 3:
+        raise ValueError('%s: expected two (V, 3) vertex tensors of one shape, got %s and %s'
+                         % (who, tuple(outvertices.shape), tuple(refvertices.shape)))
+    _check_view_arguments(resolution, None, who)
+    views = SILHOUETTE_VIEWS if views is None else tuple(views)
+    if not views:
+        raise ValueError('%s: no views' % who)
+    for view in views:
+        _view_basis(view, who)                                                            # raises on a bad view before any work
+    both = torch.stack([outvertices, refvertices.to(device=outvertices.device, dtype=outvertices.dtype)]).detach()
+    f32, V = _check_ray_mesh(who, both, faces), both.shape[1]
+    box = torch.cat([torch.stack(f32.aminmax()).double(), both.amin((0, 1)).double(), both.amax((0, 1)).double()]).tolist()
+    if box[0] < 0 or box[1] >= V:                                                         # (one read-back: the face ids and the box)
+        raise IndexError('%s: faces index [%d, %d] but there are %d vertices' % (who, box[0], box[1], V))
+    frame = _frame_of_box(who, box[2:5], box[5:8])
+    counts = []
+    with torch.no_grad():
+        for view in views:
+            _, mask = _depth_map_unchecked(both, f32, view, int(resolution), frame)
+            counts += [(mask[0] & mask[1]).sum(), (mask[0] | mask[1]).sum()]
+        counts = torch.stack(counts).tolist()                                             # one read-back
+    return sum(a / o if o else 0.0 for a, o in zip(counts[::2], counts[1::2])) / len(views)
 
 
 def output2vertices(subdivisions, output):

@@ -1,0 +1,788 @@
+"""Ray casting against batched meshes and what is built on it (metrics.ray_cast, contains_by_parity, depth_map, silhouette_iou;
+icn_mesh_raycast, icn_mesh_raycast_bwd).
+
+The definition (metrics.ray_cast, include/icn_raycast.h) is written a third time here, as plain Python loops over float64 values of the
+fp32 inputs (`reference`), and two INDEPENDENT TRUTHS stand beside it: a float64 Moeller-Trumbore for the first hit and the generalised
+winding number of tests/test_signed_distance.py for the parity.  The three statements of the definition are compared exactly -- bits
+of the depth, every face, every count -- and on the axis-aligned cube, where rays through vertices, along edges and in face planes make
+every tie fire, no ray is set aside.  On the GPU the kernel must equal the float64 formulation bit for bit over meshes, ray counts and
+ray families chosen at the edges of its tiles (256 rays a workgroup, 256 staged faces), and the backward must lie within a bound
+derived from its roundings of float64 autograd of that formulation, element by element."""
+import functools
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from geniconet_amd import _lib, metrics
+
+from error_bounds import rho
+from test_signed_distance import _profiled, winding
+from test_voxelize import GPU_MESHES, _broken_cube, _centres, _gpu_mesh, _named, _sphere
+
+INF = float('inf')
+NAN = float('nan')
+
+
+# ---- the reference: the definition in plain loops -----------------------------------------------------------------------------------
+def _sign(x):
+    return (x > 0) - (x < 0)
+
+
+def _edge(iu, iw, pu, pw, d):
+    """(s, tau) of the directed edge u -> w for the direction d."""
+    swapped = not iu < iw
+    a, b = (pw, pu) if swapped else (pu, pw)
+    n = (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+    s = (d[0] * n[0] + d[1] * n[1]) + d[2] * n[2]
+    tau = _sign(s) or _sign(n[0]) or _sign(n[1]) or _sign(n[2])
+    return (-s, -tau) if swapped else (s, tau)
+
+
+def reference(origins, directions, vertices, faces):
+    """(depth fp32 (R,), face (R,), count (R,)) of one mesh: the definition on Python floats (IEEE doubles, no fused multiply-add) of the
+    fp32 inputs."""
+    def widened(x):
+        return np.asarray(x).astype(np.float32).astype(np.float64).tolist()
+    o_all, d_all, v = widened(origins), widened(directions), widened(vertices)
+    V = len(v)
+    usable = [(k, ids, [v[i] for i in ids]) for k, ids in enumerate(np.asarray(faces).astype(np.int64).tolist())
+              if all(0 <= i < V for i in ids) and all(math.isfinite(c) for i in ids for c in v[i])]
+    depth, face, count = [], [], []
+    for o, d in zip(o_all, d_all):
+        best, best_face, hits = INF, -1, 0
+        if all(math.isfinite(x) for x in o + d) and any(x != 0 for x in d):
+            dd = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
+            for k, (i0, i1, i2), corners in usable:
+                p0, p1, p2 = ([c[a] - o[a] for a in range(3)] for c in corners)
+                (s0, t0), (s1, t1), (s2, t2) = _edge(i1, i2, p1, p2, d), _edge(i2, i0, p2, p0, d), _edge(i0, i1, p0, p1, d)
+                if not (t0 > 0 and t1 > 0 and t2 > 0) and not (t0 < 0 and t1 < 0 and t2 < 0):
+                    continue
+                c0, c1, c2 = ((p[0] * d[0] + p[1] * d[1]) + p[2] * d[2] for p in (p0, p1, p2))
+                num, den = (s0 * c0 + s1 * c1) + s2 * c2, ((s0 + s1) + s2) * dd
+                if den == 0:                                                  # t is infinite or NaN: no hit
+                    continue
+                t = num / den
+                if math.isfinite(t) and t > 0:
+                    hits += 1
+                    if t < best:
+                        best, best_face = t, k
+        depth.append(best if best_face >= 0 else INF)
+        face.append(best_face)
+        count.append(hits)
+    with np.errstate(over='ignore'):
+        return np.asarray(depth).astype(np.float32), np.asarray(face), np.asarray(count)
+
+
+def _bits(depth):
+    return depth.contiguous().view(torch.int32)
+
+
+def _same(got, want, what=''):
+    """Bits of the depth, every face, every count."""
+    assert got[0].dtype == want[0].dtype == torch.float32 and got[1].dtype == torch.int64 and got[2].dtype == torch.int32, what
+    assert torch.equal(_bits(got[0].cpu()), _bits(want[0].cpu())), what
+    assert torch.equal(got[1].cpu(), want[1].cpu()), what
+    assert torch.equal(got[2].cpu(), want[2].cpu()), what
+
+
+# ---- rays -------------------------------------------------------------------------------------------------------------------------------
+def _box(v):
+    p = v[torch.isfinite(v).all(-1)]
+    return p.amin(0), p.amax(0)
+
+
+def _random_rays(v, count, seed, spread=1.5):
+    """Origins uniform in the mesh's box widened by `spread`, each aimed at a point drawn from the same box: hits and misses."""
+    g = torch.Generator().manual_seed(seed)
+    lo, hi = _box(v)
+    mid, half = (lo + hi) / 2, (hi - lo) / 2 * spread
+    o = mid + (2 * torch.rand(count, 3, generator=g) - 1) * half
+    aim = mid + (2 * torch.rand(count, 3, generator=g) - 1) * half
+    return o.float(), (aim - o).float()
+
+
+INVALID_RAYS = (((0.3, 0.4, -1.0), (0.0, 0.0, 0.0)), ((NAN, 0.4, -1.0), (0.0, 0.0, 1.0)), ((0.3, INF, -1.0), (0.0, 0.0, 1.0)),
+                ((0.3, 0.4, -INF), (0.0, 0.0, 1.0)), ((0.3, 0.4, -1.0), (0.0, NAN, 1.0)), ((0.3, 0.4, -1.0), (0.0, 0.0, INF)),
+                ((0.3, 0.4, -1.0), (-INF, 0.0, 1.0)), ((0.3, 0.4, -1.0), (-0.0, 0.0, -0.0)))
+
+
+def _with_invalid(o, d, every=7):
+    o, d = o.clone(), d.clone()
+    for n, k in enumerate(range(2, o.shape[0], every)):
+        o[k], d[k] = (torch.tensor(x) for x in INVALID_RAYS[n % len(INVALID_RAYS)])
+    return o, d
+
+
+# ---- CPU 1: the three statements of the definition -------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', ('tetrahedron', 'cube', 'spike', 'noisy I1'))
+def test_torch_formulation_equals_the_definition_in_plain_loops(name):
+    v, f = _sphere(1, 0.1, seed=1) if name == 'noisy I1' else _named(name)
+    o, d = _with_invalid(*_random_rays(v, 90, seed=3))
+    lo, hi = _box(v)
+    aimed = torch.cat([v, (v[f[:, 0]] + v[f[:, 1]]) / 2, v[f].mean(1)])[:60] - (hi + 0.75)     # from one origin at its vertices, edges, faces
+    o, d = torch.cat([o, (hi + 0.75).expand_as(aimed)]), torch.cat([d, aimed])
+    got = metrics._torch_ray_cast(o[None], d[None], v[None], f)
+    want = reference(o, d, v, f)
+    _same(got, tuple(torch.from_numpy(x)[None].to(y.dtype) for x, y in zip(want, got)), name)
+    assert (want[2] > 0).any() and (want[2] == 0).any() and (want[2] > 1).any()
+    assert not torch.isnan(got[0]).any()
+    _same(metrics.ray_cast(o, d, v[None], f), got)                            # the checked function, rays shared by the batch
+    _same(metrics._torch_ray_cast(o[None], d[None], v[None], f, chunk=1), got)                  # one face chunk or many: the same
+    _same(metrics._torch_ray_cast(o[None], d[None], v[None], f, chunk=o.shape[0] * 5), got)
+
+
+# ---- CPU 2: the axis-aligned cube, where the tie rule decides --------------------------------------------------------------------------
+CUBE_ORIGINS_INSIDE = ((0.5, 0.5, 0.5), (0.25, 0.5, 0.75), (0.125, 0.375, 0.625))
+CUBE_ORIGINS_OUTSIDE = ((-1.0, -1.0, -1.0), (2.0, 0.5, 0.5), (0.5, -0.75, 0.25), (-0.5, 1.5, 2.0))
+
+
+def _cube_targets():
+    """Every vertex, the midpoint of every edge of the triangulation (the 12 cube edges and the 6 face diagonals, whose midpoints are
+    the face centres), and the centroid of every triangle."""
+    v, f = _named('cube')
+    edges = {tuple(sorted((int(a), int(b)))) for tri in f.tolist() for a, b in zip(tri, tri[1:] + tri[:1])}
+    assert len(edges) == 18
+    mid = torch.stack([(v[a] + v[b]) / 2 for a, b in sorted(edges)])
+    centres = torch.tensor([[0.5, 0.5, 0.0], [0.5, 0.5, 1.0], [0.5, 0.0, 0.5], [0.5, 1.0, 0.5], [0.0, 0.5, 0.5], [1.0, 0.5, 0.5]])
+    assert all(any(torch.equal(c, m) for m in mid) for c in centres)          # the face centres are among the midpoints
+    return torch.cat([v, mid, v[f].mean(1)])
+
+
+@functools.lru_cache(maxsize=None)
+def _degenerate_cube_rays():
+    """(origins, directions, inside): rays aimed exactly at every target from origins inside and outside (all values dyadic, so the
+    differences are exact), away from them, and rays that run IN the planes of the faces from origins in those planes outside the cube."""
+    targets = _cube_targets()
+    o, d, inside = [], [], []
+    for origin, is_in in [(x, True) for x in CUBE_ORIGINS_INSIDE] + [(x, False) for x in CUBE_ORIGINS_OUTSIDE]:
+        for target in targets[:26].tolist():                                  # vertices and midpoints: dyadic
+            for sign in (1.0, -1.0):
+                o.append(origin), d.append([sign * (t - x) for t, x in zip(target, origin)]), inside.append(is_in)
+        for target in targets[26:].tolist():                                  # centroids: thirds, not exact; through face interiors
+            o.append(origin), d.append([t - x for t, x in zip(target, origin)]), inside.append(is_in)
+    for axis in range(3):                                                     # in the plane `axis` = 0 or 1, from outside, along and across
+        for level in (0.0, 1.0):
+            for start, along in (((-1.0, 0.25), (1.0, 0.0)), ((-1.0, 0.0), (1.0, 0.0)), ((-1.0, -1.0), (1.0, 1.0)), ((-1.0, 1.0), (1.0, 0.0)),
+                                 ((-0.5, -1.0), (0.5, 1.0)), ((2.0, 0.5), (-1.0, 0.0)), ((-1.0, 0.5), (1.0, 0.0)), ((-1.0, 2.0), (1.0, -1.0))):
+                origin, direction = list(start), list(along)
+                origin.insert(axis, level), direction.insert(axis, 0.0)
+                o.append(origin), d.append(direction), inside.append(False)
+    return torch.tensor(o), torch.tensor(d), torch.tensor(inside)
+
+
+def test_degenerate_rays_on_the_aligned_cube_have_the_parity_of_their_origin():
+    v, f = _named('cube')
+    o, d, inside = _degenerate_cube_rays()
+    depth, face, count = metrics.ray_cast(o, d, v[None], f)
+    odd = (count[0] & 1).bool()
+    print('%d rays, %d from inside; counts %s; %d with the wrong parity'
+          % (len(o), int(inside.sum()), sorted(set(count[0].tolist())), int((odd != inside).sum())))
+    assert len(o) >= 400
+    assert torch.equal(odd, inside)                                           # every ray, none set aside
+    assert torch.equal(face[0] >= 0, count[0] > 0) and torch.equal(torch.isfinite(depth[0]), count[0] > 0)
+    want = reference(o, d, v, f)
+    _same((depth, face, count), tuple(torch.from_numpy(x)[None].to(y.dtype) for x, y in zip(want, (depth, face, count))))
+
+
+def test_the_aligned_cube_under_relabelled_vertices_permuted_faces_and_flipped_windings():
+    v, f = _named('cube')
+    o, d, inside = _degenerate_cube_rays()
+    exact = torch.ones(len(o), dtype=torch.bool)
+    per_origin = 26 * 2 + 12
+    for k in range(7):
+        exact[k * per_origin + 52:(k + 1) * per_origin] = False              # aimed at centroids: thirds, the sums round
+    depth, _, count = metrics.ray_cast(o, d, v[None], f)
+    g = torch.Generator().manual_seed(6)
+    for trial in range(6):
+        label = torch.randperm(8, generator=g)                                # old id -> new id
+        vv = torch.empty_like(v)
+        vv[label] = v
+        ff = label[f][torch.randperm(12, generator=g)]
+        flip = torch.rand(12, generator=g) < (0.0, 0.5, 1.0)[trial % 3]        # none, a subset, all wound the other way
+        ff = torch.where(flip[:, None], ff.flip(1), ff)
+        depth2, _, count2 = metrics.ray_cast(o, d, vv[None], ff)
+        assert torch.equal(count2, count), trial
+        assert torch.equal(_bits(depth2[0][exact]), _bits(depth[0][exact])), trial
+        assert int((_bits(depth2).long() - _bits(depth).long()).abs().max()) <= 1    # the sums round in another order: one ulp of fp32
+
+
+# ---- CPU 3: truth by Moeller-Trumbore and by the winding number ------------------------------------------------------------------------
+def moeller_trumbore(o, d, v, f):
+    """Float64 Moeller-Trumbore of every ray against every face of one mesh -> (t, u, v) arrays (R, F); t = nan where the ray is
+    parallel to the face's plane."""
+    tri = np.asarray(v).astype(np.float32).astype(np.float64)[np.asarray(f)]
+    o, d = (np.asarray(x).astype(np.float32).astype(np.float64)[:, None, :] for x in (o, d))
+    e1, e2 = (tri[:, 1] - tri[:, 0])[None], (tri[:, 2] - tri[:, 0])[None]
+    h = np.cross(d, e2)
+    det = (e1 * h).sum(-1)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        s = o - tri[None, :, 0]
+        bu = (s * h).sum(-1) / det
+        q = np.cross(s, e1)
+        bv = (d * q).sum(-1) / det
+        t = (e2 * q).sum(-1) / det
+    t[det == 0] = np.nan
+    return t, bu, bv, np.abs(det) / (np.linalg.norm(np.cross(e1, e2), axis=-1) * np.linalg.norm(d, axis=-1))     # |cos| to the normal
+
+
+@pytest.mark.parametrize('r,sigma', ((1, 0.1), (2, 0.2), (3, 0.3)))
+def test_first_hit_and_count_against_moeller_trumbore_and_parity_against_the_winding_number(r, sigma):
+    """Rays may be set aside only where Moeller-Trumbore's own barycentrics lie within 1e-9 of an edge of a face in front of the origin,
+    at most 1 % of them.  Both sides intersect the ray with the plane of the same face in float64 with fewer than 32 roundings each, on
+    differences of size |p| <= |o| + |v|, so |dt| <= 64 u |p| / (|d| |cos|), u = 2^-53, |cos| the cosine between ray and face normal."""
+    v, f = _sphere(r, sigma, seed=r)
+    count_rays = 2000
+    o, d = _random_rays(v, count_rays, seed=10 + r, spread=1.2)
+    depth, face, count = metrics.ray_cast(o.double(), d.double(), v[None].double(), f)
+    depth, face, count = depth[0].numpy(), face[0].numpy(), count[0].numpy()
+    t, bu, bv, cosine = moeller_trumbore(o, d, v, f)
+    front = t > 0
+    inside = front & (bu >= 0) & (bv >= 0) & (bu + bv <= 1)
+    near = front & (np.minimum(np.minimum(bu, bv), 1 - bu - bv) > -1e-9) & (np.minimum(np.minimum(np.abs(bu), np.abs(bv)), np.abs(1 - bu - bv)) <= 1e-9)
+    aside = near.any(1)
+    first = np.where(inside, t, np.inf)
+    want_t, want_face = first.min(1), first.argmin(1)
+    keep = ~aside
+    hit = np.isfinite(want_t)
+    scale = (np.abs(o.numpy()).max(1) + np.abs(v.numpy()).max()) * math.sqrt(3)
+    bound = 64 * 2.0 ** -53 * scale / (np.linalg.norm(d.numpy().astype(np.float64), axis=1) * cosine[np.arange(count_rays), want_face])
+    delta = np.abs(depth[keep & hit] - want_t[keep & hit])
+    print('I%d sigma %.1f: %d rays, %d hit, %d set aside, %d differ in hit or miss, %d in count, largest |dt| %.3g (bound there %.3g)'
+          % (r, sigma, count_rays, int(hit.sum()), int(aside.sum()), int(((face >= 0) != hit)[keep].sum()),
+             int((count != inside.sum(1))[keep].sum()), delta.max(), bound[keep & hit][delta.argmax()]))
+    assert aside.sum() <= 0.01 * count_rays
+    assert hit.any() and not hit.all()
+    assert np.array_equal((face >= 0)[keep], hit[keep])
+    assert np.array_equal(count[keep], inside.sum(1)[keep])
+    assert (delta <= bound[keep & hit]).all()
+    assert np.array_equal(face[keep & hit], want_face[keep & hit])
+    # the parity of the count is the inside test of the origin: the winding number, at every origin
+    w = winding(o.numpy(), v.numpy(), f.numpy())
+    assert np.abs(w - 0.5).min() > 1e-6                                       # no origin on the surface: nothing is set aside
+    assert np.array_equal(count % 2 == 1, w > 0.5)
+    assert (w > 0.5).any() and not (w > 0.5).all()
+
+
+# ---- CPU 4: invalid and non-finite input -----------------------------------------------------------------------------------------------
+def test_invalid_rays_and_faces_answer_as_defined_and_no_nan_comes_out():
+    v, f, extra = _broken_cube()                                              # a NaN vertex, an id out of range, faces without area
+    plain_v, plain_f = _named('cube')
+    o, d = _random_rays(plain_v, 120, seed=4)
+    want = metrics._torch_ray_cast(o[None], d[None], plain_v[None], plain_f)
+    assert (want[2] > 0).any() and (want[2] == 0).any()
+    everything = torch.cat([extra, f, extra]).int()
+    got = metrics._ray_cast_unchecked(o[None], d[None], v[None], everything)
+    assert torch.equal(_bits(got[0]), _bits(want[0])) and torch.equal(got[2], want[2])
+    assert torch.equal(got[1], torch.where(want[1] >= 0, want[1] + len(extra), want[1]))
+    # a face of three positions on a line with distinct ids, both ways round: never hit, even by a ray along that line
+    v2 = torch.cat([plain_v, torch.tensor([[0.5, 0.5, 0.5], [0.25, 0.25, 0.25], [0.75, 0.75, 0.75]])])
+    line = torch.tensor([[8, 9, 10], [10, 9, 8]])
+    o2, d2 = torch.cat([o, torch.tensor([[-1.0, -1.0, -1.0]])]), torch.cat([d, torch.tensor([[1.0, 1.0, 1.0]])])
+    got = metrics.ray_cast(o2, d2, v2[None], torch.cat([line, plain_f]))
+    assert torch.equal(got[2][0, :-1], want[2][0]) and int(got[2][0, -1]) == 2 and not (got[1] == 0).any() and not (got[1] == 1).any()
+    # the invalid rays, among valid ones
+    o, d = _with_invalid(o, d, every=3)
+    dead = ~(torch.isfinite(o).all(-1) & torch.isfinite(d).all(-1) & (d != 0).any(-1))
+    assert int(dead.sum()) == 40
+    depth, face, count = metrics.ray_cast(o, d, plain_v[None], plain_f)
+    assert (depth[0][dead] == INF).all() and (face[0][dead] == -1).all() and (count[0][dead] == 0).all()
+    assert torch.equal(_bits(depth[0][~dead]), _bits(want[0][0][~dead])) and torch.equal(count[0][~dead], want[2][0][~dead])
+    assert not torch.isnan(depth).any()
+    # an origin exactly on the surface does not count that surface; a depth beyond fp32 is +inf while the face tells the hit
+    depth, face, count = metrics.ray_cast(torch.tensor([[0.25, 0.5, 0.0], [0.25, 0.5, 0.0], [0.25, 0.5, -1.0]]),
+                                          torch.tensor([[0.0, 0.0, 1.0], [0.0, 0.0, -1.0], [0.0, 0.0, 1e-39]]), plain_v[None], plain_f)
+    assert count[0].tolist() == [1, 0, 2] and depth[0].tolist() == [1.0, INF, INF] and face[0].tolist()[1] == -1 and face[0].tolist()[2] >= 0
+
+
+def test_a_face_whose_plane_holds_the_ray_can_be_a_hit_however_far_it_is():
+    """Why a test of the distance between ray and face alone may not stand in front of the definition.  Ray and face on the plane x = 3 y, whose products round: the exact
+    edge values are all 0, the computed ones are rounding noise, and where the three agree in sign the definition counts a hit -- of a
+    face whose bounding sphere the ray misses by more than half its radius.  The kernel's filter keeps such faces for the double path: it
+    skips a face only if the ray is also not within 2^-16 of its plane."""
+    o, d, v, f = _coplanar_cases()
+    depth, face, count = metrics._torch_ray_cast(o, d, v, f)
+    hit = count[:, 0] > 0
+    centre = v.double().mean(1)
+    m, u = centre - o[:, 0].double(), d[:, 0].double() / d[:, 0].double().norm(dim=1, keepdim=True)
+    distance = (m - (m * u).sum(1, keepdim=True) * u).norm(dim=1)
+    radius = (v.double() - centre[:, None]).norm(dim=2).amax(1)
+    print('%d of %d faces coplanar with their ray are hits; the nearest of them is %.1f radii from the ray'
+          % (int(hit.sum()), len(hit), float((distance / radius)[hit].min())))
+    assert hit.any() and (distance[hit] > 1.5 * radius[hit]).all()
+    k = int(hit.nonzero()[0])
+    want = reference(o[k], d[k], v[k], f)
+    assert want[2][0] == 1 and torch.equal(_bits(depth[k]), _bits(torch.from_numpy(want[0])))
+
+
+@functools.lru_cache(maxsize=None)
+def _coplanar_cases(n=4000):
+    """(origins (n, 1, 3), directions (n, 1, 3), vertices (n, 3, 3), faces (1, 3)): n meshes of one face, each with one ray, all on the
+    plane x = 3 y: y of 20 bits, so that 3 y is an fp32 value too."""
+    g = np.random.default_rng(0)
+
+    def q(x):
+        m, e = np.frexp(np.float32(x))
+        return np.float32(np.ldexp(np.round(m * 2 ** 20) / 2 ** 20, e))
+    o, d, v = [], [], []
+    for _ in range(n):
+        a, c, b, e = (q(g.normal()) for _ in range(4))
+        o.append([3 * a, a, c]), d.append([3 * b, b, e])
+        v.append([[3 * y, y, z] for y, z in ((q(a + 40 + g.normal()), q(c + g.normal())) for _ in range(3))])
+    as_tensor = lambda x: torch.from_numpy(np.asarray(x, dtype=np.float32))   # noqa: E731
+    return as_tensor(o)[:, None], as_tensor(d)[:, None], as_tensor(v), torch.tensor([[0, 1, 2]])
+
+
+@functools.lru_cache(maxsize=None)
+def _small_scene_cases(n=1500):
+    """(origins (4 n + 1, 1, 3), directions, vertices (4 n + 1, 3, 3), faces (1, 3)): meshes of one face with coordinates about 2^-77,
+    2^-76, 2^-75 and 2^-60, origins within twice that, each ray aimed at an interior point of its face -- a hit.  The squares of these
+    fp32 values are subnormal or 0 in fp32, where a rounding is absolute.  Case 0 is a ray that a filter without a guard on its own
+    underflow skipped (the face's rho^2 and |c - o|^2 both round to 0 or near it)."""
+    h = float.fromhex
+    v0 = [[h('-0x1.b1f092p-76'), h('-0x1.98d71cp-77'), h('0x1.22e63cp-78')], [h('-0x1.556920p-76'), h('0x1.02ae9ep-78'), h('-0x1.2e1154p-77')],
+          [h('-0x1.2a1164p-77'), h('0x1.1e9802p-76'), h('0x1.bff6e4p-79')]]
+    o0, d0 = [h('0x1.5ec91cp-75'), h('-0x1.e0e5c4p-76'), h('0x1.217842p-75')], [-4.15195990, 1.72854161, -2.31218624]
+    g = torch.Generator().manual_seed(76)
+    scale = torch.tensor([2.0 ** -77, 2.0 ** -76, 2.0 ** -75, 2.0 ** -60]).repeat_interleave(n)[:, None, None]
+    v = (2 * torch.rand(4 * n, 3, 3, generator=g) - 1) * scale
+    o = (2 * torch.rand(4 * n, 1, 3, generator=g) - 1) * 2 * scale
+    w = 0.1 + torch.rand(4 * n, 3, generator=g)
+    target = (v * (w / w.sum(1, keepdim=True))[..., None]).sum(1, keepdim=True)
+    d = (target - o) * (2.0 ** 76) * (0.5 + torch.rand(4 * n, 1, 1, generator=g))
+    return (torch.cat([torch.tensor([[o0]]), o]), torch.cat([torch.tensor([[d0]]), d]), torch.cat([torch.tensor([v0]), v]),
+            torch.tensor([[0, 1, 2]]))
+
+
+def test_scenes_of_subnormal_squares_are_hit_as_defined():
+    o, d, v, f = _small_scene_cases()
+    assert (v.abs().max() < 2.0 ** -59) and (v != 0).all() and torch.isfinite(d).all()
+    depth, face, count = metrics._torch_ray_cast(o, d, v, f)
+    want = reference(o[0], d[0], v[0], f)
+    assert want[2][0] == 1 and int(count[0, 0]) == 1 and torch.equal(_bits(depth[0]), _bits(torch.from_numpy(want[0])))
+    assert (count[:, 0] > 0).float().mean() > 0.9                            # aimed inside; a few round to an edge's other side
+
+
+# ---- CPU 5: gradients ------------------------------------------------------------------------------------------------------------------
+def _interior_rays(v, f, count, seed):
+    """Rays from outside aimed at points well inside faces (barycentrics >= 0.15): away from every edge."""
+    g = torch.Generator().manual_seed(seed)
+    w = 0.15 + 0.55 * torch.rand(count, 3, generator=g)
+    w = w / w.sum(1, keepdim=True)
+    target = (v[f[torch.randint(len(f), (count,), generator=g)]] * w[..., None]).sum(1)
+    lo, hi = _box(v)
+    o = (lo + hi) / 2 + (hi - lo) * (1.5 + torch.rand(count, 3, generator=g)) * torch.tensor([1.0, -1.0, 1.0])
+    return o, (target - o) * (0.5 + torch.rand(count, 1, generator=g))
+
+
+def test_gradcheck_in_float64_away_from_edges_and_the_gradient_of_a_miss_is_zero():
+    v, f = _named('tetrahedron')
+    o, d = _interior_rays(v, f, 6, seed=1)
+    o, d = torch.cat([o, o[:2]]).double(), torch.cat([d, -d[:2]]).double()    # the last two point away: misses
+    args = tuple(x.clone().requires_grad_() for x in (o, d, v[None].double()))
+    depth, face, count = metrics.ray_cast(*args, f)
+    assert (face[0, :6] >= 0).all() and (face[0, 6:] == -1).all() and depth.requires_grad
+    assert not face.requires_grad and not count.requires_grad
+    assert torch.autograd.gradcheck(lambda a, b, c: metrics.ray_cast(a, b, c, f)[0][:, :6], args, eps=1e-6, atol=1e-7, rtol=1e-6)
+    depth[0, 6:].sum().backward()                                             # inf, twice: the gradient of a miss is exactly 0
+    assert all(x.grad is not None and (x.grad == 0).all() for x in args)
+    depth, _, _ = metrics.ray_cast(*args, f)
+    torch.where(torch.isfinite(depth), depth, torch.zeros_like(depth)).sum().backward()
+    assert (args[0].grad[6:] == 0).all() and (args[1].grad[6:] == 0).all() and (args[0].grad[:6] != 0).any(1).all()
+    assert all(torch.isfinite(x.grad).all() for x in args)
+    # the analytic gradient of include/icn_raycast.h on the first ray
+    ids = f[face[0, 0]]
+    v0, v1, v2 = (v.double()[i] for i in ids)
+    n = torch.linalg.cross(v1 - v0, v2 - v0)
+    assert torch.allclose(args[0].grad[0], -n / (n * d[0]).sum(), rtol=1e-12, atol=0)
+    assert torch.allclose(args[1].grad[0], -float(depth.detach()[0, 0]) * n / (n * d[0]).sum(), rtol=1e-12, atol=0)
+
+
+# ---- CPU 6: the view functions ---------------------------------------------------------------------------------------------------------
+def test_depth_map_of_the_cube_along_an_axis():
+    v, f = _named('cube')
+    n, radius = 8, math.sqrt(3) / 2
+    offsets = (np.arange(n) + 0.5) * (2 * radius / n) - radius
+    in_square = np.abs(offsets) < 0.5
+    assert np.abs(np.abs(offsets) - 0.5).min() > 0.04                         # no pixel centre on the silhouette
+    for view in ((0, 0, 1), (0, 0, -3.0), (1, 0, 0), (0, 2, 0)):
+        depth, mask = metrics.depth_map(v[None], f, view, n)
+        assert depth.shape == mask.shape == (1, n, n) and mask.dtype == torch.bool and depth.dtype == torch.float32
+        want = torch.from_numpy(in_square[:, None] & in_square[None, :])
+        assert torch.equal(mask[0], want), view
+        assert (depth[0][~want] == INF).all()
+        assert (depth[0][want] - (2 * radius - 0.5)).abs().max() <= 4 * 2.0 ** -24 * 2 * radius      # the origin and the depth round to fp32
+    # an explicit frame, where every value is exact: 4 x 4 pixels of side 1/2 about the cube's centre, the plane 2 in front of it
+    depth, mask = metrics.depth_map(v[None].double(), f.int(), (0, 0, 1), 4, frame=((0.5, 0.5, 0.5), 1.0))
+    want = torch.zeros(4, 4, dtype=torch.bool)
+    want[1:3, 1:3] = True
+    assert torch.equal(mask[0], want) and (depth[0][want] == 1.5).all() and depth.dtype == torch.float64
+    # the basis: e1 = normalize(w x a), a the axis of w's smallest |component|, the first on ties; e2 = w x e1
+    assert metrics._view_basis((0, 0, 2)) == ((0.0, 0.0, 1.0), (0.0, 1.0, 0.0), (-1.0, 0.0, 0.0))
+    assert metrics._view_basis((0, 1, 0)) == ((0.0, 1.0, 0.0), (0.0, 0.0, -1.0), (-1.0, 0.0, 0.0))
+    w, e1, e2 = metrics._view_basis((1, 1, -1))
+    dots = [sum(a * b for a, b in zip(p, q)) for p, q in ((w, e1), (w, e2), (e1, e2))]
+    assert max(abs(x) for x in dots) < 1e-15 and abs(sum(x * x for x in e1) - 1) < 1e-15 and abs(sum(x * x for x in e2) - 1) < 1e-15
+    assert e1[0] == 0.0                                                       # a = x, the first of three equal components: e1 is w x (1, 0, 0)
+
+
+def test_silhouette_iou_of_cubes_is_exact():
+    v, f = _named('cube')
+    shifted = v + torch.tensor([0.5, 0.0, 0.0])
+    assert metrics.silhouette_iou(v, v, f, resolution=16) == 1.0
+    # the shared frame: centre (0.75, 0.5, 0.5), rho = sqrt(4.25) / 2; at 8 and at 58 pixels no centre lies on a silhouette edge, and
+    # the pixels in [0.5, 1] are a third of those in [0, 1.5] along x
+    for n in (8, 58):
+        radius = math.sqrt(4.25) / 2
+        offsets = (np.arange(n) + 0.5) * (2 * radius / n) - radius
+        edges = np.array([-0.75, -0.25, 0.25, 0.75, -0.5, 0.5])
+        assert np.abs(offsets[:, None] - edges[None]).min() > 0.01
+        assert 3 * (np.abs(offsets) < 0.25).sum() == (np.abs(offsets) < 0.75).sum()
+        assert metrics.silhouette_iou(v, shifted, f, resolution=n, views=[(1, 0, 0)]) == 1.0
+        assert metrics.silhouette_iou(v, shifted, f, resolution=n, views=[(0, 1, 0)]) == 1 / 3
+        assert metrics.silhouette_iou(v, shifted, f, resolution=n, views=[(0, 0, 1)]) == 1 / 3
+        assert metrics.silhouette_iou(v, shifted, f, resolution=n, views=metrics.SILHOUETTE_VIEWS[:3]) == (1.0 + 1 / 3 + 1 / 3) / 3
+    assert metrics.silhouette_iou(v.double(), shifted.double(), f.int(), resolution=n, views=[(0, -1, 0)]) == 1 / 3      # the mirror image
+    assert len(metrics.SILHOUETTE_VIEWS) == 7
+    assert 0.0 < metrics.silhouette_iou(v, shifted, f, resolution=24) < 1.0
+    assert metrics.silhouette_iou(v, v + 5.0, f, resolution=16, views=[(0, 0, 1)]) == 0.0
+    empty = torch.tensor([[0, 0, 0]])                                         # nothing to see: the union is empty, the view counts 0
+    assert metrics.silhouette_iou(v, shifted, empty, resolution=8) == 0.0
+
+
+def test_contains_by_parity_equals_contains_on_the_cubes():
+    v, f = _named('cube')
+    both = torch.stack([v, v + torch.tensor([0.5, 0.0, 0.0])])
+    axis = torch.arange(-3, 16, dtype=torch.float32) / 8 + 1 / 16            # no point on a surface
+    points = torch.stack(torch.meshgrid(axis, axis[:12], axis[:12], indexing='ij'), -1).reshape(1, -1, 3).expand(2, -1, -1)
+    want = metrics.contains(points, both, f)
+    assert want.any() and not want.all()
+    for direction in ((1, 0, 0), (0, 0, -1), (1, 2, 3), (-0.5, 0.25, 0.0)):
+        assert torch.equal(metrics.contains_by_parity(points, both, f, direction=direction), want), direction
+    assert torch.equal(metrics.contains_by_parity(points[0], both, f), want)                                    # (P, 3): shared by the batch
+    assert torch.equal(metrics.contains_by_parity(points, both, f.flip(1)), want)                               # wound the other way
+    flipped = torch.where((torch.arange(12) % 3 == 0)[:, None], f.flip(1), f)
+    assert torch.equal(metrics.contains_by_parity(points, both, flipped), want)                                 # or inconsistently
+    assert not metrics.contains_by_parity(torch.tensor([[NAN, 0.5, 0.5]]), both, f).any()
+
+
+# ---- CPU 7: rejected input -------------------------------------------------------------------------------------------------------------
+def test_bad_arguments_raise_and_open_meshes_are_refused_by_the_checked_function_only():
+    v, f = _named('cube')
+    o, d = _random_rays(v, 5, seed=0)
+    ok = (o, d, v[None], f)
+    assert metrics.ray_cast(*ok)[0].shape == (1, 5)
+    assert metrics.ray_cast(o[None], d, v[None], f.int())[0].shape == (1, 5)
+    for k, bad in ((0, o[:4]), (0, o[:, :2]), (0, o[None, None]), (0, o.long()), (0, o[:0]), (0, torch.stack([o, o])), (1, d[:3]), (1, None),
+                   (2, v), (2, v[None, :, :2]), (2, v[None].long()), (2, v[None][:0]), (3, f[:, :2]), (3, f[:0]), (3, f.float()), (3, f == 0)):
+        args = list(ok)
+        args[k] = bad
+        with pytest.raises(ValueError):
+            metrics.ray_cast(*args)
+    for bad in (f + 1, f - 1):
+        with pytest.raises(IndexError):
+            metrics.ray_cast(o, d, v[None], bad)
+        with pytest.raises(IndexError):
+            metrics.depth_map(v[None], bad, (0, 0, 1), 4)
+        with pytest.raises(IndexError):
+            metrics.silhouette_iou(v, v, bad, resolution=4)
+        with pytest.raises(IndexError):
+            metrics.contains_by_parity(o, v[None], bad)
+    # an open mesh: fine for ray_cast, depth_map and silhouette_iou, refused by contains_by_parity
+    assert metrics.ray_cast(o, d, v[None], f[:-1])[0].shape == (1, 5)
+    assert metrics.depth_map(v[None], f[:-1], (0, 0, 1), 4)[1].any()
+    assert metrics.silhouette_iou(v, v, f[:-1], resolution=4) == 1.0
+    with pytest.raises(ValueError, match=r'not closed: the edge \(\d+, \d+\) belongs to an odd number of faces \(3 such edges\)'):
+        metrics.contains_by_parity(o, v[None], f[:-1])
+    for direction in ((0, 0, 0), (1, 0), (NAN, 0, 1), (INF, 0, 0), 'abc', None):
+        with pytest.raises(ValueError):
+            metrics.contains_by_parity(o, v[None], f, direction=direction)
+    for view, resolution, frame in (((0, 0, 0), 4, None), ((1, 0), 4, None), ((NAN, 0, 1), 4, None), ('abc', 4, None), ((0, 0, 1), 0, None),
+                                    ((0, 0, 1), 2.5, None), ((0, 0, 1), None, None), ((0, 0, 1), 4, ((0, 0), 1.0)), ((0, 0, 1), 4, ((0, 0, 0), 0.0)),
+                                    ((0, 0, 1), 4, ((0, 0, NAN), 1.0)), ((0, 0, 1), 4, 3.0)):
+        with pytest.raises(ValueError):
+            metrics.depth_map(v[None], f, view, resolution, frame=frame)
+    for args, kwargs in (((v[None], v[None], f), {}), ((v, v[:7], f), {}), ((v, v, f), dict(resolution=0)), ((v, v, f), dict(resolution=None)), ((v, v, f), dict(views=[])),
+                         ((v, v, f), dict(views=[(0, 0, 0)])), ((v * 0, v * 0, f), {}), ((v * NAN, v, f), {})):
+        with pytest.raises(ValueError, match='silhouette_iou: '):
+            metrics.silhouette_iou(*args, **kwargs)
+
+
+# ---- GPU -------------------------------------------------------------------------------------------------------------------------------
+RAY_COUNTS = (1, 255, 256, 257, 1000)
+FAMILIES = ('random', 'aimed', 'grid', 'inside', 'scaled', 'shifted', 'invalid', 'tiny', 'huge')
+SCENE_SCALES = {'tiny': 2.0 ** -76, 'huge': 2.0 ** 63}       # the whole scene by a power of two: the filter's own fp32 values, m.m and
+                                                            # rho^2, underflow (below 2^-126) and overflow (above 2^128); the geometry stays
+
+
+def _family_rays(family, v, f, seed):
+    """(origins, directions) (1000, 3) fp32 about one mesh (vertices (V, 3), faces (F, 3)); each family holds hits and misses."""
+    n = RAY_COUNTS[-1]
+    finite = torch.isfinite(v).all(-1)
+    usable = f[((f >= 0) & (f < len(v))).all(1)].long()
+    usable = usable[finite[usable].all(1)]
+    lo, hi = _box(v)
+    mid, extent = (lo + hi) / 2, (hi - lo).max()
+    g = torch.Generator().manual_seed(seed)
+    if family in ('random', 'scaled', 'shifted', 'invalid', 'tiny', 'huge'):
+        o, d = _random_rays(v, n, seed)
+        if family == 'scaled':                                               # |d| of 1e-20 and of 1e20: dd far outside fp32
+            d = d * torch.where(torch.arange(n) % 2 == 0, 1e-20, 1e20)[:, None]
+        if family == 'invalid':
+            o, d = _with_invalid(o, d)
+        return o, d
+    if family == 'aimed':                                                     # one origin; the mesh's own vertices, edge midpoints, centroids
+        origin = hi + 0.6 * extent * torch.tensor([1.0, 0.7, 0.4])
+        tri = v[usable]
+        targets = torch.cat([v[finite], (tri[:, 0] + tri[:, 1]) / 2, (tri[:, 1] + tri[:, 2]) / 2, tri.mean(1)])
+        d = targets[torch.arange(n) % len(targets)] - origin
+        d = torch.where((torch.arange(n) % 4 == 3)[:, None], -d, d)          # every fourth points away: a miss
+        return origin.expand(n, 3).contiguous(), d
+    if family == 'grid':                                                      # orthographic, along the axis seed % 3, wider than the mesh
+        axis, side = seed % 3, 32
+        u = (torch.arange(side, dtype=torch.float32) + 0.5) / side * 1.3 - 0.65
+        a, b = torch.meshgrid(u, u, indexing='ij')
+        o = torch.zeros(side * side, 3)
+        o[:, axis] = -1.0
+        o[:, (axis + 1) % 3], o[:, (axis + 2) % 3] = a.reshape(-1), b.reshape(-1)
+        d = torch.zeros(side * side, 3)
+        d[:, axis] = 1.0
+        return (mid + o * (hi - lo))[:n].contiguous(), d[:n].contiguous()
+    assert family == 'inside'                                                 # origins on segments between face centroids: inside a convex
+    tri = v[usable]                                                           # mesh; every fifth moved far along its ray: it points away
+    c = tri.mean(1)
+    i, j = torch.randint(len(c), (n,), generator=g), torch.randint(len(c), (n,), generator=g)
+    s = 0.3 + 0.4 * torch.rand(n, 1, generator=g)
+    o = c[i] * s + c[j] * (1 - s)
+    d = torch.randn(n, 3, generator=g)
+    o = torch.where((torch.arange(n) % 5 == 4)[:, None], o + 4 * extent * d / d.norm(dim=1, keepdim=True), o)
+    return o, d
+
+
+@functools.lru_cache(maxsize=None)
+def _float64_case(name, family):
+    """(origins, directions (3, 1000, 3), vertices, faces, the float64 formulation's answer on the CPU): computed once, shared, never
+    changed.  The smaller ray counts and batches are slices of it: rays and meshes are independent of each other."""
+    v, f = _gpu_mesh(name)
+    v = (v + 1000.0) if family == 'shifted' else v * SCENE_SCALES.get(family, 1.0)
+    rays = [_family_rays(family, v[b], f, seed=b + 1) for b in range(3)]
+    o, d = torch.stack([r[0] for r in rays]), torch.stack([r[1] for r in rays])
+    return o, d, v, f, metrics._torch_ray_cast(o, d, v, f)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('family', FAMILIES)
+@pytest.mark.parametrize('name', GPU_MESHES)
+def test_hip_equals_the_float64_formulation_bit_for_bit(name, family):
+    o, d, v, f, want = _float64_case(name, family)
+    assert (want[2] > 0).any() and (want[2] == 0).any(), 'the family must hold hits and misses'
+    assert torch.equal(want[1] >= 0, want[2] > 0) and not torch.isnan(want[0]).any()
+    oc, dc, vc, fc = o.cuda(), d.cuda(), v.cuda(), f.cuda()
+    for B in (1, 3):
+        for R in RAY_COUNTS:
+            got = metrics._ray_cast_unchecked(oc[:B, :R].contiguous(), dc[:B, :R].contiguous(), vc[:B], fc)
+            assert all(x.is_cuda and x.shape == (B, R) for x in got)
+            _same(got, tuple(x[:B, :R] for x in want), (name, family, B, R))
+    if NO_CULL_LIBRARY:                                                       # the kernel built without its filter: the same bits
+        _same(_through_library(NO_CULL_LIBRARY, oc, dc, vc, fc), want, (name, family, 'no filter'))
+
+
+NO_CULL_LIBRARY = os.environ.get('ICN_RAYCAST_NO_CULL_LIB')                   # a libicn.so built with -DICN_RAYCAST_NO_CULL (tools/time_raycast.py)
+
+
+def _through_library(path, o, d, v, f):
+    """icn_mesh_raycast of another build of the library on contiguous device tensors -> (depth, face int64, count)."""
+    import ctypes
+    res, argtypes, _ = _lib.UNPINNED_HEADERS['icn_raycast.h']['icn_mesh_raycast']
+    fn = ctypes.CDLL(path).icn_mesh_raycast
+    fn.restype, fn.argtypes = res, argtypes
+    B, R = o.shape[:2]
+    depth = torch.empty(B, R, device=o.device)
+    face, count = (torch.empty(B, R, dtype=torch.int32, device=o.device) for _ in range(2))
+    assert fn(o.data_ptr(), d.data_ptr(), v.data_ptr(), f.data_ptr(), B, R, v.shape[1], f.shape[0], depth.data_ptr(), face.data_ptr(),
+              count.data_ptr(), _lib.stream()) == 0
+    torch.cuda.synchronize()
+    return depth, face.long(), count
+
+
+@pytest.mark.gpu
+def test_hip_on_scenes_at_the_ends_of_the_fp32_range():
+    o, d, v, f = _small_scene_cases()
+    want = metrics._torch_ray_cast(o, d, v, f)
+    assert int(want[2][0, 0]) == 1 and (want[2] > 0).float().mean() > 0.9
+    _same(metrics._ray_cast_unchecked(o.cuda(), d.cuda(), v.cuda(), f.int().cuda()), want)
+
+
+@pytest.mark.gpu
+def test_hip_counts_the_far_coplanar_faces_that_the_definition_counts():
+    o, d, v, f = _coplanar_cases()
+    want = metrics._torch_ray_cast(o, d, v, f)
+    assert (want[2] > 0).any()
+    _same(metrics._ray_cast_unchecked(o.cuda(), d.cuda(), v.cuda(), f.int().cuda()), want)
+
+
+@pytest.mark.gpu
+def test_hip_through_the_checked_functions_with_shared_rays():
+    o, d, v, f, want = _float64_case('I2', 'random')
+    got = metrics.ray_cast(o[0].cuda(), d[0].cuda(), v.cuda(), f.long().cuda())                  # rays (R, 3), shared by the batch
+    _same(got, metrics._torch_ray_cast(o[:1].expand(3, -1, -1), d[:1].expand(3, -1, -1), v, f))
+    with pytest.raises(IndexError):
+        metrics.ray_cast(o[0].cuda(), d[0].cuda(), v.cuda(), f.cuda() + 1)
+    with pytest.raises(ValueError, match='not closed'):
+        metrics.contains_by_parity(o.cuda(), v.cuda(), f[:-1].cuda())
+
+
+def _backward_case(R):
+    """fp32 inputs on the CPU for the backward: the noisy I2 at its three scales, rays aimed inside faces, an upstream with zeros."""
+    v, f = _gpu_mesh('I2')
+    rays = [_interior_rays(v[b], f.long(), R, seed=20 + b) for b in range(3)]
+    o, d = torch.stack([r[0] for r in rays]), torch.stack([r[1] for r in rays])
+    g = torch.Generator().manual_seed(R)
+    up = torch.randn(3, R, generator=g) * (torch.rand(3, R, generator=g) > 0.25)       # zeros on a quarter of the rays
+    return o, d, v, f, up
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('R', (257, 1000))
+def test_hip_backward_against_float64_autograd_element_by_element(R):
+    """|got - ref| <= rho 2^-24 A, A the same sum on absolute values.  dorigins / ddirections are one term each, computed in double
+    and rounded once: rho = 2 (the rounding, and one unit for the double arithmetic and the reference's own).  A vertex with n records
+    gets n products of (float)G and (float)w -- three roundings a term -- and n - 1 fp32 additions: rho = n + 3.  Exactly 0 where A is."""
+    o, d, v, f, up = _backward_case(R)
+    ref_in = tuple(x.double().requires_grad_() for x in (o, d, v))
+    depth, face, count = metrics._torch_ray_cast(*ref_in, f)
+    hit = face >= 0
+    assert hit.sum() > 0.9 * hit.numel() and ((up == 0) & hit).any()
+    masked = torch.where(hit, up, torch.zeros_like(up))
+    depth.backward(masked.double())
+    # the per-ray terms of the vertex gradient, for A and n: t once more on the gathered corners as a leaf
+    ids = f.long()[face.clamp(0)]
+    tri = torch.gather(v.double(), 1, ids.reshape(3, R * 3, 1).expand(-1, -1, 3)).reshape(3, R, 3, 3).requires_grad_()
+    t, _ = metrics._ray_parameter(ids, tri, o.double(), d.double())
+    torch.where(hit, t, torch.zeros_like(t)).backward(masked.double())
+    terms = torch.where(hit[..., None, None], tri.grad, torch.zeros_like(tri.grad))                # (3, R, corners, 3)
+    at = ids.reshape(3, R * 3, 1).expand(-1, -1, 3)
+    A_v = torch.zeros_like(v, dtype=torch.float64).scatter_add_(1, at, terms.abs().reshape(3, R * 3, 3))
+    n_v = torch.zeros_like(v, dtype=torch.float64).scatter_add_(1, at, hit[..., None, None].expand(-1, -1, 3, 3).double().reshape(3, R * 3, 3))
+    again = torch.zeros_like(v, dtype=torch.float64).scatter_add_(1, at, terms.reshape(3, R * 3, 3))
+    assert torch.allclose(again, ref_in[2].grad, rtol=1e-12, atol=1e-300)     # the terms are the reference's
+    got_in = tuple(x.cuda().requires_grad_() for x in (o, d, v))
+    got = metrics._ray_cast_unchecked(*got_in, f.cuda())
+    _same(got, (depth.detach().float(), face, count))
+    got[0].backward(masked.cuda())
+    measured = {}
+    for name, x, ref, A, factor in (('dorigins', got_in[0].grad, ref_in[0].grad, ref_in[0].grad.abs(), 2.0),
+                                    ('ddirections', got_in[1].grad, ref_in[1].grad, ref_in[1].grad.abs(), 2.0),
+                                    ('dvertices', got_in[2].grad, ref_in[2].grad, A_v, n_v + 3)):
+        measured[name] = rho(x, ref, A * factor)
+        print('R = %d, %s: largest |got - ref| / (2^-24 A) = %.3f, as a share of its bound %.3f'
+              % (R, name, rho(x, ref, A), measured[name]))
+    assert (got_in[0].grad[~hit.cuda()] == 0).all() and (got_in[1].grad[~hit.cuda()] == 0).all()
+    assert (got_in[2].grad[(A_v == 0).cuda()] == 0).all() and (A_v == 0).any()
+    assert all(m <= 1.0 for m in measured.values()), measured
+
+
+@pytest.mark.gpu
+def test_launch_counts_determinism_and_batch_slicing(monkeypatch):
+    o, d, v, f, up = _backward_case(257)
+    oc, dc, vc, fc, upc = o.cuda(), d.cuda(), v.cuda(), f.cuda(), up.cuda()
+
+    def forward():
+        return metrics._ray_cast_unchecked(oc, dc, vc, fc)
+
+    def both(needs=(True, True, True)):
+        args = tuple(x.detach().requires_grad_(n) for x, n in zip((oc, dc, vc), needs))
+        out = metrics._ray_cast_unchecked(*args, fc)
+        out[0].backward(torch.where(out[1] >= 0, upc, torch.zeros_like(upc)))
+        return out + tuple(x.grad for x in args)
+    whole, kernels = _profiled(forward)
+    assert kernels == {'k_mesh_raycast': 1}
+    full, kernels = _profiled(both)
+    assert kernels == {'k_mesh_raycast': 1, 'k_mesh_raycast_bwd_record': 1, 'k_mesh_raycast_bwd_vertex': 1}
+    _, kernels = _profiled(lambda: both((True, True, False)))                 # without dvertices: no scatter, no workspace
+    assert kernels == {'k_mesh_raycast': 1, 'k_mesh_raycast_bwd_record': 1}
+    only_v, kernels = _profiled(lambda: both((False, False, True)))
+    assert kernels == {'k_mesh_raycast': 1, 'k_mesh_raycast_bwd_record': 1, 'k_mesh_raycast_bwd_vertex': 1}
+    assert only_v[3] is None and only_v[4] is None and torch.equal(only_v[5], full[5])
+    again = both()
+    assert all(torch.equal(a, b) for a, b in zip(again, full))                # bit-identical run to run
+    assert all(torch.equal(a, b) for a, b in zip(whole, full[:3]))
+    for limit, launches in ((2, 2), (1, 3)):
+        monkeypatch.setattr(metrics, '_MAX_GRID_Y', limit)
+        sliced, kernels = _profiled(both)
+        assert kernels == {'k_mesh_raycast': launches, 'k_mesh_raycast_bwd_record': launches, 'k_mesh_raycast_bwd_vertex': launches}
+        assert all(torch.equal(a, b) for a, b in zip(sliced, full))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('with_gradient', (False, True))
+def test_no_host_synchronisation_in_the_unchecked_calls(with_gradient):
+    o, d, v, f, up = _backward_case(257)
+    oc, dc, vc, fc, upc = o.cuda(), d.cuda(), v.cuda(), f.cuda(), up.cuda()
+
+    def run():
+        x = vc.detach().requires_grad_(with_gradient)
+        out = metrics._ray_cast_unchecked(oc, dc, x, fc)
+        if with_gradient:
+            out[0].backward(torch.where(out[1] >= 0, upc, torch.zeros_like(upc)))
+        return out + (x.grad,)
+    want = run()                                                              # the allocator settles
+    torch.cuda.synchronize()
+    probe = torch.ones(1, device='cuda')
+    previous = torch.cuda.get_sync_debug_mode()
+    torch.cuda.set_sync_debug_mode('error')
+    try:
+        try:
+            probe.item()
+            caught = False
+        except RuntimeError:
+            caught = True
+        if caught:
+            got = run()
+    finally:
+        torch.cuda.set_sync_debug_mode(previous)
+    assert caught, "torch.cuda.set_sync_debug_mode('error') does not catch a deliberate .item() on this build"
+    assert (got[3] is not None) == with_gradient
+    assert all((a is None and b is None) or torch.equal(a, b) for a, b in zip(got, want))
+
+
+@pytest.mark.gpu
+def test_parity_against_contains_on_the_device():
+    """The parity may differ from the fp32 signed distance only where |phi| <= 1e-5, and at most 1 % of the origins may be set aside so."""
+    v, f = _sphere(2, 0.1)
+    origin, h, counts = metrics.voxel_lattice(v, v, 24)
+    vc, fc = v.cuda()[None], f.cuda()
+    centres = torch.from_numpy(_centres(origin, h, counts)).float().cuda()[None]
+    phi = metrics.signed_point_to_mesh_distance(centres, vc, fc)[0]
+    aside = phi.abs() <= 1e-5
+    for direction in ((1, 0, 0), (0.3, -1.0, 0.2)):
+        got = metrics.contains_by_parity(centres, vc, fc, direction=direction)
+        print('%d origins, %d inside, %d set aside, %d differ' % (got.numel(), int(got.sum()), int(aside.sum()), int((got != (phi < 0)).sum())))
+        assert int(aside.sum()) <= 0.01 * got.numel()
+        assert torch.equal(got[~aside], (phi < 0)[~aside])
+        assert got.any() and not got.all()
+        assert torch.equal(got.cpu(), metrics.contains_by_parity(centres.cpu(), v[None], f, direction=direction))
+
+
+@pytest.mark.gpu
+def test_depth_map_and_silhouette_iou_on_the_device_are_the_cpu_values():
+    v, f = _named('cube')
+    shifted = v + torch.tensor([0.5, 0.0, 0.0])
+    for views, want in (([(1, 0, 0)], 1.0), ([(0, 1, 0)], 1 / 3), ([(0, 0, 1)], 1 / 3)):
+        assert metrics.silhouette_iou(v.cuda(), shifted.cuda(), f.cuda(), resolution=58, views=views) == want
+    s, sf = _sphere(2, 0.1)
+    want = metrics.silhouette_iou(0.9 * s, s + 0.05, sf, resolution=32)
+    assert 0.5 < want < 1.0
+    assert metrics.silhouette_iou(0.9 * s.cuda(), s.cuda() + 0.05, sf.cuda(), resolution=32) == want
+    both = torch.stack([0.9 * s, s + 0.05])
+    for view in ((0, 0, 1), (1, 1, -1), (0.2, -0.7, 0.4)):
+        depth, mask = metrics.depth_map(both, sf, view, 48)
+        got_depth, got_mask = metrics.depth_map(both.cuda(), sf.cuda(), view, 48)
+        assert torch.equal(got_mask.cpu(), mask) and torch.equal(_bits(got_depth.cpu()), _bits(depth))
+        assert mask.any() and not mask.all()
+    frame = ((0.1, 0.0, -0.1), 1.7)
+    depth, mask = metrics.depth_map(both, sf, (1, 2, 3), 31, frame=frame)
+    got_depth, got_mask = metrics.depth_map(both.cuda(), sf.cuda(), (1, 2, 3), 31, frame=frame)
+    assert torch.equal(got_mask.cpu(), mask) and torch.equal(_bits(got_depth.cpu()), _bits(depth))
