@@ -148,7 +148,7 @@ LATER_HEADERS = {
 
 # Every header after those: the same shape, conventions and library, bound in the same loop of lib() and hashed by source_files().
 # This table ends the chain of tables: NO TEST MAY FIX ITS KEY SET.  A new header is one more key here and one more ABI test file that
-# names only its own header (icn_voxel.h: tests/test_abi_voxel.py, icn_raycast.h: tests/test_abi_raycast.py), so adding a header never needs another table.
+# names only its own header (icn_voxel.h: tests/test_abi_voxel.py, icn_raycast.h: tests/test_abi_raycast.py, icn_nn.h: tests/test_abi_nn.py), so adding a header never needs another table.
 UNPINNED_HEADERS = {
     'icn_voxel.h': {                   # solid voxelisation by ray parity
         'icn_mesh_voxelize': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_double] * 4 + [ctypes.c_int] * 3
@@ -159,6 +159,12 @@ UNPINNED_HEADERS = {
         'icn_mesh_raycast_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 3, PLAIN),
         'icn_mesh_raycast_bwd': (ctypes.c_int, [_c_float_p] * 6 + [ctypes.c_int] * 4 + [_c_float_p] * 3
                                  + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+    },
+    'icn_nn.h': {                      # nearest-neighbour search between point sets, and the backward of the distance
+        'icn_nearest_points': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 3 + [_c_float_p] * 2 + [ctypes.c_void_p], RC),
+        'icn_nearest_points_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 3, PLAIN),
+        'icn_nearest_points_bwd': (ctypes.c_int, [_c_float_p] * 4 + [ctypes.c_int] * 3 + [_c_float_p] * 2
+                                   + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
     },
 }
 

@@ -20,6 +20,7 @@
 #include "../../include/icn_sdf.h"
 #include "../../include/icn_voxel.h"
 #include "../../include/icn_raycast.h"
+#include "../../include/icn_nn.h"
 #include "../../include/icn_measure.h"
 #include "icn_geometry.h"
 #include "icn_launch.h"
@@ -798,7 +799,8 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_mesh_cotlap_fwd", "k_mesh_willmore_finish", "k_mesh_willmore_upstream", "k_mesh_cotlap_bwd",
                                             "k_mesh_angle_defect_fwd", "k_mesh_angle_defect_bwd", "k_mesh_self_intersect", "k_p2m_sign",
                                             "k_mesh_voxelize",
-                                            "k_mesh_raycast", "k_mesh_raycast_bwd_record", "k_mesh_raycast_bwd_vertex"};
+                                            "k_mesh_raycast", "k_mesh_raycast_bwd_record", "k_mesh_raycast_bwd_vertex",
+                                            "k_nn_points", "k_nn_points_bwd_record", "k_nn_points_bwd_vertex"};
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1629,6 +1631,37 @@ int icn_mesh_raycast_bwd(const float* origins, const float* directions, const fl
         if (!dorigins && !ddirections && !dvertices) return;         // no gradient asked for
         if (dvertices) check_workspace("icn_mesh_raycast_bwd", ws, ws_bytes, icn::vertex_records_bytes((size_t)B * R));
         icn::launch_mesh_raycast_bwd(origins, directions, vertices, faces, face, ddepth, B, R, V, F, dorigins, ddirections, dvertices, ws, s);
+        ICN_HIP(hipGetLastError());
+    });
+}
+
+// ---- nearest-neighbour search between point sets (include/icn_nn.h): two point counts whose three values per point fit an int -----------
+namespace {
+bool nearest_sizes_ok(int B, int N, int M) { return mesh_sizes_ok(B, N, M, 1) && N <= 0x7fffffff / 3 && M <= 0x7fffffff / 3; }
+}  // namespace
+
+int icn_nearest_points(const float* points, const float* targets, int B, int N, int M, float* dist, int32_t* idx, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!points || !targets || !dist || !idx) throw std::invalid_argument("icn_nearest_points: null pointer");
+        if (!nearest_sizes_ok(B, N, M)) throw std::invalid_argument("icn_nearest_points: bad sizes");
+        icn::launch_nearest_points(points, targets, B, N, M, dist, idx, s);
+    });
+}
+
+size_t icn_nearest_points_bwd_workspace_bytes(int B, int N, int M) {
+    return nearest_sizes_ok(B, N, M) ? icn::vertex_records_bytes((size_t)B * N) : 0;
+}
+
+int icn_nearest_points_bwd(const float* points, const float* targets, const int32_t* idx, const float* ddist, int B, int N, int M,
+                           float* dpoints, float* dtargets, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return guarded([&] {                                             // (not `launched`: the early way out touches no device)
+        if (!points || !targets || !idx || !ddist) throw std::invalid_argument("icn_nearest_points_bwd: null pointer");
+        if (!nearest_sizes_ok(B, N, M)) throw std::invalid_argument("icn_nearest_points_bwd: bad sizes");
+        if (!dpoints && !dtargets) return;                           // no gradient asked for
+        if (dtargets) check_workspace("icn_nearest_points_bwd", ws, ws_bytes, icn::vertex_records_bytes((size_t)B * N));
+        icn::launch_nearest_points_bwd(points, targets, idx, ddist, B, N, M, dpoints, dtargets, ws, s);
         ICN_HIP(hipGetLastError());
     });
 }

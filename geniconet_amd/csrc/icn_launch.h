@@ -314,6 +314,14 @@ void launch_mesh_raycast(const float* org, const float* dir, const float* vts, c
 void launch_mesh_raycast_bwd(const float* org, const float* dir, const float* vts, const int32_t* faces, const int32_t* face,
                              const float* ddepth, int B, int R, int V, int F, float* dorg, float* ddir, float* dvts, void* ws, hipStream_t s);
 
+// nearest-neighbour search between point sets (icn_nn.hip; include/icn_nn.h): every thread a few queries against the targets of its
+// cloud through LDS tiles, fp32 without contraction: squared distance and index of the nearest target.  One launch on s, no workspace.
+void launch_nearest_points(const float* pts, const float* tgt, int B, int N, int M, float* dist, int32_t* idx, hipStream_t s);
+// its backward at the forward's choice: dpts (B, N, 3) and / or dtgt (B, M, 3), each may be null (not both); ws (only read when dtgt
+// is wanted): vertex_records_bytes(B * N) bytes, 16-byte aligned.  One launch, then launch_vertex_scatter for dtgt.
+void launch_nearest_points_bwd(const float* pts, const float* tgt, const int32_t* idx, const float* ddist, int B, int N, int M,
+                               float* dpts, float* dtgt, void* ws, hipStream_t s);
+
 // developer routing flags (ICN_DEBUG / icn_set_debug_flags): 16 = convs on k_gather_gemm, 32 = wgrads on k_wgrad,
 // 128 = no stream-K, 256 = fault injection: every stream-K finisher reports its partners lost (tests of the failure path),
 // 512 = masked launches walk tiles b, b + G, ... instead of the balanced tile lists, 1024 = the sparse passes of the decoder-block
@@ -324,7 +332,7 @@ int debug_flags();
 int set_debug_flags(int flags);
 
 // ---- optional per-launch HIP-event timing of the MFMA kernels (bench.py's live roofline measurement) and of the
-// point-to-mesh, surface-sampling, normal-agreement, mesh-measure, mesh-curvature, angle-defect, self-intersection, distance-sign, voxelisation and ray-casting kernels ----------
+// point-to-mesh, surface-sampling, normal-agreement, mesh-measure, mesh-curvature, angle-defect, self-intersection, distance-sign, voxelisation, ray-casting and nearest-neighbour kernels ----------
 enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA_64x64, PROF_GG_128x128, PROF_GG_128x64,
                 PROF_GG_64x128, PROF_GG_64x64, PROF_WGD_128x128, PROF_WGD_128x64, PROF_WGD_64x128, PROF_WGD_64x64, PROF_WG_128x128,
                 PROF_WG_128x64, PROF_WG_64x128, PROF_WG_64x64,
@@ -348,6 +356,7 @@ enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA
                 PROF_P2M_SIGN,                                                                      // sign of the point-to-mesh distance
                 PROF_MESH_VOXELIZE,                                                                 // solid voxelisation by ray parity
                 PROF_MESH_RAYCAST, PROF_MESH_RAYCAST_BWD_RECORD, PROF_MESH_RAYCAST_BWD_VERTEX,      // ray casting and its backward
+                PROF_NN, PROF_NN_BWD_RECORD, PROF_NN_BWD_VERTEX,                                    // nearest-neighbour search and its backward
                 PROF_KINDS };
 extern const char* const PROF_NAMES[PROF_KINDS];
 void prof_mark_begin(int kind, double flops, hipStream_t s);   // no-ops unless profiling is on

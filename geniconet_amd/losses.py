@@ -718,3 +718,81 @@ class SurfaceKLD_Loss(Surface_Loss, KLD_Loss):
 
     def get_last_losses(self):
         return float(self.recons_loss.detach()), 0, 0, -float(self.kld_loss.detach()), float(self.loss.detach())
+
+
+class Chamfer_Loss(torch.nn.Module):
+    """Chamfer training criterion, criterion(output (B, 3, 5n, 2n), target (B, 9, V)) as Trainer.step calls it: the CustomChamfer loss
+    the reference names beside its others (run.py:629) and does not ship.
+
+        out = grid_to_vertices(output);  ref = target[:, 0:3] as (B, V, 3)
+        loss = mean_b ( w1 mean_i sided(out, ref)_i + w2 mean_j sided(ref, out)_j )          = mean_b metrics.chamfer_distance(out, ref)
+
+    with metrics.sided_distance, the squared distance of every point to its nearest point in the other set (HIP kernels
+    icn_nearest_points / icn_nearest_points_bwd on ROCm fp32 tensors, fixed summation order: bit-identical run to run).  Both terms
+    are differentiable in the output: the first through the points, the second through the chosen targets.
+    samples = S > 0 measures surfaces instead of vertices, as in Surface_Loss and with its sampler and its draw order: every forward
+    draws u = torch.rand((2, B, S, 3), generator=g, device=output.device), g seeded with sample_seed on the first forward's device,
+    and the two point sets are sampling.sample_points(out mesh, u[0]) and sampling.sample_points(ref mesh, u[1]) over the ico faces
+    (gradient to the output through icn_mesh_sample_bwd).  The loss is then a stochastic estimate.  The face list is a buffer
+    validated at construction and nothing is read back: forward + backward never synchronise the host.
+    Cost on an MI355X: profiles/nearest_neighbour.txt (tools/time_nearest.py)."""
+
+    _draw_uniforms = Surface_Loss._draw_uniforms
+
+    def __init__(self, subdivisions, samples=0, sample_seed=0, w1=1.0, w2=1.0):
+        super().__init__()
+        who = type(self).__name__
+        _check_subdivisions(who, subdivisions)
+        _check_factors(who, w1=w1, w2=w2)
+        if isinstance(samples, bool) or not isinstance(samples, int) or samples < 0:
+            raise ValueError('%s: samples must be a non-negative integer, got %r' % (who, samples))
+        if isinstance(sample_seed, bool) or not isinstance(sample_seed, int):
+            raise ValueError('%s: sample_seed must be an integer, got %r' % (who, sample_seed))
+        self.subdivisions, self.w1, self.w2 = subdivisions, w1, w2
+        self.samples, self.sample_seed, self._sample_generator = samples, sample_seed, None
+        faces = geometry.get_ico_faces(subdivisions)
+        nv = geometry.num_vertices(subdivisions)
+        if faces.ndim != 2 or faces.shape[1] != 3 or faces.min() < 0 or faces.max() >= nv:
+            raise ValueError('%s: the face table does not index %d vertices' % (who, nv))
+        self.register_buffer('ico_faces', torch.from_numpy(faces).to(torch.int32))
+        self.last_chamfer = 0
+
+    def forward(self, output, target):
+        from .metrics import _chamfer_unchecked
+        from .sampling import _sample_points_unchecked
+        n, who = 2 ** self.subdivisions, type(self).__name__
+        if output.dim() != 4 or tuple(output.shape[1:]) != (3, 5 * n, 2 * n) or output.shape[0] < 1:
+            raise ValueError('%s: expected output (B, 3, %d, %d), got %s' % (who, 5 * n, 2 * n, tuple(output.shape)))
+        if tuple(target.shape) != (output.shape[0], 9, 10 * n * n + 2):
+            raise ValueError('%s: expected target (%d, 9, %d), got %s' % (who, output.shape[0], 10 * n * n + 2, tuple(target.shape)))
+        out = grid_to_vertices(output, self.subdivisions)
+        ref = target[:, 0:3].transpose(1, 2).contiguous().to(out.dtype)
+        if self.samples:
+            faces = self.ico_faces if self.ico_faces.device == out.device else self.ico_faces.to(out.device)
+            u = self._draw_uniforms(out.shape[0], out.device)
+            out, ref = _sample_points_unchecked(out, faces, u[0])[0], _sample_points_unchecked(ref, faces, u[1])[0]
+        loss = _chamfer_unchecked(out, ref, self.w1, self.w2).mean()
+        self.last_chamfer = loss.detach()
+        return loss
+
+    def get_last_losses(self):
+        """(chamfer, 0, 0, 0., total) -- the five-tuple of P2P_Loss."""
+        return float(self.last_chamfer), 0, 0, 0., float(self.last_chamfer)
+
+
+class ChamferKLD_Loss(Chamfer_Loss, KLD_Loss):
+    """Chamfer_Loss of the reconstruction + factor_kl * KLD, for (recon, mu, logvar) outputs -- as SurfaceKLD_Loss is to Surface_Loss."""
+
+    def __init__(self, subdivisions, samples=0, sample_seed=0, w1=1.0, w2=1.0, factor_kl=1.0):
+        super().__init__(subdivisions, samples=samples, sample_seed=sample_seed, w1=w1, w2=w2)
+        _check_factors('ChamferKLD_Loss', factor_kl=factor_kl)
+        self.factor_kl = factor_kl
+
+    def forward(self, output, target):
+        self.kld_loss = KLD_Loss.forward(self, output, target)
+        self.recons_loss = Chamfer_Loss.forward(self, output[0], target)
+        self.loss = self.recons_loss + self.factor_kl * self.kld_loss
+        return self.loss
+
+    def get_last_losses(self):
+        return float(self.recons_loss.detach()), 0, 0, -float(self.kld_loss.detach()), float(self.loss.detach())

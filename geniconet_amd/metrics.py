@@ -80,6 +80,15 @@ through it; an fp32 filter proved to change nothing in front).  The parity of th
 needs no consistent winding; the depth is differentiable in vertices, origins and directions (icn_mesh_raycast_bwd: one record per
 ray, then the vertex scatter); depth_map renders orthographic depth images and silhouettes, and silhouette_iou is the 2-D mask IoU
 of one mesh pair over seven views, to stand beside volumetric_iou.  The HIP path reproduces the float64 formulation bit for bit.
+
+sided_distance, chamfer_distance, f_score and hausdorff_distance (below) measure two POINT SETS against each other, the figures every
+mesh-reconstruction paper reports and the reference's test modes `chamfer` and `f_<radius>` (run.py:630; kaolin.metrics.pointcloud
+upstream): for every point of one set the squared distance to its nearest point in the other set and which point that is
+(icn_nearest_points, include/icn_nn.h: the targets through LDS tiles in ascending order, two queries per thread in registers, fp32
+without contraction, the lowest index among equal distances, no atomics; the distance is differentiable in both sets through
+icn_nearest_points_bwd, one record per point, then the vertex scatter).  The HIP path reproduces the fp32 formulation bit for bit.
+evaluate_distance gives every test mode of the reference for one mesh pair -- point2point, point2mesh, chamfer, f_<radius> -- and
+hausdorff, on the vertices or on surface samples, where compute_distance keeps the reference's answer (None but for point2mesh).
 """
 import torch
 
@@ -1851,6 +1860,215 @@ def silhouette_iou(outvertices, refvertices, faces, resolution=64, views=None):
     return sum(a / o if o else 0.0 for a, o in zip(counts[::2], counts[1::2])) / len(views)
 
 
+# ---- nearest neighbours between point sets: sided distance, chamfer, F-score, Hausdorff ------------------------------------------------
+_SIDED_CHUNK = 1 << 22             # (cloud, query, target) triples the torch formulation holds at once: 16 MiB per fp32 temporary
+
+
+def _torch_sided_distance_fwd(points, targets, chunk=_SIDED_CHUNK):
+    """The forward of the definition of sided_distance in torch, in the dtype of `points`: every difference, product and sum a torch
+    operation of its own, in the order of include/icn_nn.h -> (dist (B, N), idx (B, N) int64); no graph.  Chunked over the targets; the
+    lowest index among equal distances is picked explicitly, inside a chunk and between chunks."""
+    B, N, _ = points.shape
+    M, dev = targets.shape[1], points.device
+    with torch.no_grad():
+        p, t = points.detach(), targets.detach()
+        px, py, pz = p[:, :, None, 0], p[:, :, None, 1], p[:, :, None, 2]                                                # (B, N, 1)
+        best = torch.full((B, N), float('inf'), dtype=p.dtype, device=dev)
+        idx = torch.full((B, N), -1, dtype=torch.int64, device=dev)
+        step = max(1, chunk // (B * N))
+        for lo in range(0, M, step):
+            q = t[:, None, lo:lo + step]                                                                                  # (B, 1, c, 3)
+            dx, dy, dz = px - q[..., 0], py - q[..., 1], pz - q[..., 2]
+            d = (dx * dx + dy * dy) + dz * dz                                                                             # (B, N, c)
+            ok = d < float('inf')                                                          # what can ever be `< best`: no NaN, no +inf
+            d = torch.where(ok, d, torch.full_like(d, float('inf')))
+            nearest = d.amin(-1)
+            index = torch.arange(lo, lo + q.shape[2], device=dev).expand_as(d)
+            first = torch.where(ok & (d == nearest[..., None]), index, torch.full_like(index, M)).amin(-1)               # the lowest index
+            take = (first < M) & (nearest < best)                                                                         # earlier chunks win ties
+            best, idx = torch.where(take, nearest, best), torch.where(take, first, idx)
+    return best, idx
+
+
+def _torch_sided_distance_bwd(points, targets, idx, ddist, need_points=True, need_targets=True):
+    """The backward of the definition in torch, in the dtype of `points`, at the fixed choice idx (B, N) integer under the upstream
+    ddist (B, N): e = p - q_idx, s = 2 g, dpoints = s e, dtargets[idx] += -(s e); a row whose idx is outside [0, M) or whose e or g is
+    not finite is an exact zero and contributes nothing -> (dpoints or None, dtargets or None)."""
+    M = targets.shape[1]
+    idx = idx.long()
+    ok = (idx >= 0) & (idx < M)
+    at = idx.clamp(0, M - 1)[..., None].expand(-1, -1, 3)
+    e = points - torch.gather(targets, 1, at)
+    s = 2 * ddist
+    ok = ok & torch.isfinite(e).all(-1) & torch.isfinite(ddist)
+    d = torch.where(ok[..., None], s[..., None] * e, torch.zeros_like(e))
+    dtargets = torch.zeros_like(targets).scatter_add_(1, at, -d) if need_targets else None
+    return (d if need_points else None), dtargets
+
+
+class _TorchSidedDistanceFn(torch.autograd.Function):
+    """The definition with its own backward (not autograd's of the forward's lines: the rows that contribute nothing are part of the
+    definition), in any floating dtype on any device."""
+
+    @staticmethod
+    def forward(ctx, points, targets):
+        dist, idx = _torch_sided_distance_fwd(points, targets)
+        ctx.save_for_backward(points, targets, idx)
+        ctx.mark_non_differentiable(idx)
+        return dist, idx
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, ddist, _gidx):
+        points, targets, idx = ctx.saved_tensors
+        return _torch_sided_distance_bwd(points, targets, idx, ddist.to(points.dtype), *ctx.needs_input_grad)
+
+
+def _torch_sided_distance(points, targets):
+    """sided_distance by the definition in torch: fp32 in, the definition; float64 in, the same lines in double; differentiable in
+    both point sets."""
+    if torch.is_grad_enabled() and (points.requires_grad or targets.requires_grad):
+        return _TorchSidedDistanceFn.apply(points, targets)
+    return _torch_sided_distance_fwd(points, targets)
+
+
+def _hip_sided_distance(pts, tgt):
+    """icn_nearest_points on contiguous fp32 ROCm tensors -> (dist fp32, idx int32)."""
+    B, N, M = pts.shape[0], pts.shape[1], tgt.shape[1]
+    dist = torch.empty(B, N, dtype=torch.float32, device=pts.device)
+    idx = torch.empty(B, N, dtype=torch.int32, device=pts.device)
+    _launch('icn_nearest_points', _per_mesh(pts), _per_mesh(tgt), _NB, N, M, _per_mesh(dist), _per_mesh(idx))
+    return dist, idx
+
+
+class _SidedDistanceFn(torch.autograd.Function):
+    """sided_distance on the HIP path with a gradient (icn_nearest_points / icn_nearest_points_bwd in include/icn_nn.h): at the
+    forward's choice, 2 g (p - q) to the point and its negative to the chosen target, summed per target in a fixed order (bit-identical
+    run to run).  Only the gradients autograd asks for are computed."""
+
+    @staticmethod
+    def forward(ctx, points, targets):
+        pts, tgt = points.contiguous(), targets.contiguous()
+        dist, idx = _hip_sided_distance(pts, tgt)
+        ctx.save_for_backward(pts, tgt, idx)
+        idx64 = idx.long()
+        ctx.mark_non_differentiable(idx64)
+        return dist, idx64
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, ddist, _gidx):
+        pts, tgt, idx = ctx.saved_tensors
+        N, M = pts.shape[1], tgt.shape[1]
+        dpts = torch.empty_like(pts) if ctx.needs_input_grad[0] else None
+        dtgt = torch.empty_like(tgt) if ctx.needs_input_grad[1] else None
+        args = (_per_mesh(pts), _per_mesh(tgt), _per_mesh(idx), _per_mesh(_upstream(ddist)), _NB, N, M, _per_mesh(dpts), _per_mesh(dtgt))
+        if dtgt is not None:                                                              # only the targets' gradient needs scratch
+            _launch('icn_nearest_points_bwd', *args, workspace=('icn_nearest_points_bwd_workspace_bytes', N, M))
+        else:
+            _launch('icn_nearest_points_bwd', *args, None, 0)
+        return dpts, dtgt
+
+
+def _sided_distance_unchecked(p1, p2):
+    """sided_distance without its argument checks and without a host synchronisation, for callers that validated once: p1 (B, N, 3)
+    and p2 (B, M, 3) floating-point tensors of one dtype on one device, N, M >= 1."""
+    if _on_hip_path(p1) and p2.dtype == torch.float32:
+        if torch.is_grad_enabled() and (p1.requires_grad or p2.requires_grad):
+            return _SidedDistanceFn.apply(p1, p2)
+        dist, idx = _hip_sided_distance(p1.detach().contiguous(), p2.detach().contiguous())
+        return dist, idx.long()
+    return _torch_sided_distance(p1, p2)
+
+
+def _check_point_sets(who, p1, p2):
+    """The shape checks of two batched point sets -> (p1, p2 in p1's dtype and on its device).  ValueError."""
+    for name, x in (('the first', p1), ('the second', p2)):
+        if not torch.is_tensor(x) or not x.is_floating_point() or x.dim() != 3 or x.shape[-1] != 3 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError('%s: expected %s point set as a floating-point (B, N, 3) tensor with B, N >= 1, got %s'
+                             % (who, name, tuple(x.shape) if torch.is_tensor(x) else type(x).__name__))
+        if 3 * x.shape[1] > 0x7fffffff:
+            raise ValueError('%s: %d points: 3 N must fit an int32' % (who, x.shape[1]))
+    if p1.shape[0] != p2.shape[0]:
+        raise ValueError('%s: the batch sizes differ: %s and %s' % (who, tuple(p1.shape), tuple(p2.shape)))
+    return p1, p2.to(device=p1.device, dtype=p1.dtype)
+
+
+def sided_distance(p1, p2):
+    """(dist (B, N), idx (B, N) int64): for every point of p1 (B, N, 3) the SQUARED distance to its nearest point in p2 (B, M, 3) and
+    the index of that point (-1: none) -- kaolin.metrics.pointcloud.sided_distance, and the primitive under chamfer_distance, f_score
+    and hausdorff_distance.  dist is differentiable in both point sets at the choice it made; idx carries no gradient.
+
+    One definition for the HIP kernel (include/icn_nn.h), the torch formulation and the tests.  All arithmetic is in the dtype of p1
+    (fp32 on the device) on the values as stored, every product and sum rounded on its own, in exactly the order written:
+        dx = p.x - q_j.x;  dy = p.y - q_j.y;  dz = p.z - q_j.z;   d_j = (dx dx + dy dy) + dz dz
+        best = +inf, idx = -1;  for j = 0 ... M - 1 ascending: if d_j < best then best = d_j, idx = j
+    so among equal distances the lowest index wins, a NaN anywhere makes d_j NaN, which is never <, an infinite coordinate or an
+    overflowing d_j gives +inf, which is not < +inf, and a point with no acceptable target answers (+inf, -1).  A NaN never comes out.
+    Against float64 on the same values |d32 - d64| <= 6 2^-24 d64 while nothing underflows.
+    The gradient, at the chosen index under the upstream g: e = p - q_idx, s = 2 g, s e to the point and -(s e) to target idx; a row
+    with idx = -1, or with a non-finite e or g, is an exact zero and contributes nothing.
+    ROCm fp32 tensors run on icn_nearest_points: the targets pass through LDS tiles in ascending order, every thread holds two
+    queries in registers, no atomics, bit-identical run to run and equal to the fp32 formulation bit for bit; the backward is
+    icn_nearest_points_bwd, one record per point and the vertex scatter in a fixed order.  ICN_NO_HIP_LOSS=1, CPU tensors and other
+    dtypes take the definition in torch (_torch_sided_distance), chunked over the targets.  Shapes are checked (ValueError); nothing
+    is read back."""
+    return _sided_distance_unchecked(*_check_point_sets('sided_distance', p1, p2))
+
+
+def _rooted(d):
+    """sqrt of squared distances whose gradient at 0 is 0, not NaN."""
+    positive = d > 0
+    return torch.where(positive, torch.where(positive, d, torch.ones_like(d)).sqrt(), torch.zeros_like(d))
+
+
+def _per_cloud_mean(d):
+    """The mean over the points of every cloud, summed in double; still a double."""
+    return d.double().mean(1)
+
+
+def _chamfer_unchecked(p1, p2, w1=1.0, w2=1.0, squared=True):
+    """chamfer_distance after its checks: no host synchronisation."""
+    d12, d21 = _sided_distance_unchecked(p1, p2)[0], _sided_distance_unchecked(p2, p1)[0]
+    if not squared:
+        d12, d21 = _rooted(d12), _rooted(d21)
+    return (w1 * _per_cloud_mean(d12) + w2 * _per_cloud_mean(d21)).to(p1.dtype)
+
+
+def chamfer_distance(p1, p2, w1=1.0, w2=1.0, squared=True):
+    """(B,): w1 mean_i sided(p1, p2)_i + w2 mean_j sided(p2, p1)_j of two batched point sets (B, N, 3) and (B, M, 3) --
+    kaolin.metrics.pointcloud.chamfer_distance.  squared=False takes the root of each distance first (its gradient at a zero distance
+    is 0, not NaN).  The means are summed in double and the result is rounded once to the dtype of p1.  Differentiable in both sets
+    through sided_distance; nothing is read back."""
+    p1, p2 = _check_point_sets('chamfer_distance', p1, p2)
+    return _chamfer_unchecked(p1, p2, w1, w2, squared)
+
+
+def f_score(gt_points, pred_points, radius=0.01, eps=1e-8):
+    """(B,): the F-score of pred_points (B, N_pred, 3) against gt_points (B, N_gt, 3) at `radius` -- kaolin 0.9.1's
+    kaolin.metrics.pointcloud.f_score:
+        d_gt = sqrt(sided(pred, gt));  d_pred = sqrt(sided(gt, pred))
+        fp = #(d_gt > radius);  fn = #(d_pred > radius);  tp = N_pred - fp
+        precision = tp / (tp + fp);  recall = tp / (tp + fn);  F = 2 precision recall / (precision + recall + eps)
+    The counts are exact integers; the ratios are taken in double and F is rounded once to the dtype of gt_points.  No gradient;
+    nothing is read back."""
+    gt, pred = _check_point_sets('f_score', gt_points, pred_points)
+    with torch.no_grad():
+        d_gt, d_pred = _sided_distance_unchecked(pred, gt)[0].sqrt(), _sided_distance_unchecked(gt, pred)[0].sqrt()
+        fp, fn = (d_gt > radius).sum(1).double(), (d_pred > radius).sum(1).double()
+        tp = pred.shape[1] - fp
+        precision, recall = tp / (tp + fp), tp / (tp + fn)
+        return (2 * precision * recall / (precision + recall + eps)).to(gt.dtype)
+
+
+def hausdorff_distance(p1, p2):
+    """(B,): the point-set Hausdorff distance of two batched point sets, the larger of the two directed maxima of the (unsquared)
+    distances: max(max_i sqrt sided(p1, p2)_i, max_j sqrt sided(p2, p1)_j).  Differentiable through the one pair that attains it."""
+    p1, p2 = _check_point_sets('hausdorff_distance', p1, p2)
+    d12, d21 = _rooted(_sided_distance_unchecked(p1, p2)[0]), _rooted(_sided_distance_unchecked(p2, p1)[0])
+    return torch.maximum(d12.amax(1), d21.amax(1))
+
+
 def output2vertices(subdivisions, output):
     """Grid -> vertex list incl. the two pole means (reference ico_utils.py:10-24)."""
     from .losses import grid_to_vertices
@@ -1866,3 +2084,53 @@ def compute_distance(outvertices, refvertices, reffaces, mode='point2mesh', sear
         return None
     dist, _, _ = point_to_mesh_distance(outvertices[None], refvertices[None], reffaces, search=search)
     return float(dist.mean())
+
+
+EVALUATION_MODES = ('point2point', 'point2mesh', 'chamfer', 'f_<radius>', 'hausdorff')
+
+
+def evaluate_distance(outvertices, refvertices, reffaces, mode, samples=0, seed=0):
+    """The test modes the reference names (run.py:630: point2point, point2mesh, chamfer, f_<radius>) and 'hausdorff', for one mesh
+    pair ((V, 3) tensors; `reffaces` (F, 3) is the face table of both, as everywhere in the reference), as a Python float.
+    compute_distance itself keeps answering None to every mode but 'point2mesh', as the reference's computeDistance does.
+        'point2point'  the mean squared distance of corresponding vertices (the two meshes have one shape)
+        'point2mesh'   exactly compute_distance(outvertices, refvertices, reffaces)
+        'chamfer'      chamfer_distance of the two point sets
+        'f_<radius>'   f_score of the output's points against the reference's at that radius, for example 'f_0.01'
+        'hausdorff'    hausdorff_distance of the two point sets
+    The point sets of the last three are the vertices, or with samples = S > 0 sampling.sample_points of the two surfaces from
+    uniforms torch.rand((2, S, 3), generator=g), g a CPU generator seeded with `seed` (the output's surface takes the first S): the
+    same samples on every device.  An unknown mode raises ValueError."""
+    who = 'evaluate_distance'
+    radius = None
+    if isinstance(mode, str) and mode.startswith('f_'):
+        try:
+            radius = float(mode[2:])
+        except ValueError:
+            radius = None
+        if radius is None or not radius >= 0 or radius == float('inf'):
+            raise ValueError("%s: mode 'f_<radius>' needs a finite radius >= 0, got %r" % (who, mode))
+    elif mode not in ('point2point', 'point2mesh', 'chamfer', 'hausdorff'):
+        raise ValueError('%s: mode must be one of %s, got %r' % (who, EVALUATION_MODES, mode))
+    if isinstance(samples, bool) or not isinstance(samples, int) or samples < 0:
+        raise ValueError('%s: samples must be a non-negative integer, got %r' % (who, samples))
+    if outvertices.dim() != 2 or refvertices.dim() != 2 or outvertices.shape[-1] != 3 or refvertices.shape[-1] != 3:
+        raise ValueError('%s: expected two (V, 3) vertex tensors, got %s and %s' % (who, tuple(outvertices.shape), tuple(refvertices.shape)))
+    if mode == 'point2mesh':
+        return compute_distance(outvertices, refvertices, reffaces)
+    with torch.no_grad():
+        out, ref = outvertices.detach()[None], refvertices.detach().to(device=outvertices.device, dtype=outvertices.dtype)[None]
+        if mode == 'point2point':
+            if out.shape != ref.shape:
+                raise ValueError('%s: point2point needs two meshes of one shape, got %s and %s' % (who, tuple(out.shape[1:]), tuple(ref.shape[1:])))
+            diff = (out - ref).double()
+            return float((diff * diff).sum(-1).mean())
+        if samples:
+            from .sampling import sample_points
+            u = torch.rand((2, 1, samples, 3), generator=torch.Generator().manual_seed(seed)).to(device=out.device, dtype=out.dtype)
+            out, ref = sample_points(out, reffaces, uniforms=u[0])[0], sample_points(ref, reffaces, uniforms=u[1])[0]
+        if mode == 'chamfer':
+            return float(chamfer_distance(out, ref)[0])
+        if mode == 'hausdorff':
+            return float(hausdorff_distance(out, ref)[0])
+        return float(f_score(ref, out, radius=radius)[0])

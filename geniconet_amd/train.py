@@ -91,6 +91,14 @@ def build_criterion(params, device):
             crit = losses.Surface_Loss(ico['subdivisions'], **kw)
         else:
             crit = losses.SurfaceKLD_Loss(ico['subdivisions'], factor_kl=1., **kw)
+    elif loss_kind in ('chamfer', 'chamferkld'):
+        # the chamfer criterion (losses.Chamfer_Loss; the reference names a CustomChamfer loss and does not ship it): optional keys
+        kw = dict(samples=ico.get('surface_samples', 0), sample_seed=ico.get('surface_sample_seed', 0),
+                  w1=ico.get('chamfer_w1', 1.0), w2=ico.get('chamfer_w2', 1.0))
+        if loss_kind == 'chamfer':
+            crit = losses.Chamfer_Loss(ico['subdivisions'], **kw)
+        else:
+            crit = losses.ChamferKLD_Loss(ico['subdivisions'], factor_kl=1., **kw)
     else:
         raise ValueError('loss for %s model not specified' % params['model_name'])
     return crit.to(device)
