@@ -133,23 +133,9 @@ EXTENSION_HEADERS = {
     'icn_isect.h': {                   # self-intersection count of meshes
         'icn_mesh_self_intersect': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 3 + [_c_float_p, ctypes.c_void_p], RC),
     },
-}
-
-# Headers added after tests/test_abi_mesh.py fixed the set of EXTENSION_HEADERS and the names in each: the same shape (header ->
-# {entry: (restype, argtypes, reply)}), the same conventions, the same library, and each mirrors its header one to one -- but each
-# header here has an ABI test file of its own (icn_sdf.h: tests/test_abi_sdf.py).  lib() binds these with the tables above in one
-# loop and source_files() hashes their headers too.
-LATER_HEADERS = {
     'icn_sdf.h': {                     # sign of the point-to-mesh distance
         'icn_point_to_mesh_sign': (ctypes.c_int, [_c_float_p] * 8 + [ctypes.c_int] * 4 + [_c_float_p, ctypes.c_void_p], RC),
     },
-}
-
-
-# Every header after those: the same shape, conventions and library, bound in the same loop of lib() and hashed by source_files().
-# This table ends the chain of tables: NO TEST MAY FIX ITS KEY SET.  A new header is one more key here and one more ABI test file that
-# names only its own header (icn_voxel.h: tests/test_abi_voxel.py, icn_raycast.h: tests/test_abi_raycast.py, icn_nn.h: tests/test_abi_nn.py), so adding a header never needs another table.
-UNPINNED_HEADERS = {
     'icn_voxel.h': {                   # solid voxelisation by ray parity
         'icn_mesh_voxelize': (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_double] * 4 + [ctypes.c_int] * 3
                               + [ctypes.c_void_p, ctypes.c_void_p], RC),
@@ -202,7 +188,7 @@ def lib():
                 '(or `make -C geniconet_amd/csrc`).' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
         checked = types.SimpleNamespace()
-        for name, (res, args, reply) in [item for table in (SIGNATURES, *EXTENSION_HEADERS.values(), *LATER_HEADERS.values(), *UNPINNED_HEADERS.values()) for item in table.items()]:
+        for name, (res, args, reply) in [item for table in (SIGNATURES, *EXTENSION_HEADERS.values()) for item in table.items()]:
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             fn = handle[name]            # a function object of its own (handle.name is cached, handle[name] is not)
@@ -266,9 +252,9 @@ def set_arith(mode):
 
 def source_files():
     """The files source_sha256() hashes, sorted: the kernel / library sources under csrc/, include/icn.h and every header of
-    EXTENSION_HEADERS, LATER_HEADERS and UNPINNED_HEADERS."""
+    EXTENSION_HEADERS."""
     import glob
-    headers = [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('icn.h', *EXTENSION_HEADERS, *LATER_HEADERS, *UNPINNED_HEADERS)]
+    headers = [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('icn.h', *EXTENSION_HEADERS)]
     return sorted([f for pattern in ('*.hip', '*.h', '*.cpp') for f in glob.glob(os.path.join(_HERE, 'csrc', pattern))] + headers)
 
 

@@ -30,9 +30,8 @@ namespace icn {
 namespace {
 
 constexpr int ISECT_WORDS = 19;              // 9 coordinates, 3 ids, box lo / hi, valid: odd, so the fills are conflict-free
-constexpr int ISECT_ID = 9, ISECT_LO = 12, ISECT_HI = 15, ISECT_VALID = 18;
+constexpr int ISECT_LO = FACE_WORDS, ISECT_HI = 15, ISECT_VALID = 18;
 
-__device__ __forceinline__ d3 widened(f3 p) { return {(double)p.x, (double)p.y, (double)p.z}; }
 __device__ __forceinline__ d3 pick(bool first, d3 a, d3 b) { return {first ? a.x : b.x, first ? a.y : b.y, first ? a.z : b.z}; }
 
 __device__ __forceinline__ double orient(d3 a, d3 b, d3 c, d3 d) {
@@ -59,26 +58,13 @@ __device__ __forceinline__ bool faces_intersect(const d3 (&A)[3], const d3 (&B)[
            crosses(B[2], B[0], b2, b0, A[0], A[1], A[2]);
 }
 
-// One face as a thread loads it: ids, vertices (zeros unless the ids index V vertices), box, valid = ids in range and nine finite
-// coordinates.  f < F.
-struct StagedFace {
-    f3 p[3], lo, hi;
-    int id[3];
-    bool valid;
+// One face as a thread loads it (load_face of icn_mesh_device.h) and its fp32 box.  f < F.
+struct StagedFace : LoadedFace {
+    f3 lo, hi;
 };
 
 __device__ __forceinline__ StagedFace staged_face(const float* __restrict__ v, const int32_t* __restrict__ faces, int f, int V) {
-    StagedFace t;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) t.id[k] = faces[(size_t)f * 3 + k];
-    const bool ok = ids_ok(t.id[0], t.id[1], t.id[2], V);
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        t.p[k] = ok ? load3(v + (size_t)t.id[k] * 3) : f3{0.f, 0.f, 0.f};
-        finite = finite && isfinite(t.p[k].x) && isfinite(t.p[k].y) && isfinite(t.p[k].z);
-    }
-    t.valid = ok && finite;
+    StagedFace t = {load_face(v, faces, f, V), {}, {}};
     t.lo = {fminf(fminf(t.p[0].x, t.p[1].x), t.p[2].x), fminf(fminf(t.p[0].y, t.p[1].y), t.p[2].y), fminf(fminf(t.p[0].z, t.p[1].z), t.p[2].z)};
     t.hi = {fmaxf(fmaxf(t.p[0].x, t.p[1].x), t.p[2].x), fmaxf(fmaxf(t.p[0].y, t.p[1].y), t.p[2].y), fmaxf(fmaxf(t.p[0].z, t.p[1].z), t.p[2].z)};
     return t;
@@ -100,11 +86,7 @@ __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_self_intersect(const float*
         if (f < F) {
             const StagedFace t = staged_face(v, faces, f, V);
             float* e = tile + threadIdx.x * ISECT_WORDS;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                e[3 * k] = t.p[k].x, e[3 * k + 1] = t.p[k].y, e[3 * k + 2] = t.p[k].z;
-                e[ISECT_ID + k] = __int_as_float(t.id[k]);
-            }
+            store_face(e, t);
             e[ISECT_LO] = t.lo.x, e[ISECT_LO + 1] = t.lo.y, e[ISECT_LO + 2] = t.lo.z;
             e[ISECT_HI] = t.hi.x, e[ISECT_HI + 1] = t.hi.y, e[ISECT_HI + 2] = t.hi.z;
             e[ISECT_VALID] = __int_as_float(t.valid ? 1 : 0);
@@ -122,7 +104,7 @@ __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_self_intersect(const float*
                                      (e[ISECT_LO + 1] <= me.hi.y) & (me.lo.z <= e[ISECT_HI + 2]) & (e[ISECT_LO + 2] <= me.hi.z);
                 if (!overlap) continue;
                 // the face itself, invalid faces, shared vertex ids
-                const int j0 = __float_as_int(e[ISECT_ID]), j1 = __float_as_int(e[ISECT_ID + 1]), j2 = __float_as_int(e[ISECT_ID + 2]);
+                const int j0 = __float_as_int(e[FACE_ID]), j1 = __float_as_int(e[FACE_ID + 1]), j2 = __float_as_int(e[FACE_ID + 2]);
                 const bool shared = (j0 == me.id[0]) | (j0 == me.id[1]) | (j0 == me.id[2]) | (j1 == me.id[0]) | (j1 == me.id[1]) |
                                     (j1 == me.id[2]) | (j2 == me.id[0]) | (j2 == me.id[1]) | (j2 == me.id[2]);
                 if (j == i || __float_as_int(e[ISECT_VALID]) == 0 || shared) continue;

@@ -1,5 +1,8 @@
-// Device code shared by the mesh kernels of icn_loss.hip, icn_sample.hip, icn_measure.hip, icn_curvature.hip, icn_gauss.hip, icn_isect.hip and icn_sdf.hip: 3-vectors, the
-// incident face of a per-vertex gather and its corner in double, the pixel <-> vertex rule of the icosahedral grid, fixed-order block reductions, the tiled block scan and the per-record vertex scatter's record set.
+// Device code shared by the mesh kernels of icn_loss.hip, icn_sample.hip, icn_measure.hip, icn_curvature.hip, icn_gauss.hip, icn_isect.hip,
+// icn_sdf.hip, icn_voxel.hip, icn_raycast.hip and icn_nn.hip: 3-vectors, the incident face of a per-vertex gather and its corner in double,
+// one face of a shared face list as a thread loads it and the compacted LDS tile of such faces (for the kernels that sweep all faces),
+// the pixel <-> vertex rule of the icosahedral grid, fixed-order block reductions, the tiled block scan and the per-record vertex
+// scatter's record set.
 // Everything here is inlined into its callers; every sum has a fixed order (bit-identical run to run).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -62,11 +65,81 @@ __device__ __forceinline__ d3 operator-(d3 a, d3 b) { return {a.x - b.x, a.y - b
 __device__ __forceinline__ d3 cross(d3 a, d3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 __device__ __forceinline__ double dot(d3 a, d3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 __device__ __forceinline__ d3 widened(const float* __restrict__ p) { return {(double)p[0], (double)p[1], (double)p[2]}; }
+__device__ __forceinline__ d3 widened(f3 a) { return {(double)a.x, (double)a.y, (double)a.z}; }
+__device__ __forceinline__ bool finite3(f3 a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
+__device__ __forceinline__ int sign_of(double x) { return (x > 0.0) - (x < 0.0); }
 
 // face_normal above in double: no contraction, so that a x a is exactly 0
 __device__ __forceinline__ d3 dnormal(d3 a, d3 b) {
 #pragma clang fp contract(off)
     return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+
+// ---- one face of the shared face list, and a tile of them in LDS --------------------------------------------------------------
+// Face f < F as a thread loads it: ids, vertices (zeros unless the ids index V vertices: nothing is read out of bounds whatever `faces`
+// holds), valid = ids in range and nine finite coordinates.  What a kernel derives from it (a box, a filter) is arithmetic of its own file.
+struct LoadedFace { int id[3]; f3 p[3]; bool valid; };
+
+__device__ __forceinline__ LoadedFace load_face(const float* __restrict__ v, const int32_t* __restrict__ faces, int f, int V) {
+    LoadedFace t = {};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t.id[k] = faces[(size_t)f * 3 + k];
+    if (ids_ok(t.id[0], t.id[1], t.id[2], V)) {                              // the three loads in one region, the tests after them
+#pragma unroll
+        for (int k = 0; k < 3; ++k) t.p[k] = load3(v + (size_t)t.id[k] * 3);
+        t.valid = finite3(t.p[0]) && finite3(t.p[1]) && finite3(t.p[2]);
+    }
+    return t;
+}
+
+// The words every staged face begins with: nine coordinates (vertex k at 3 k), the three ids as bit patterns; then the kernel's own.
+constexpr int FACE_ID = 9, FACE_WORDS = 12;
+
+__device__ __forceinline__ void store_face(float* __restrict__ e, const LoadedFace& t) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        e[3 * k] = t.p[k].x, e[3 * k + 1] = t.p[k].y, e[3 * k + 2] = t.p[k].z;
+        e[FACE_ID + k] = __int_as_float(t.id[k]);
+    }
+}
+
+struct EveryValidFace {
+    __device__ bool operator()(const LoadedFace&) const { return true; }
+};
+
+// Stages faces f0 .. f0 + MESH_BLOCK of the list (those below F) into `tile`, entries of WORDS floats (odd, so that the fill touches
+// every bank once), one face per thread; every thread of the block calls it.  A face stays iff it is valid and keep_if(face) holds; the
+// others are dropped and the survivors compacted by ballot and popcount: a wave's count through wave_count[], the waves before it summed
+// in wave order.  No atomics, and THE SURVIVORS KEEP THE ASCENDING ORDER OF THEIR FACE INDEX: k_mesh_raycast's rule for equal
+// parameters (the lowest index wins by `t < best` alone) rests on it.  fill(face, f, entry) writes the words from FACE_WORDS on.  Opens
+// with the barrier that ends the readers of the tile's previous contents, closes with the one that publishes this one -> entries staged.
+template <int WORDS, class Fill, class Keep = EveryValidFace>
+__device__ __forceinline__ int stage_face_tile(float* tile, int (&wave_count)[MESH_BLOCK / 64], const float* __restrict__ v,
+                                               const int32_t* __restrict__ faces, int f0, int F, int V, Fill fill, Keep keep_if = Keep()) {
+    static_assert(WORDS >= FACE_WORDS && WORDS % 2 == 1, "an entry holds the common words and has an odd stride");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();
+    const int f = f0 + threadIdx.x;                                          // F <= 0x7fffffff / 3: no overflow
+    LoadedFace t = {};
+    if (f < F) t = load_face(v, faces, f, V);
+    const bool keep = t.valid && keep_if(t);
+    const unsigned long long kept = __ballot(keep);
+    if (lane == 0) wave_count[wave] = __popcll(kept);
+    __syncthreads();
+    int before = 0, nf = 0;
+#pragma unroll
+    for (int w = 0; w < MESH_BLOCK / 64; ++w) {
+        const int n = wave_count[w];
+        before += w < wave ? n : 0;
+        nf += n;
+    }
+    if (keep) {
+        float* e = tile + (before + __popcll(kept & ((1ull << lane) - 1ull))) * WORDS;
+        store_face(e, t);
+        fill(t, f, e);
+    }
+    __syncthreads();
+    return nf;
 }
 
 // the vertex ids of corners k + 1 and k + 2 of an incident face (selects, not a runtime index into registers)

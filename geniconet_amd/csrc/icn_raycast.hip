@@ -18,9 +18,10 @@
 //   count = the number of hits, face = the hit of smallest t (the lowest face index among equal t; -1 if none), depth = (float)t of
 //   that face, else +inf.  The products of fp32 values stay far inside the range of a double (|s c| < 1e194), so a NaN arises only as
 //   0 / 0 and is no hit: no NaN ever comes out.
-// k_mesh_raycast: grid (ceil(R / MESH_BLOCK), B), one thread per ray.  Faces are staged through LDS in tiles of MESH_BLOCK as
-// k_mesh_voxelize stages them; a face that is not TESTED is dropped while staging and the survivors are compacted by ballot and
-// popcount, which keeps them in ascending face order: `t < best` alone gives the lowest index among equal t.  An entry is nine
+// k_mesh_raycast: grid (ceil(R / MESH_BLOCK), B), one thread per ray.  Faces are staged through LDS in tiles of MESH_BLOCK in the
+// sequence of stage_face_tile (icn_mesh_device.h), written out here: through the shared template this kernel measured 1 - 2 % slower on
+// rays aimed at the vertices, more than the spread of three runs (profiles/mesh_face_tile.txt).  A face that is not TESTED is dropped
+// while staging and the survivors are compacted by ballot and popcount, which keeps them in ascending face order: `t < best` alone gives the lowest index among equal t.  An entry is nine
 // coordinates, three ids, the face index and the eight words of the filter below, 21 words -- odd, so the fill touches every bank once;
 // the reads are broadcasts.  Each thread keeps (best t, best face, count) in registers and writes its three outputs once, misses and
 // dead rays too.  No atomics, no workspace, safe whatever `faces` holds, bit-identical run to run and equal to the float64 formulation
@@ -81,10 +82,8 @@
 namespace icn {
 namespace {
 
-constexpr int RAY_ID = 9, RAY_FACE = 12, RAY_CENTRE = 13, RAY_R2 = 16, RAY_NORMAL = 17, RAY_K = 20;   // words of a staged face
+constexpr int RAY_FACE = FACE_WORDS, RAY_CENTRE = 13, RAY_R2 = 16, RAY_NORMAL = 17, RAY_K = 20;   // after the common words
 constexpr int RAY_WORDS = 21;               // 9 coordinates, 3 ids, the face index, c, R2, nh, K: odd, so the fills are conflict-free
-
-__device__ __forceinline__ int sign_of(double x) { return (x > 0.0) - (x < 0.0); }
 
 // the raw value s and the decided sign tau of the directed edge u -> w for direction d, evaluated on its ends in the order of their ids
 __device__ __forceinline__ void ray_edge(int iu, int iw, d3 pu, d3 pw, d3 d, double& s, int& tau) {
@@ -100,8 +99,6 @@ __device__ __forceinline__ void ray_edge(int iu, int iw, d3 pu, d3 pw, d3 d, dou
     tau = as_given ? sign : -sign;
 }
 
-__device__ __forceinline__ bool finite3(f3 a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
-__device__ __forceinline__ d3 widened3(f3 a) { return {(double)a.x, (double)a.y, (double)a.z}; }
 __device__ __forceinline__ double dot_in_order(d3 a, d3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 
 template <bool CULL>
@@ -115,10 +112,10 @@ __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_raycast(const float* __rest
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.y, r = blockIdx.x * MESH_BLOCK + tid;
     const float* v = vts + (size_t)b * V * 3;
-    const size_t at = (size_t)b * R + (r < R ? r : 0);                       // threads past R read ray 0 of the mesh and write nothing
+    const size_t at = (size_t)b * R + (r < R ? r : 0);                      // threads past R read ray 0 of the mesh and write nothing
     const f3 o32 = load3(org + at * 3), d32 = load3(dir + at * 3);
     const bool live = r < R && finite3(o32) && finite3(d32) && !(d32.x == 0.f && d32.y == 0.f && d32.z == 0.f);
-    const d3 o = widened3(o32), d = widened3(d32);
+    const d3 o = widened(o32), d = widened(d32);
     const double dd = dot_in_order(d, d);
     f3 u32 = {0.f, 0.f, 0.f};
     if (CULL) {
@@ -160,13 +157,13 @@ __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_raycast(const float* __rest
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 e[3 * c] = p[c].x, e[3 * c + 1] = p[c].y, e[3 * c + 2] = p[c].z;
-                e[RAY_ID + c] = __int_as_float(id[c]);
+                e[FACE_ID + c] = __int_as_float(id[c]);
             }
             e[RAY_FACE] = __int_as_float(f);
             if (CULL) {                                                      // the filter's eight words, in double, rounded once
-                const d3 q0 = widened3(p[0]), q1 = widened3(p[1]), q2 = widened3(p[2]);
+                const d3 q0 = widened(p[0]), q1 = widened(p[1]), q2 = widened(p[2]);
                 const f3 c = {(float)((q0.x + q1.x + q2.x) / 3.0), (float)((q0.y + q1.y + q2.y) / 3.0), (float)((q0.z + q1.z + q2.z) / 3.0)};
-                const d3 cd = widened3(c), e01 = q1 - q0, e02 = q2 - q0, e12 = q2 - q1;
+                const d3 cd = widened(c), e01 = q1 - q0, e02 = q2 - q0, e12 = q2 - q1;
                 const double rr = fmax(fmax(dot(q0 - cd, q0 - cd), dot(q1 - cd, q1 - cd)), dot(q2 - cd, q2 - cd));
                 const double ll = fmax(fmax(dot(e01, e01), dot(e02, e02)), dot(e12, e12));
                 const d3 n = dnormal(e01, e02);
@@ -191,7 +188,7 @@ __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_raycast(const float* __rest
                 const bool far = (mm >= 0x1p-100f) & (fmaf(-along, along, mm) > fmaf(0x1p-18f, mm, e[RAY_R2]));
                 if (far & (steep * e[RAY_K] > mm + e[RAY_R2])) continue;     // FAR and STEEP: proved not to cover (the head of this file)
             }
-            const int i0 = __float_as_int(e[RAY_ID]), i1 = __float_as_int(e[RAY_ID + 1]), i2 = __float_as_int(e[RAY_ID + 2]);
+            const int i0 = __float_as_int(e[FACE_ID]), i1 = __float_as_int(e[FACE_ID + 1]), i2 = __float_as_int(e[FACE_ID + 2]);
             const d3 p0 = {(double)e[0] - o.x, (double)e[1] - o.y, (double)e[2] - o.z};
             const d3 p1 = {(double)e[3] - o.x, (double)e[4] - o.y, (double)e[5] - o.z};
             const d3 p2 = {(double)e[6] - o.x, (double)e[7] - o.y, (double)e[8] - o.z};

@@ -13,9 +13,9 @@
 //     x = (s0 v0.x + s1 v1.x + s2 v2.x) / (s0 + s1 + s2),  tau = (x - origin_x) / h - 0.5, dropped if not finite, k0 = clamp(ceil(tau), 0, n0)
 //   cell i of the column is occupied iff the number of crossings with k0 <= i is odd.
 // k_mesh_voxelize: grid (tiles of columns, B), one thread per column, a workgroup of MESH_BLOCK threads covers VOX_TJ x VOX_TK columns
-// (j, k) with k fastest, as the output has it.  Faces are staged through LDS in tiles of MESH_BLOCK as k_mesh_self_intersect stages
-// them; while staging, a face that no column of the workgroup would test -- invalid, or its (y, z) box misses the box of the tile's
-// columns, which is exact because py and pz are monotone in j and k -- is dropped and the survivors are compacted by ballot and
+// (j, k) with k fastest, as the output has it.  Faces are staged through LDS in tiles of MESH_BLOCK by stage_face_tile
+// (icn_mesh_device.h); while staging, a face that no column of the workgroup would test -- invalid, or its (y, z) box misses the box of
+// the tile's columns, which is exact because py and pz are monotone in j and k -- is dropped and the survivors are compacted by ballot and
 // popcount (a fixed order, no atomics).  An entry is VOX_WORDS = 17 words -- nine coordinates, three ids, the (y, z) box, one of padding
 // -- odd, so the fill touches every bank once; the reads are broadcasts.  The box test of the hot loop is four fp32 compares: for a
 // float l and a double p, l <= p iff l <= the largest float <= p, and p <= l iff the smallest float >= p <= l.
@@ -38,7 +38,7 @@ namespace {
 constexpr int VOX_TJ = 16, VOX_TK = 16;     // the workgroup's tile of columns, k fastest
 static_assert(VOX_TJ * VOX_TK == MESH_BLOCK, "one thread per column of the tile");
 constexpr int VOX_WORDS = 17;               // 9 coordinates, 3 ids, lo_y hi_y lo_z hi_z, 1 of padding: odd, so the fills are conflict-free
-constexpr int VOX_ID = 9, VOX_BOX = 12;
+constexpr int VOX_BOX = FACE_WORDS;
 constexpr int VOX_BITS = VOXEL_MAX_DEPTH / 32;
 
 struct VoxLattice {
@@ -72,13 +72,20 @@ __device__ __forceinline__ void edge_value(int iu, int iw, double uy, double uz,
     t = as_given ? sign : -sign;
 }
 
+// the fp32 (y, z) box of a face: min / max of fp32 values are exact
+struct YZBox { float lo_y, hi_y, lo_z, hi_z; };
+__device__ __forceinline__ YZBox yz_box(const LoadedFace& t) {
+    return {fminf(fminf(t.p[0].y, t.p[1].y), t.p[2].y), fmaxf(fmaxf(t.p[0].y, t.p[1].y), t.p[2].y),
+            fminf(fminf(t.p[0].z, t.p[1].z), t.p[2].z), fmaxf(fmaxf(t.p[0].z, t.p[1].z), t.p[2].z)};
+}
+
 template <bool CULL>
 __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_voxelize(const float* __restrict__ vts, const int32_t* __restrict__ faces, int V, int F,
                                                                VoxLattice L, uint8_t* __restrict__ occ) {
     __shared__ float tile[MESH_BLOCK * VOX_WORDS];
     __shared__ uint32_t bits[VOX_BITS * MESH_BLOCK];
     __shared__ int wave_count[MESH_BLOCK / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int b = blockIdx.y, tj = blockIdx.x / L.tiles_k, tk = blockIdx.x - tj * L.tiles_k;
     const int j0 = tj * VOX_TJ, k0 = tk * VOX_TK;
     const int j = j0 + tid / VOX_TK, k = k0 + tid % VOX_TK;
@@ -92,54 +99,24 @@ __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_voxelize(const float* __res
     const int words = (L.n0 + 31) >> 5;
     for (int w = 0; w < words; ++w) bits[w * MESH_BLOCK + tid] = 0u;         // thread-private: no barrier needed
     for (int f0 = 0; f0 < F; f0 += MESH_BLOCK) {
-        __syncthreads();
-        const int f = f0 + tid;                                              // F <= 0x7fffffff / 3: no overflow
-        int id[3] = {0, 0, 0};
-        f3 p[3] = {};
-        bool keep = false;
-        float lo_y = 0.f, hi_y = 0.f, lo_z = 0.f, hi_z = 0.f;
-        if (f < F) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) id[c] = faces[(size_t)f * 3 + c];
-            if (ids_ok(id[0], id[1], id[2], V)) {
-                keep = true;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    p[c] = load3(v + (size_t)id[c] * 3);
-                    keep = keep && isfinite(p[c].x) && isfinite(p[c].y) && isfinite(p[c].z);
-                }
-                lo_y = fminf(fminf(p[0].y, p[1].y), p[2].y), hi_y = fmaxf(fmaxf(p[0].y, p[1].y), p[2].y);
-                lo_z = fminf(fminf(p[0].z, p[1].z), p[2].z), hi_z = fmaxf(fmaxf(p[0].z, p[1].z), p[2].z);
-                if (CULL) keep = keep && (lo_y <= ty_below) && (ty_above <= hi_y) && (lo_z <= tz_below) && (tz_above <= hi_z);
-            }
-        }
-        const unsigned long long kept = __ballot(keep);
-        if (lane == 0) wave_count[wave] = __popcll(kept);
-        __syncthreads();
-        int before = 0, nf = 0;
-#pragma unroll
-        for (int w = 0; w < MESH_BLOCK / 64; ++w) {
-            const int n = wave_count[w];
-            before += w < wave ? n : 0;
-            nf += n;
-        }
-        if (keep) {
-            float* e = tile + (before + __popcll(kept & ((1ull << lane) - 1ull))) * VOX_WORDS;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                e[3 * c] = p[c].x, e[3 * c + 1] = p[c].y, e[3 * c + 2] = p[c].z;
-                e[VOX_ID + c] = __int_as_float(id[c]);
-            }
-            e[VOX_BOX] = lo_y, e[VOX_BOX + 1] = hi_y, e[VOX_BOX + 2] = lo_z, e[VOX_BOX + 3] = hi_z;
-        }
-        __syncthreads();
+        const int nf = stage_face_tile<VOX_WORDS>(
+            tile, wave_count, v, faces, f0, F, V,
+            [](const LoadedFace& t, int, float* e) {
+                const YZBox box = yz_box(t);
+                e[VOX_BOX] = box.lo_y, e[VOX_BOX + 1] = box.hi_y, e[VOX_BOX + 2] = box.lo_z, e[VOX_BOX + 3] = box.hi_z;
+            },
+            [&](const LoadedFace& t) {                                       // a face whose (y, z) box misses the tile's columns is dropped
+                if (!CULL) return true;
+                const YZBox box = yz_box(t);
+                return (box.lo_y <= ty_below) && (ty_above <= box.hi_y) && (box.lo_z <= tz_below) && (tz_above <= box.hi_z);
+            });
         if (!live) continue;
         for (int jj = 0; jj < nf; ++jj) {
             const float* e = tile + jj * VOX_WORDS;
             const bool tested = (e[VOX_BOX] <= py_below) & (py_above <= e[VOX_BOX + 1]) & (e[VOX_BOX + 2] <= pz_below) &
                                 (pz_above <= e[VOX_BOX + 3]);
             if (!tested) continue;
-            const int i0 = __float_as_int(e[VOX_ID]), i1 = __float_as_int(e[VOX_ID + 1]), i2 = __float_as_int(e[VOX_ID + 2]);
+            const int i0 = __float_as_int(e[FACE_ID]), i1 = __float_as_int(e[FACE_ID + 1]), i2 = __float_as_int(e[FACE_ID + 2]);
             const double y0 = e[1], z0 = e[2], y1 = e[4], z1 = e[5], y2 = e[7], z2 = e[8];
             double s0, s1, s2;
             int t0, t1, t2;

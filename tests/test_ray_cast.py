@@ -20,7 +20,7 @@ from geniconet_amd import _lib, metrics
 
 from error_bounds import rho
 from test_signed_distance import _profiled, winding
-from test_voxelize import GPU_MESHES, _broken_cube, _centres, _gpu_mesh, _named, _sphere
+from test_voxelize import GPU_MESHES, SEAMS, _broken_cube, _centres, _gpu_mesh, _named, _seam_mesh, _sphere
 
 INF = float('inf')
 NAN = float('nan')
@@ -589,13 +589,48 @@ def test_hip_equals_the_float64_formulation_bit_for_bit(name, family):
         _same(_through_library(NO_CULL_LIBRARY, oc, dc, vc, fc), want, (name, family, 'no filter'))
 
 
+@functools.lru_cache(maxsize=None)
+def _seam_case():
+    """(origins, directions (3, 257, 3) about the meshes of _seam_mesh, the float64 formulation on its face list, the same on the list
+    without its ten invalid faces with the face indices mapped back to the full list): computed once, shared, never changed."""
+    v, f, kept = _seam_mesh()
+    rays = [_random_rays(v[b], 257, seed=b + 1) for b in range(3)]
+    o, d = torch.stack([r[0] for r in rays]), torch.stack([r[1] for r in rays])
+    return o, d, metrics._torch_ray_cast(o, d, v, f), _mapped(metrics._torch_ray_cast(o, d, v, f[kept]), kept)
+
+
+def _mapped(result, kept):
+    """(depth, face, count) of a cast against faces[kept], its face indices as indices of `faces`."""
+    depth, face, count = result
+    return depth, torch.where(face >= 0, kept.to(face.device)[face.clamp(min=0)], face), count
+
+
+def test_invalid_faces_on_the_seams_of_a_staging_tile_are_faces_removed_in_the_float64_formulation():
+    """An invalid face is not TESTED: by the definition alone the list with it equals the list without it, index for index."""
+    o, d, want, without = _seam_case()
+    assert (want[2] > 0).any() and (want[2] == 0).any() and not torch.isin(want[1], torch.tensor(SEAMS)).any()
+    _same(want, without)
+
+
+@pytest.mark.gpu
+def test_hip_with_invalid_faces_on_the_seams_of_a_staging_tile():
+    """The compaction of the staged tile with holes at both ends of every wave and of the tile: the float64 formulation bit for bit,
+    and the bits of the face list without those faces, whose order the compaction must keep."""
+    v, f, kept = _seam_mesh()
+    o, d, want, _ = _seam_case()
+    oc, dc, vc = o.cuda(), d.cuda(), v.cuda()
+    got = metrics._ray_cast_unchecked(oc, dc, vc, f.cuda())
+    _same(got, want)
+    _same(got, _mapped(metrics._ray_cast_unchecked(oc, dc, vc, f[kept].cuda()), kept))
+
+
 NO_CULL_LIBRARY = os.environ.get('ICN_RAYCAST_NO_CULL_LIB')                   # a libicn.so built with -DICN_RAYCAST_NO_CULL (tools/time_raycast.py)
 
 
 def _through_library(path, o, d, v, f):
     """icn_mesh_raycast of another build of the library on contiguous device tensors -> (depth, face int64, count)."""
     import ctypes
-    res, argtypes, _ = _lib.UNPINNED_HEADERS['icn_raycast.h']['icn_mesh_raycast']
+    res, argtypes, _ = _lib.EXTENSION_HEADERS['icn_raycast.h']['icn_mesh_raycast']
     fn = ctypes.CDLL(path).icn_mesh_raycast
     fn.restype, fn.argtypes = res, argtypes
     B, R = o.shape[:2]

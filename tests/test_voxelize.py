@@ -360,6 +360,54 @@ def test_hip_equals_the_float64_formulation_byte_for_byte(name, group):
     assert filled > 0
 
 
+SEAMS = (0, 63, 64, 65, 127, 128, 255, 256, 257, 319)                         # the ends of the waves of a staging tile, and of the tile
+
+
+@functools.lru_cache(maxsize=None)
+def _seam_mesh():
+    """(vertices (3, V, 3), faces (320, 3) int32, the indices of the faces left valid): the noisy I2 -- one full staging tile of the
+    kernels that sweep all faces and a partial one -- with the faces at SEAMS made invalid, in turn by an id outside [0, V) (-1, then
+    V) and by a reference to the appended vertex V - 1, which is NaN and which no other face uses."""
+    v, f = _gpu_mesh('F320')
+    v = torch.cat([v, torch.full((len(SCALES), 1, 3), float('nan'))], 1)
+    V, f = v.shape[1], f.clone()
+    assert len(f) == 320 and int(f.max()) == V - 2
+    for n, i in enumerate(SEAMS):
+        f[i, n % 3] = V - 1 if n % 2 else (-1, V)[n // 2 % 2]
+    return v, f, torch.tensor([i for i in range(len(f)) if i not in SEAMS])
+
+
+@functools.lru_cache(maxsize=None)
+def _seam_case():
+    """(lattice of (33, 17, 18) cells over the first mesh, the float64 formulation on the face list of _seam_mesh, the same on the list
+    without its ten invalid faces): computed once, shared, never changed."""
+    v, f, kept = _seam_mesh()
+    counts = (33, 17, 18)
+    lo, hi = (x.double() for x in v[0, :-1].aminmax(dim=0))
+    h = 1.1 * float(((hi - lo)[1:] / torch.tensor(counts[1:])).max())
+    lattice = (tuple(float((lo + hi)[k]) / 2 - counts[k] * h / 2 for k in range(3)), h, counts)
+    return lattice, metrics._torch_voxelize(v, f, *lattice), metrics._torch_voxelize(v, f[kept], *lattice)
+
+
+def test_invalid_faces_on_the_seams_of_a_staging_tile_are_faces_removed_in_the_float64_formulation():
+    """An invalid face is not TESTED: by the definition alone the list with it equals the list without it."""
+    lattice, want, without = _seam_case()
+    assert want.shape == (3, 33, 17, 18) and want.any() and not want.all()
+    assert torch.equal(want, without)
+
+
+@pytest.mark.gpu
+def test_hip_with_invalid_faces_on_the_seams_of_a_staging_tile():
+    """The compaction of the staged tile with holes at both ends of every wave and of the tile: the float64 formulation byte for byte,
+    and the bytes of the face list without those faces."""
+    v, f, kept = _seam_mesh()
+    lattice, want, _ = _seam_case()
+    vc = v.cuda()
+    got = metrics._voxelize_unchecked(vc, f.cuda(), *lattice)
+    assert torch.equal(got.view(torch.uint8).cpu(), want.to(torch.uint8))
+    assert torch.equal(got, metrics._voxelize_unchecked(vc, f[kept].cuda(), *lattice))
+
+
 @pytest.mark.gpu
 def test_hip_on_the_closed_meshes_through_the_checked_function_and_the_aligned_cube():
     v, f = _gpu_mesh('cube')

@@ -121,7 +121,7 @@ say('  %.1f ps a (ray, face) pair; %.1f %% of the pixels covered' % (med_map * 1
 
 if NO_CULL:
     say('3. the forward with and without the reject filter (%s), alternating, device events:' % os.path.basename(NO_CULL))
-    res, argtypes, _ = _lib.UNPINNED_HEADERS['icn_raycast.h']['icn_mesh_raycast']
+    res, argtypes, _ = _lib.EXTENSION_HEADERS['icn_raycast.h']['icn_mesh_raycast']
     entries = {}
     for name, path in (('with the filter', _lib.LIB_PATH), ('without the filter', NO_CULL)):
         fn = ctypes.CDLL(path).icn_mesh_raycast

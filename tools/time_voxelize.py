@@ -128,7 +128,7 @@ say('  %.1f MB of occupancy written, %.0f GB/s of it' % (occupancy.numel() / 1e6
 
 if NO_CULL:
     say('4. the kernel with and without the tile culling of its staging loop (%s), alternating, device events:' % os.path.basename(NO_CULL))
-    res, argtypes, _ = _lib.UNPINNED_HEADERS['icn_voxel.h']['icn_mesh_voxelize']
+    res, argtypes, _ = _lib.EXTENSION_HEADERS['icn_voxel.h']['icn_mesh_voxelize']
     entries = {}
     for name, path in (('with culling', _lib.LIB_PATH), ('without culling', NO_CULL)):
         fn = ctypes.CDLL(path).icn_mesh_voxelize
