@@ -21,6 +21,7 @@
 #include "../../include/icn_voxel.h"
 #include "../../include/icn_raycast.h"
 #include "../../include/icn_nn.h"
+#include "../../include/icn_pairs.h"
 #include "../../include/icn_measure.h"
 #include "icn_geometry.h"
 #include "icn_launch.h"
@@ -800,7 +801,8 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_mesh_angle_defect_fwd", "k_mesh_angle_defect_bwd", "k_mesh_self_intersect", "k_p2m_sign",
                                             "k_mesh_voxelize",
                                             "k_mesh_raycast", "k_mesh_raycast_bwd_record", "k_mesh_raycast_bwd_vertex",
-                                            "k_nn_points", "k_nn_points_bwd_record", "k_nn_points_bwd_vertex"};
+                                            "k_nn_points", "k_nn_points_bwd_record", "k_nn_points_bwd_vertex",
+                                            "k_pair_sums", "k_pair_sums_finish"};
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1663,6 +1665,26 @@ int icn_nearest_points_bwd(const float* points, const float* targets, const int3
         if (dtargets) check_workspace("icn_nearest_points_bwd", ws, ws_bytes, icn::vertex_records_bytes((size_t)B * N));
         icn::launch_nearest_points_bwd(points, targets, idx, ddist, B, N, M, dpoints, dtargets, ws, s);
         ICN_HIP(hipGetLastError());
+    });
+}
+
+// ---- sided sums of every pair of clouds of two sets (include/icn_pairs.h): both set sizes are grid dimensions ---------------------------
+namespace {
+bool sided_sums_sizes_ok(int G, int R, int N, int M) { return nearest_sizes_ok(G, N, M) && R >= 1 && R <= 65535; }   // G is gridDim.z, R gridDim.y
+}  // namespace
+
+size_t icn_sided_sums_workspace_bytes(int G, int R, int N, int M) {
+    return sided_sums_sizes_ok(G, R, N, M) ? icn::sided_sums_workspace_bytes(G, R, N) : 0;
+}
+
+int icn_sided_sums(const float* queries, const float* targets, int G, int R, int N, int M, double* sums, void* ws, size_t ws_bytes,
+                   void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!queries || !targets || !sums) throw std::invalid_argument("icn_sided_sums: null pointer");
+        if (!sided_sums_sizes_ok(G, R, N, M)) throw std::invalid_argument("icn_sided_sums: bad sizes");
+        check_workspace("icn_sided_sums", ws, ws_bytes, icn::sided_sums_workspace_bytes(G, R, N));
+        icn::launch_sided_sums(queries, targets, G, R, N, M, sums, ws, s);
     });
 }
 

@@ -322,6 +322,12 @@ void launch_nearest_points(const float* pts, const float* tgt, int B, int N, int
 void launch_nearest_points_bwd(const float* pts, const float* tgt, const int32_t* idx, const float* ddist, int B, int N, int M,
                                float* dpts, float* dtgt, void* ws, hipStream_t s);
 
+// directed sums of nearest squared distances for every pair of clouds of two sets (icn_pairs.hip; include/icn_pairs.h): the pair is
+// (gridDim.z, gridDim.y), a workgroup sums one chunk of queries in double into ws, a finishing launch adds the chunks of every pair in
+// ascending order.  Two launches on s; ws: sided_sums_workspace_bytes(G, R, N) bytes, 16-byte aligned.
+size_t sided_sums_workspace_bytes(int G, int R, int N);
+void launch_sided_sums(const float* qry, const float* tgt, int G, int R, int N, int M, double* sums, void* ws, hipStream_t s);
+
 // developer routing flags (ICN_DEBUG / icn_set_debug_flags): 16 = convs on k_gather_gemm, 32 = wgrads on k_wgrad,
 // 128 = no stream-K, 256 = fault injection: every stream-K finisher reports its partners lost (tests of the failure path),
 // 512 = masked launches walk tiles b, b + G, ... instead of the balanced tile lists, 1024 = the sparse passes of the decoder-block
@@ -357,6 +363,7 @@ enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA
                 PROF_MESH_VOXELIZE,                                                                 // solid voxelisation by ray parity
                 PROF_MESH_RAYCAST, PROF_MESH_RAYCAST_BWD_RECORD, PROF_MESH_RAYCAST_BWD_VERTEX,      // ray casting and its backward
                 PROF_NN, PROF_NN_BWD_RECORD, PROF_NN_BWD_VERTEX,                                    // nearest-neighbour search and its backward
+                PROF_PAIR_SUMS, PROF_PAIR_SUMS_FINISH,                                              // sided sums of every pair of clouds
                 PROF_KINDS };
 extern const char* const PROF_NAMES[PROF_KINDS];
 void prof_mark_begin(int kind, double flops, hipStream_t s);   // no-ops unless profiling is on

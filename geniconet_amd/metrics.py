@@ -89,6 +89,13 @@ without contraction, the lowest index among equal distances, no atomics; the dis
 icn_nearest_points_bwd, one record per point, then the vertex scatter).  The HIP path reproduces the fp32 formulation bit for bit.
 evaluate_distance gives every test mode of the reference for one mesh pair -- point2point, point2mesh, chamfer, f_<radius> -- and
 hausdorff, on the vertices or on surface samples, where compute_distance keeps the reference's answer (None but for point2mesh).
+
+pairwise_sided_sums, pairwise_chamfer, minimum_matching_distance, coverage, one_nn_accuracy and generation_metrics (below) score a
+GENERATED set of shapes, which has no targets to be paired with: the G x R matrix of chamfer distances between every generated and
+every reference cloud, and the three figures the shape-generation literature reads off it (Achlioptas et al. 2018; Yang et al. 2019):
+MMD-CD, COV-CD and 1-NNA-CD.  The matrix comes from icn_sided_sums (include/icn_pairs.h): a kernel that indexes the pair of clouds
+itself, keeps no index, sums the distances of a pair in double inside the launch and writes one double a pair; its distances are
+those of icn_nearest_points bit for bit.  No gradient.  geniconet_amd/generation.py draws the shapes of ico2ico_vae to score.
 """
 import torch
 
@@ -2067,6 +2074,167 @@ def hausdorff_distance(p1, p2):
     p1, p2 = _check_point_sets('hausdorff_distance', p1, p2)
     d12, d21 = _rooted(_sided_distance_unchecked(p1, p2)[0]), _rooted(_sided_distance_unchecked(p2, p1)[0])
     return torch.maximum(d12.amax(1), d21.amax(1))
+
+
+# ---- every pair of clouds of two sets: the chamfer matrix, and the generation metrics on it -------------------------------------------
+_MAX_CLOUDS = 65535                # clouds a set of the pairwise functions may hold: both set sizes are grid dimensions of k_pair_sums
+
+
+def _check_cloud_sets(who, p1, p2):
+    """The shape checks of two SETS of clouds, whose sizes are independent -> (p1, p2 in p1's dtype and on its device), detached.
+    ValueError.  Shapes only: a zero-stride view of 65536 clouds is rejected without being materialised."""
+    for name, x in (('the first', p1), ('the second', p2)):
+        if not torch.is_tensor(x) or not x.is_floating_point() or x.dim() != 3 or x.shape[-1] != 3 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError('%s: expected %s set as a floating-point (clouds, points, 3) tensor with clouds, points >= 1, got %s'
+                             % (who, name, tuple(x.shape) if torch.is_tensor(x) else type(x).__name__))
+        if x.shape[0] > _MAX_CLOUDS:
+            raise ValueError('%s: %d clouds in %s set: at most %d' % (who, x.shape[0], name, _MAX_CLOUDS))
+        if 3 * x.shape[1] > 0x7fffffff:
+            raise ValueError('%s: %d points: 3 N must fit an int32' % (who, x.shape[1]))
+    return p1.detach(), p2.detach().to(device=p1.device, dtype=p1.dtype)
+
+
+def _torch_pairwise_sided_sums(p1, p2, chunk=_SIDED_CHUNK):
+    """pairwise_sided_sums by the definition in torch, in the dtype of p1: cloud g against a few clouds of p2 at a time through
+    _torch_sided_distance_fwd, the distances converted to double and summed per pair.  Never more than `chunk` (cloud, query, target)
+    triples at once: the queries go in slices of at most `chunk`, as many clouds of p2 at a time as then fit, and the targets are
+    chunked by _torch_sided_distance_fwd itself."""
+    (G, N, _), (R, M, _) = p1.shape, p2.shape
+    sums = torch.zeros(G, R, dtype=torch.float64, device=p1.device)
+    queries = min(N, chunk)
+    clouds = max(1, min(R, chunk // (queries * M)))                                        # 1: the targets are chunked instead
+    for g in range(G):
+        for lo in range(0, N, queries):
+            q = p1[g:g + 1, lo:lo + queries]
+            for r0 in range(0, R, clouds):
+                t = p2[r0:r0 + clouds]
+                dist, _ = _torch_sided_distance_fwd(q.expand(t.shape[0], -1, -1), t, chunk)
+                sums[g, r0:r0 + clouds] += dist.double().sum(1)
+    return sums
+
+
+def _hip_pairwise_sided_sums(qry, tgt):
+    """icn_sided_sums on contiguous fp32 ROCm tensors -> sums (G, R) float64."""
+    (G, N, _), (R, M, _) = qry.shape, tgt.shape
+    L = _lib.api()
+    sums = torch.empty(G, R, dtype=torch.float64, device=qry.device)
+    ws_bytes = L.icn_sided_sums_workspace_bytes(G, R, N, M)
+    ws = _lib.workspace(ws_bytes, qry.device)
+    with torch.cuda.device(qry.device):
+        L.icn_sided_sums(qry.data_ptr(), tgt.data_ptr(), G, R, N, M, sums.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream())
+    return sums
+
+
+def _pairwise_sided_sums_unchecked(p1, p2):
+    """pairwise_sided_sums after its checks: detached tensors of one dtype on one device; no host synchronisation."""
+    if _on_hip_path(p1) and p2.dtype == torch.float32:
+        return _hip_pairwise_sided_sums(p1.contiguous(), p2.contiguous())
+    return _torch_pairwise_sided_sums(p1, p2)
+
+
+def pairwise_sided_sums(p1, p2):
+    """sums (G, R) float64 of two SETS of clouds p1 (G, N, 3) and p2 (R, M, 3): sums[g, r] = sum_i sided_distance(p1[g], p2[r])_i, the
+    sum over the points of cloud g of the squared distance to the nearest point of cloud r, for EVERY pair -- where sided_distance pairs
+    cloud b with cloud b.  G, R, N and M are independent; G, R <= 65535.  No gradient: the inputs are detached.
+
+    Every distance is the `dist` of sided_distance, bit for bit (fp32 on the device, every product and sum rounded on its own, a NaN
+    distance passed over, +inf where a point has no acceptable target); the distances of a pair are converted to double, which is
+    exact, and summed in double in a fixed order.  Every term is >= 0, so no NaN comes out, and a single +inf distance makes the
+    entry exactly +inf.  Against the same distances summed in another order, |difference| <= N 2^-53 sum on either side.
+    ROCm fp32 tensors run on icn_sided_sums (include/icn_pairs.h): the kernel indexes the pair itself, keeps no index, reduces in the
+    launch and writes one double a pair -- nothing of size G R N is ever held, where sided_distance on repeat_interleave / repeat copies
+    reads G R (N + M) 12 bytes and writes G R N 8; two launches, no atomics, bit-identical run to run, and entry (g, r) does not depend
+    on G, R or the position of the two clouds.  ICN_NO_HIP_LOSS=1, CPU tensors and other dtypes take _torch_pairwise_sided_sums, which
+    never holds more than _SIDED_CHUNK (cloud, query, target) triples.  Shapes are checked (ValueError); nothing is read back."""
+    return _pairwise_sided_sums_unchecked(*_check_cloud_sets('pairwise_sided_sums', p1, p2))
+
+
+def pairwise_chamfer(p1, p2, w1=1.0, w2=1.0, squared=True):
+    """(G, R) in the dtype of p1: the chamfer distance of EVERY pair of clouds of p1 (G, N, 3) and p2 (R, M, 3),
+        d[g, r] = w1 pairwise_sided_sums(p1, p2)[g, r] / N + w2 pairwise_sided_sums(p2, p1)[r, g] / M,
+    computed in double and rounded once: chamfer_distance(p1[g:g+1], p2[r:r+1]) for all g and r.  The distance matrix that
+    minimum_matching_distance, coverage and one_nn_accuracy take.  No gradient.
+    squared=False (the root of every distance before the mean) is NOT SUPPORTED on the fused path, because the root has to be taken
+    per point before the sum: it is defined, and computed by chamfer_distance(squared=False) of cloud g against every cloud of p2, one
+    g at a time -- G calls that each hold R copies of one cloud."""
+    p1, p2 = _check_cloud_sets('pairwise_chamfer', p1, p2)
+    if not squared:
+        with torch.no_grad():
+            return torch.stack([_chamfer_unchecked(p1[g:g + 1].expand(p2.shape[0], -1, -1), p2, w1, w2, False) for g in range(p1.shape[0])])
+    d = w1 * _pairwise_sided_sums_unchecked(p1, p2) / p1.shape[1] + w2 * _pairwise_sided_sums_unchecked(p2, p1).t() / p2.shape[1]
+    return d.to(p1.dtype)
+
+
+def _check_distance_matrix(who, d, name='d', shape=None):
+    if not torch.is_tensor(d) or not d.is_floating_point() or d.dim() != 2 or d.shape[0] < 1 or d.shape[1] < 1:
+        raise ValueError('%s: expected %s as a floating-point (G, R) distance matrix with G, R >= 1, got %s'
+                         % (who, name, tuple(d.shape) if torch.is_tensor(d) else type(d).__name__))
+    if shape is not None and tuple(d.shape) != tuple(shape):
+        raise ValueError('%s: expected %s of shape %s, got %s' % (who, name, tuple(shape), tuple(d.shape)))
+    return d.detach()
+
+
+def _lowest_argmin(d):
+    """(minimum, index) along the last dimension of d over its acceptable entries -- those < +inf: no NaN, no +inf -- THE LOWEST INDEX
+    AMONG EQUAL MINIMA, written out with the masked amin of _torch_sided_distance_fwd (argmin on the device promises no tie rule).
+    A row without an acceptable entry answers (+inf, n), n its length."""
+    n = d.shape[-1]
+    ok = d < float('inf')
+    d = torch.where(ok, d, torch.full_like(d, float('inf')))
+    nearest = d.amin(-1)
+    index = torch.arange(n, device=d.device).expand_as(d)
+    return nearest, torch.where(ok & (d == nearest[..., None]), index, torch.full_like(index, n)).amin(-1)
+
+
+def minimum_matching_distance(d):
+    """MMD of a distance matrix d (G, R), generated shapes by reference shapes (Achlioptas et al. 2018): the mean over the reference
+    shapes r of min_g d[g, r], how far the nearest generated shape is from each reference shape.  A 0-dim tensor in the dtype of d,
+    the mean taken in double.  NaN and +inf entries are never a minimum; a reference shape without a finite distance contributes +inf."""
+    d = _check_distance_matrix('minimum_matching_distance', d)
+    return _lowest_argmin(d.t())[0].double().mean().to(d.dtype)
+
+
+def coverage(d):
+    """COV of a distance matrix d (G, R): #unique{argmin_r d[g, r] : g} / R, the share of the reference shapes that are the nearest
+    reference shape of some generated shape.  Among equally near reference shapes the lowest index is the match; a generated shape
+    without a finite distance matches none.  A 0-dim float64 tensor; nothing is read back."""
+    d = _check_distance_matrix('coverage', d)
+    R = d.shape[1]
+    match = _lowest_argmin(d)[1]                                                           # R: no match
+    hit = torch.zeros(R + 1, dtype=torch.bool, device=d.device)
+    hit[match] = True
+    return hit[:R].sum().double() / R
+
+
+def one_nn_accuracy(d_gg, d_gr, d_rr):
+    """1-NNA of the distance matrices generated x generated (G, G), generated x reference (G, R) and reference x reference (R, R): the
+    accuracy of the leave-one-out 1-nearest-neighbour classifier on the merged set, generated shapes first, then reference shapes
+    (Yang et al. 2019).  Every element looks for its nearest OTHER element (the diagonal is excluded; the lowest merged index among
+    equally near ones) and is right when that neighbour carries its own label; an element without a finite distance to anyone
+    counts as wrong.  0.5 is the ideal (the sets cannot be told apart), 1 the worst.  Row g of the merged matrix is
+    (d_gg[g], d_gr[g]), row G + r is (d_gr[:, r], d_rr[r]).  A 0-dim float64 tensor; nothing is read back."""
+    who = 'one_nn_accuracy'
+    d_gr = _check_distance_matrix(who, d_gr, 'd_gr')
+    G, R = d_gr.shape
+    d_gg, d_rr = _check_distance_matrix(who, d_gg, 'd_gg', (G, G)), _check_distance_matrix(who, d_rr, 'd_rr', (R, R))
+    d_gg, d_rr = d_gg.to(device=d_gr.device, dtype=d_gr.dtype), d_rr.to(device=d_gr.device, dtype=d_gr.dtype)
+    merged = torch.cat([torch.cat([d_gg, d_gr], 1), torch.cat([d_gr.t(), d_rr], 1)], 0)
+    own = torch.eye(G + R, dtype=torch.bool, device=merged.device)
+    neighbour = _lowest_argmin(torch.where(own, torch.full_like(merged, float('inf')), merged))[1]      # G + R: none
+    generated = torch.arange(G + R, device=merged.device) < G
+    right = torch.where(generated, neighbour < G, (neighbour >= G) & (neighbour < G + R))
+    return right.sum().double() / (G + R)
+
+
+def generation_metrics(generated, reference):
+    """dict(mmd=, cov=, one_nna=) of Python floats for a set of generated clouds (G, N, 3) against a set of reference clouds (R, M, 3):
+    minimum_matching_distance and coverage of pairwise_chamfer(generated, reference), one_nn_accuracy with the two within-set matrices
+    as well.  Three pairwise_chamfer calls (squared distances, unit weights) and one read-back at the end."""
+    generated, reference = _check_cloud_sets('generation_metrics', generated, reference)
+    d_gr = pairwise_chamfer(generated, reference)
+    d_gg, d_rr = pairwise_chamfer(generated, generated), pairwise_chamfer(reference, reference)
+    mmd, cov, nna = torch.stack([minimum_matching_distance(d_gr).double(), coverage(d_gr), one_nn_accuracy(d_gg, d_gr, d_rr)]).tolist()
+    return dict(mmd=mmd, cov=cov, one_nna=nna)
 
 
 def output2vertices(subdivisions, output):
