@@ -22,6 +22,7 @@
 #include "../../include/icn_raycast.h"
 #include "../../include/icn_nn.h"
 #include "../../include/icn_pairs.h"
+#include "../../include/icn_match.h"
 #include "../../include/icn_measure.h"
 #include "icn_geometry.h"
 #include "icn_launch.h"
@@ -802,7 +803,8 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_mesh_voxelize",
                                             "k_mesh_raycast", "k_mesh_raycast_bwd_record", "k_mesh_raycast_bwd_vertex",
                                             "k_nn_points", "k_nn_points_bwd_record", "k_nn_points_bwd_vertex",
-                                            "k_pair_sums", "k_pair_sums_finish"};
+                                            "k_pair_sums", "k_pair_sums_finish",
+                                            "k_match_auction"};
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1685,6 +1687,29 @@ int icn_sided_sums(const float* queries, const float* targets, int G, int R, int
         if (!sided_sums_sizes_ok(G, R, N, M)) throw std::invalid_argument("icn_sided_sums: bad sizes");
         check_workspace("icn_sided_sums", ws, ws_bytes, icn::sided_sums_workspace_bytes(G, R, N));
         icn::launch_sided_sums(queries, targets, G, R, N, M, sums, ws, s);
+    });
+}
+
+// ---- optimal matching of two clouds of one size (include/icn_match.h): one workgroup a pair, R and G are grid dimensions ----------------
+namespace {
+bool match_sizes_ok(int G, int R, int N, int paired, int phases, int max_rounds) {
+    return nearest_sizes_ok(G, N, N) && R >= 1 && R <= 65535 && icn::match_clouds_fits(N) && (paired == 0 || (paired == 1 && G == R)) &&
+           phases >= 1 && phases <= 26 && max_rounds >= 1;
+}
+}  // namespace
+
+size_t icn_match_clouds_workspace_bytes(int G, int R, int N, int paired) {
+    return match_sizes_ok(G, R, N, paired, 1, 1) ? icn::match_clouds_workspace_bytes(G, R, N, paired) : 0;
+}
+
+int icn_match_clouds(const float* queries, const float* targets, int G, int R, int N, int paired, int phases, int max_rounds,
+                     int* match, double* prices, double* cost, int* rounds, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!queries || !targets || !cost || !rounds) throw std::invalid_argument("icn_match_clouds: null pointer");
+        if (!match_sizes_ok(G, R, N, paired, phases, max_rounds)) throw std::invalid_argument("icn_match_clouds: bad sizes");
+        check_workspace("icn_match_clouds", ws, ws_bytes, icn::match_clouds_workspace_bytes(G, R, N, paired));
+        icn::launch_match_clouds(queries, targets, G, R, N, paired, phases, max_rounds, match, prices, cost, rounds, ws, s);
     });
 }
 

@@ -328,6 +328,15 @@ void launch_nearest_points_bwd(const float* pts, const float* tgt, const int32_t
 size_t sided_sums_workspace_bytes(int G, int R, int N);
 void launch_sided_sums(const float* qry, const float* tgt, int G, int R, int N, int M, double* sums, void* ws, hipStream_t s);
 
+// optimal matching of two clouds of one size by an epsilon-scaling auction (icn_match.hip; include/icn_match.h): one workgroup a
+// pair, grid (R, G) or, paired, (1, G); prices and owners in 12 N bytes of LDS (match_clouds_fits(N)), the rest of a pair's state in
+// its slice of ws.  match and prices may be null.  One launch on s; ws: match_clouds_workspace_bytes(G, R, N, paired) bytes, 16-byte
+// aligned.
+bool match_clouds_fits(int N);
+size_t match_clouds_workspace_bytes(int G, int R, int N, int paired);
+void launch_match_clouds(const float* qry, const float* tgt, int G, int R, int N, int paired, int phases, int max_rounds, int* match,
+                         double* prices, double* cost, int* rounds, void* ws, hipStream_t s);
+
 // developer routing flags (ICN_DEBUG / icn_set_debug_flags): 16 = convs on k_gather_gemm, 32 = wgrads on k_wgrad,
 // 128 = no stream-K, 256 = fault injection: every stream-K finisher reports its partners lost (tests of the failure path),
 // 512 = masked launches walk tiles b, b + G, ... instead of the balanced tile lists, 1024 = the sparse passes of the decoder-block
@@ -364,6 +373,7 @@ enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA
                 PROF_MESH_RAYCAST, PROF_MESH_RAYCAST_BWD_RECORD, PROF_MESH_RAYCAST_BWD_VERTEX,      // ray casting and its backward
                 PROF_NN, PROF_NN_BWD_RECORD, PROF_NN_BWD_VERTEX,                                    // nearest-neighbour search and its backward
                 PROF_PAIR_SUMS, PROF_PAIR_SUMS_FINISH,                                              // sided sums of every pair of clouds
+                PROF_MATCH_AUCTION,                                                                 // optimal matching of two clouds
                 PROF_KINDS };
 extern const char* const PROF_NAMES[PROF_KINDS];
 void prof_mark_begin(int kind, double flops, hipStream_t s);   // no-ops unless profiling is on
