@@ -23,6 +23,7 @@
 #include "../../include/icn_nn.h"
 #include "../../include/icn_pairs.h"
 #include "../../include/icn_match.h"
+#include "../../include/icn_fused.h"
 #include "../../include/icn_measure.h"
 #include "icn_geometry.h"
 #include "icn_launch.h"
@@ -1909,6 +1910,43 @@ int icn_head_bwd(const float* dy, const float* y, const float* x, const float* w
         if (!dy || !y || !x || !w || !dw || !db || !ws || M < 1) throw std::invalid_argument("icn_head_bwd: bad arguments");
         if (!icn::head_supported(Cin, Cout)) throw std::invalid_argument("icn_head_bwd: unsupported channel counts");
         icn::launch_head_bwd(dy, y, x, w, dx, dw, db, ws, M, Cin, Cout, s);
+    });
+}
+
+// ---- fused decoder tail: BatchNorm + residual + ReLU + 1x1 head + tanh (include/icn_fused.h) ---------------------
+namespace {
+bool bn_head_sizes_ok(int M, int C, int Cout) { return M >= 1 && icn::bn_supported(C) && icn::head_supported(C, Cout); }
+}  // namespace
+
+size_t icn_bn_head_workspace_bytes(int M, int C, int Cout) {
+    return bn_head_sizes_ok(M, C, Cout) ? icn::bn_head_workspace_bytes(M, C) : 0;
+}
+
+int icn_bn_head_fwd(const float* a, const float* b, const float* stat_a, const float* stat_b, const float* gamma_a, const float* beta_a,
+                    const float* gamma_b, const float* beta_b, const float* w, const float* bias, float* y, int M, int C, int Cout,
+                    void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!a || !b || !stat_a || !stat_b || !gamma_a || !beta_a || !gamma_b || !beta_b || !w || !bias || !y)
+            throw std::invalid_argument("icn_bn_head_fwd: null pointer");
+        if (!bn_head_sizes_ok(M, C, Cout)) throw std::invalid_argument("icn_bn_head_fwd: bad sizes");
+        icn::launch_bn_head_fwd(a, b, stat_a, stat_b, gamma_a, beta_a, gamma_b, beta_b, w, bias, y, M, C, Cout, s);
+    });
+}
+
+int icn_bn_head_bwd(const float* dy, const float* y, const float* a, const float* b, const float* stat_a, const float* stat_b,
+                    const float* gamma_a, const float* beta_a, const float* gamma_b, const float* beta_b, const float* w, float* da,
+                    float* db, float* sums, float* dw, float* dbias, float* dbeta_a, float* dgamma_a, float* dbeta_b, float* dgamma_b,
+                    int M, int C, int Cout, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!dy || !y || !a || !b || !stat_a || !stat_b || !gamma_a || !beta_a || !gamma_b || !beta_b || !w || !da || !db || !sums || !dw ||
+            !dbias)
+            throw std::invalid_argument("icn_bn_head_bwd: null pointer");
+        if (!bn_head_sizes_ok(M, C, Cout)) throw std::invalid_argument("icn_bn_head_bwd: bad sizes");
+        check_workspace("icn_bn_head_bwd", ws, ws_bytes, icn::bn_head_workspace_bytes(M, C));
+        icn::launch_bn_head_bwd(dy, y, a, b, stat_a, stat_b, gamma_a, beta_a, gamma_b, beta_b, w, da, db, sums, dw, dbias, dbeta_a,
+                                dgamma_a, dbeta_b, dgamma_b, ws, M, C, Cout, s);
     });
 }
 

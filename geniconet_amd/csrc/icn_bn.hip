@@ -8,6 +8,7 @@
 
 #include <algorithm>
 
+#include "icn_bn_device.h"
 #include "icn_launch.h"
 
 // (see icn_kernels.hip: wave priority of the kernels on the backward pass's critical chain)
@@ -22,11 +23,6 @@
 
 namespace icn {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-__device__ __forceinline__ f32x4 ldv(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void stv(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ f32x4 relu4(f32x4 v) { return f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)}; }
-
 #ifndef ICN_BN_MAX_CHUNKS
 #define ICN_BN_MAX_CHUNKS 512
 #endif
@@ -35,26 +31,7 @@ constexpr int BN_MAX_CHUNKS = ICN_BN_MAX_CHUNKS;
 //  is sized by bn_chunks(), which is capped by this constant, so it only has to be positive)
 static_assert(BN_MAX_CHUNKS >= 1 && BN_MAX_CHUNKS <= 65536, "ICN_BN_MAX_CHUNKS");
 
-// Sums of the BatchNorm passes are accumulated in DOUBLE from the first add (round 3), as the CPU reference does (torch's
-// acc_type<float> on the CPU is double; its device kernels sum in fp32).  A batch statistic enters every element of its channel,
-// so its rounding error is a COHERENT perturbation of the tensor, unlike the element-wise rounding of the convolutions, and the
-// next cancelling sum (a BatchNorm backward's sum g, sum g * xhat, where |sum g| is 10 - 400 x smaller than sum |g| in this
-// network) amplifies exactly that kind of error.  The kernels are HBM-bound: the fp64 adds cost nothing measurable (same
-// throughput in the bench).  (What this does NOT remove: gradients of this network are discontinuous at ReLU pre-activations
-// within rounding of zero; see tests/test_gpu_training_parity.py for how the parity tests deal with that.)
-using f64x4 = __attribute__((ext_vector_type(4))) double;
-__device__ __forceinline__ f64x4 to_d(f32x4 v) { return f64x4{(double)v[0], (double)v[1], (double)v[2], (double)v[3]}; }
-
-// pre-activation of the fused op for 4 channels: bn_a(a) [+ bn_b(b)]; scale = invstd * gamma.  Forward and both backward
-// passes go through this one function, so the ReLU mask the backward recomputes is bit-identical to the forward's.
-template <int DUAL>
-__device__ __forceinline__ f32x4 bn_pre4(f32x4 a, f32x4 mean_a, f32x4 scale_a, f32x4 beta_a, f32x4 b, f32x4 mean_b, f32x4 scale_b,
-                                         f32x4 beta_b) {
-    f32x4 v = (a - mean_a) * scale_a + beta_a;
-    if (DUAL) v += (b - mean_b) * scale_b + beta_b;
-    return v;
-}
-
+// (f32x4 / f64x4, the double sums and bn_pre4, the one pre-activation of every pass: icn_bn_device.h)
 // partial[chunk][k][C], k < NS: per-channel sums of NS quantities over the chunk's rows.
 //   MODE 0 (forward stats of x):                 k0 = sum (x - x0), k1 = sum (x - x0)^2       x0 = row 0 of x (per channel)
 //          The shift keeps var = E[(x-x0)^2] - E[x-x0]^2 free of cancellation when |mean| >> std (torch uses Welford;
@@ -388,6 +365,12 @@ void launch_bn_relu_fwd(const float* a, const float* b, const float* stat_a, con
     else hipLaunchKernelGGL(k_bn_relu_fwd<0>, dim3(stream_blocks(total4)), dim3(256), 0, s, a, b, stat_a, stat_b, ga, ba, gb, bb, y, total4, C);
 }
 
+void launch_bn_finalize_bwd(const double* partial, int chunks, int C, int NS, float* sums, float* dbeta_a, float* dgamma_a,
+                            float* dbeta_b, float* dgamma_b, hipStream_t s) {
+    hipLaunchKernelGGL(k_bn_finalize_bwd, dim3((C + 15) / 16, NS), dim3(256), 0, s, partial, chunks, C, NS, sums,
+                       BnGradOut{dbeta_a, dbeta_b, dgamma_a, dgamma_b});
+}
+
 void launch_bn_relu_bwd(const float* dy, const float* a, const float* b, const float* stat_a, const float* stat_b, const float* ga,
                         const float* ba, const float* gb, const float* bb, float* da, float* db, float* sums, float* ws, int M, int C,
                         float* dbeta_a, float* dgamma_a, float* dbeta_b, float* dgamma_b, hipStream_t s) {
@@ -396,8 +379,7 @@ void launch_bn_relu_bwd(const float* dy, const float* a, const float* b, const f
     double* wsd = reinterpret_cast<double*>(ws);
     if (b) hipLaunchKernelGGL(k_bn_partial<2>, dim3(chunks), dim3(256), 0, s, dy, a, b, stat_a, stat_b, ga, ba, gb, bb, wsd, M, C, rows);
     else hipLaunchKernelGGL(k_bn_partial<1>, dim3(chunks), dim3(256), 0, s, dy, a, b, stat_a, stat_b, ga, ba, gb, bb, wsd, M, C, rows);
-    hipLaunchKernelGGL(k_bn_finalize_bwd, dim3((C + 15) / 16, NS), dim3(256), 0, s, wsd, chunks, C, NS, sums,
-                       BnGradOut{dbeta_a, b ? dbeta_b : nullptr, dgamma_a, b ? dgamma_b : nullptr});
+    launch_bn_finalize_bwd(wsd, chunks, C, NS, sums, dbeta_a, dgamma_a, b ? dbeta_b : nullptr, b ? dgamma_b : nullptr, s);
     const size_t total4 = (size_t)M * C / 4;
     if (b) hipLaunchKernelGGL(k_bn_relu_bwd<1>, dim3(stream_blocks(total4)), dim3(256), 0, s, dy, a, b, stat_a, stat_b, ga, ba, gb, bb, sums, da, db, total4, C, 1.f / M);
     else hipLaunchKernelGGL(k_bn_relu_bwd<0>, dim3(stream_blocks(total4)), dim3(256), 0, s, dy, a, b, stat_a, stat_b, ga, ba, gb, bb, sums, da, db, total4, C, 1.f / M);
@@ -411,8 +393,6 @@ void launch_bn_relu_bwd(const float* dy, const float* a, const float* b, const f
 // (one float4 each, coalesced), partial dot products are combined with wave shuffles.
 // ---------------------------------------------------------------------------------------------------------
 namespace icn {
-
-constexpr int HEAD_MAX_OUT = 4;
 
 template <int LPR>   // lanes per row = Cin / 4 (power of two, <= 64)
 __global__ __launch_bounds__(256) void k_head_fwd(const float* __restrict__ x, const float* __restrict__ w,
@@ -447,9 +427,7 @@ __global__ __launch_bounds__(256) void k_head_fwd(const float* __restrict__ x, c
 // M = 1000 (tests/test_gpu_streaming_edges.py).  So below HEAD_F64_ROWS rows ACC is double, like the BatchNorm sums above, and dw / db
 // are rounded once; from there on ACC is float and the pass is the one it always was, bit for bit.
 constexpr int HEAD_F64_ROWS = 1024;
-template <typename ACC> struct HeadAcc;
-template <> struct HeadAcc<float> { using v4 = f32x4; static __device__ __forceinline__ v4 of(f32x4 v) { return v; } };
-template <> struct HeadAcc<double> { using v4 = f64x4; static __device__ __forceinline__ v4 of(f32x4 v) { return to_d(v); } };
+// (HeadAcc<ACC>: icn_bn_device.h)
 
 template <int LPR, typename ACC>
 __global__ __launch_bounds__(256) void k_head_bwd(const float* __restrict__ dy, const float* __restrict__ y,
@@ -558,6 +536,12 @@ static void head_bwd(const float* dy, const float* y, const float* x, const floa
         default: hipLaunchKernelGGL((k_head_bwd<64, ACC>), grid, block, 0, s, dy, y, x, w, dx, ws, M, Cout, rows); break;
     }
     hipLaunchKernelGGL(k_head_reduce<ACC>, dim3((Cout * (Cin + 1) + 3) / 4), block, 0, s, ws, chunks, Cin, Cout, dw, db);
+}
+
+void launch_head_reduce(const void* partial, bool in_double, int chunks, int Cin, int Cout, float* dw, float* db, hipStream_t s) {
+    const dim3 grid((Cout * (Cin + 1) + 3) / 4), block(256);
+    if (in_double) hipLaunchKernelGGL(k_head_reduce<double>, grid, block, 0, s, static_cast<const double*>(partial), chunks, Cin, Cout, dw, db);
+    else hipLaunchKernelGGL(k_head_reduce<float>, grid, block, 0, s, static_cast<const float*>(partial), chunks, Cin, Cout, dw, db);
 }
 
 void launch_head_bwd(const float* dy, const float* y, const float* x, const float* w, float* dx, float* dw, float* db, float* ws,

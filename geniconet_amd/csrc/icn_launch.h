@@ -192,6 +192,22 @@ void launch_head_fwd(const float* x, const float* w, const float* bias, float* y
 void launch_head_bwd(const float* dy, const float* y, const float* x, const float* w, float* dx, float* dw, float* db, float* ws,
                      int M, int Cin, int Cout, hipStream_t s);
 
+// ---- fused decoder tail (icn_fused.hip; include/icn_fused.h): y = tanh(W relu(bn_a(a) + bn_b(b)) + bias) without storing the ReLU
+// output, and its backward without storing the head's input gradient.  ws: bn_head_workspace_bytes(M, C) bytes (the chunk partials of
+// the three BatchNorm sums in double and of the head's dW / dbias in the head's own sum type), 16-byte aligned.  The second stages are the ones of the unfused
+// operators (icn_bn.hip): the BatchNorm backward's finalize over NS sums per chunk, the head's reduce over partials in double.
+size_t bn_head_workspace_bytes(int M, int C);
+void launch_bn_head_fwd(const float* a, const float* b, const float* stat_a, const float* stat_b, const float* ga, const float* ba,
+                        const float* gb, const float* bb, const float* w, const float* bias, float* y, int M, int C, int Cout,
+                        hipStream_t s);
+void launch_bn_head_bwd(const float* dy, const float* y, const float* a, const float* b, const float* stat_a, const float* stat_b,
+                        const float* ga, const float* ba, const float* gb, const float* bb, const float* w, float* da, float* db,
+                        float* sums, float* dw, float* dbias, float* dbeta_a, float* dgamma_a, float* dbeta_b, float* dgamma_b, void* ws,
+                        int M, int C, int Cout, hipStream_t s);
+void launch_bn_finalize_bwd(const double* partial, int chunks, int C, int NS, float* sums, float* dbeta_a, float* dgamma_a,
+                            float* dbeta_b, float* dgamma_b, hipStream_t s);   // parameter gradients nullable
+void launch_head_reduce(const void* partial, bool in_double, int chunks, int Cin, int Cout, float* dw, float* db, hipStream_t s);   // partials float or double
+
 // lap_mode: Laplacian convention, bit 0 = v - mean(ring) instead of mean(ring) - v, bit 1 = times the valence (sum form)
 // ---- point-to-point loss (icn_loss.hip): terms[4] = {pos, nor, lap, weighted total}; partial = 3 * p2p_loss_blocks floats
 int p2p_loss_blocks(int B, int P);

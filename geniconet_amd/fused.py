@@ -8,7 +8,8 @@ of 4-7 separate elementwise passes).  The `nn.BatchNorm2d` modules stay in the m
 statistics, `num_batches_tracked` are updated exactly as torch does in training mode); the fused path is taken in
 training mode on ROCm tensors when nobody hooked those modules, and -- as one streaming pass with the running statistics
 (bn_relu_eval / bn_add_relu_eval) -- in eval mode when no autograd graph is being recorded (inference); otherwise the
-modules are called as usual.
+modules are called as usual.  At the end of the decoder the residual form and the output head `Conv2d(C, 3, 1) + Tanh` are one
+Function (bn_add_relu_head over icn_bn_head_*, include/icn_fused.h) that stores neither the ReLU output nor its gradient.
 """
 import os
 import weakref
@@ -314,6 +315,77 @@ def head(x, seq):
     if can_fuse_head(x, seq):
         return _HeadFn.apply(x, seq[0].weight, seq[0].bias)
     return seq(x)
+
+
+_NO_TAIL = os.environ.get('ICN_NO_FUSED_TAIL', '') == '1'      # developer A/B: the decoder's tail as bn_add_relu + head again
+
+
+class _BnHeadFn(torch.autograd.Function):
+    """y = tanh(conv1x1(relu(bn_a(a) + bn_b(b)))) with batch statistics (icn_bn_head_* of include/icn_fused.h): neither the ReLU
+    output nor the head's input gradient is stored.  Statistics and running statistics as _BnReluFn (icn_bn_stats2)."""
+
+    @staticmethod
+    def forward(ctx, a, ga, ba, rm_a, rv_a, eps_a, mom_a, b, gb, bb, rm_b, rv_b, eps_b, mom_b, weight, bias):
+        L = _lib.api()
+        ap, bp = _nhwc(a), _nhwc(b)
+        Bn, H, W, C = ap.shape
+        Cout, M = weight.shape[0], Bn * H * W
+        dev = a.device
+        w2 = weight.reshape(Cout, C).contiguous()
+        ws = _lib.workspace(L.icn_bn_workspace_floats(M, C), dev, torch.float32)
+        stat_a = torch.empty(2 * C, dtype=torch.float32, device=dev)
+        stat_b = torch.empty(2 * C, dtype=torch.float32, device=dev)
+        y = torch.empty(Bn, H, W, Cout, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = _lib.stream()
+            L.icn_bn_stats2(ap.data_ptr(), bp.data_ptr(), M, C, eps_a, mom_a, rm_a.data_ptr(), rv_a.data_ptr(), stat_a.data_ptr(),
+                            eps_b, mom_b, rm_b.data_ptr(), rv_b.data_ptr(), stat_b.data_ptr(), ws.data_ptr(), st)
+            L.icn_bn_head_fwd(ap.data_ptr(), bp.data_ptr(), stat_a.data_ptr(), stat_b.data_ptr(), ga.data_ptr(), ba.data_ptr(),
+                              gb.data_ptr(), bb.data_ptr(), w2.data_ptr(), bias.contiguous().data_ptr(), y.data_ptr(), M, C, Cout, st)
+        ctx.save_for_backward(ap, bp, stat_a, stat_b, ga, ba, gb, bb, w2, y)
+        ctx.wshape, ctx.wstride = weight.shape, weight.stride()
+        ctx.params = (ga, ba, gb, bb, weight, bias)      # where the parameter gradients go (_gradbuf.lease)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        L = _lib.api()
+        ap, bp, stat_a, stat_b, ga, ba, gb, bb, w2, y = ctx.saved_tensors
+        Bn, H, W, C = ap.shape
+        Cout, M = w2.shape[0], Bn * H * W
+        gyp = _nhwc(gy)
+        dev = gyp.device
+        da, db = torch.empty_like(ap), torch.empty_like(bp)
+        sums = torch.empty(3 * C, dtype=torch.float32, device=dev)
+        need = L.icn_bn_head_workspace_bytes(M, C, Cout)
+        ws = _lib.workspace(need, dev)
+        pga, pba, pgb, pbb, pw, pbias = ctx.params       # the same targets as _BnReluFn and _HeadFn: DDP bucket views keep working
+        dga, dba = _gradbuf.lease(pga, (C,), dev), _gradbuf.lease(pba, (C,), dev)
+        dgb, dbb = _gradbuf.lease(pgb, (C,), dev), _gradbuf.lease(pbb, (C,), dev)
+        dw = _gradbuf.lease(pw, ctx.wshape, dev, stride=ctx.wstride)
+        dbias = _gradbuf.lease(pbias, (Cout,), dev)
+        with torch.cuda.device(dev):
+            L.icn_bn_head_bwd(gyp.data_ptr(), y.data_ptr(), ap.data_ptr(), bp.data_ptr(), stat_a.data_ptr(), stat_b.data_ptr(),
+                              ga.data_ptr(), ba.data_ptr(), gb.data_ptr(), bb.data_ptr(), w2.data_ptr(), da.data_ptr(), db.data_ptr(),
+                              sums.data_ptr(), dw.data_ptr(), dbias.data_ptr(), dba.data_ptr(), dga.data_ptr(), dbb.data_ptr(),
+                              dgb.data_ptr(), M, C, Cout, ws.data_ptr(), need, _lib.stream())
+        return (da.permute(0, 3, 1, 2), dga, dba, None, None, None, None, db.permute(0, 3, 1, 2), dgb, dbb, None, None, None, None,
+                dw, dbias)
+
+
+def can_fuse_tail(x, bn_a, bn_b, seq):
+    """The decoder's tail as one operator: what bn_add_relu and head each ask for (can_fuse, can_fuse_head), the head reading the
+    BatchNorms' channels."""
+    return (not _NO_TAIL and can_fuse(x, bn_a, bn_b) and can_fuse_head(x, seq)
+            and seq[0].in_channels == bn_a.num_features == bn_b.num_features)
+
+
+def bn_add_relu_head(a, bn_a, b, bn_b, seq):
+    """seq(relu(bn_a(a) + bn_b(b))) for seq = Sequential(Conv2d(C, <=4, 1), Tanh()) (can_fuse_tail)."""
+    _bump(bn_a)
+    _bump(bn_b)
+    return _BnHeadFn.apply(a, *_args(bn_a), b, *_args(bn_b), seq[0].weight, seq[0].bias)
 
 
 class _ReparamFn(torch.autograd.Function):

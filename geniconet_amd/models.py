@@ -80,6 +80,26 @@ class BasicIcoS2SUpBlock(nn.Module):
         skip = self.icobn10(c10)
         return F.relu(main + skip)
 
+    def forward_with_head(self, x, head):
+        """head(self(x)) for the last block of a decoder in training (_decode checked can_fuse / can_fuse_tail and the hooks): the
+        residual BatchNorm + ReLU and the 1x1 head + tanh are one operator that stores neither the block's output nor its gradient."""
+        c00, c10 = fused.upconv_pair(x, self.upsample00, self.upsample10, self.conv00, self.conv10)
+        h = fused.bn_relu(c00, self.icobn00)
+        return fused.bn_add_relu_head(self.conv01(h), self.icobn01, c10, self.icobn10, head)
+
+
+def _decode(decoder, head, x):
+    """head(decoder(x)).  With training-mode BatchNorms on the HIP path, when nobody hooked the decoder, its last block, that block's
+    BatchNorms or the head and its children, the last block runs through forward_with_head; else module by module as before."""
+    last = decoder[-1] if isinstance(decoder, nn.Sequential) and len(decoder) else None
+    if isinstance(last, BasicIcoS2SUpBlock) and not any(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks
+                                                       for m in (decoder, last)) \
+            and fused.can_fuse(x, last.icobn00) and fused.can_fuse_tail(x, last.icobn01, last.icobn10, head):
+        for m in list(decoder)[:-1]:
+            x = m(x)
+        return last.forward_with_head(x, head)
+    return fused.head(decoder(x), head)
+
 
 class IcoUpS2S(nn.Module):
     """upsample then stride-1 conv (reference models.py:9-20; unused by the shipped models)."""
@@ -178,7 +198,7 @@ class ico2ico(nn.Module):
 
     def forward(self, x):
         with fused.counters_deferred():                  # one num_batches_tracked bump for the 19 BatchNorms
-            return fused.head(self.decoder(self.enc(self.encoder(x))), self.enc2icoConv)
+            return _decode(self.decoder, self.enc2icoConv, self.enc(self.encoder(x)))
 
 
 class ico2enc(nn.Module):
@@ -202,7 +222,7 @@ class enc2ico(nn.Module):
                                                        self.subdivisions)
 
     def forward(self, x):
-        return fused.head(self.decoder(x), self.enc2icoConv)
+        return _decode(self.decoder, self.enc2icoConv, x)
 
 
 class VAE(nn.Module):
@@ -272,7 +292,7 @@ class ico2ico_vae(VAE):
         return self.mu_hook(m), self.logvar_hook(lv)
 
     def decode(self, z):
-        return fused.head(self.decoder(self.reparameterize_hook(z)), self.final_layer)
+        return _decode(self.decoder, self.final_layer, self.reparameterize_hook(z))
 
 
 class ico2enc_vae(VAE):
@@ -308,7 +328,7 @@ class enc2ico_vae(VAE):
         return torch.add(mean, logvar * torch.randn(logvar.shape))
 
     def decode(self, z):
-        return fused.head(self.decoder(z), self.final_layer)
+        return _decode(self.decoder, self.final_layer, z)
 
     def forward(self, x):
         return self.decode(x), torch.tensor([]), torch.tensor([])
