@@ -108,7 +108,8 @@ SIGNATURES = {
 # one (checked by tests/test_abi_mesh.py and tests/test_abi_ext.py), same conventions, same library.  A new header is one more key here: lib() binds it and
 # source_files() hashes it.  tests/test_abi_mesh.py holds this table to one row per header, so a header added after that test goes into
 # LATER_HEADERS below, which is bound and hashed the same way and has a test of its own; tests/test_abi_pairs.py in turn holds that one
-# to its one row, so a header added after it goes into MATCH_HEADERS; tests/test_abi_match.py holds that to its one row: FUSED_HEADERS.
+# to its one row, so a header added after it goes into MATCH_HEADERS; tests/test_abi_match.py holds that to its one row: FUSED_HEADERS; tests/test_abi_fused.py
+# holds that to its one row: SUBSET_HEADERS.
 EXTENSION_HEADERS = {
     'icn_ext.h': {                     # normal agreement of two sampled surfaces
         'icn_face_normal_agree_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4, PLAIN),
@@ -180,6 +181,12 @@ FUSED_HEADERS = {
         'icn_bn_head_bwd': (ctypes.c_int, [_c_float_p] * 20 + [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
     },
 }
+# ... and for the headers added after tests/test_abi_fused.py (checked by tests/test_abi_fps.py)
+SUBSET_HEADERS = {
+    'icn_fps.h': {                     # farthest point sampling: a fixed number of well-spread points of every cloud
+        'icn_farthest_points': (ctypes.c_int, [_c_float_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2 + [ctypes.c_void_p], RC),
+    },
+}
 
 
 class ProfileEntry(ctypes.Structure):
@@ -215,7 +222,7 @@ def lib():
                 '(or `make -C geniconet_amd/csrc`).' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
         checked = types.SimpleNamespace()
-        for name, (res, args, reply) in [item for table in (SIGNATURES, *EXTENSION_HEADERS.values(), *LATER_HEADERS.values(), *MATCH_HEADERS.values(), *FUSED_HEADERS.values()) for item in table.items()]:
+        for name, (res, args, reply) in [item for table in (SIGNATURES, *EXTENSION_HEADERS.values(), *LATER_HEADERS.values(), *MATCH_HEADERS.values(), *FUSED_HEADERS.values(), *SUBSET_HEADERS.values()) for item in table.items()]:
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             fn = handle[name]            # a function object of its own (handle.name is cached, handle[name] is not)
@@ -279,9 +286,9 @@ def set_arith(mode):
 
 def source_files():
     """The files source_sha256() hashes, sorted: the kernel / library sources under csrc/, include/icn.h and every header of
-    EXTENSION_HEADERS, LATER_HEADERS, MATCH_HEADERS and FUSED_HEADERS."""
+    EXTENSION_HEADERS, LATER_HEADERS, MATCH_HEADERS, FUSED_HEADERS and SUBSET_HEADERS."""
     import glob
-    headers = [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('icn.h', *EXTENSION_HEADERS, *LATER_HEADERS, *MATCH_HEADERS, *FUSED_HEADERS)]
+    headers = [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('icn.h', *EXTENSION_HEADERS, *LATER_HEADERS, *MATCH_HEADERS, *FUSED_HEADERS, *SUBSET_HEADERS)]
     return sorted([f for pattern in ('*.hip', '*.h', '*.cpp') for f in glob.glob(os.path.join(_HERE, 'csrc', pattern))] + headers)
 
 

@@ -24,6 +24,7 @@
 #include "../../include/icn_pairs.h"
 #include "../../include/icn_match.h"
 #include "../../include/icn_fused.h"
+#include "../../include/icn_fps.h"
 #include "../../include/icn_measure.h"
 #include "icn_geometry.h"
 #include "icn_launch.h"
@@ -805,7 +806,8 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_mesh_raycast", "k_mesh_raycast_bwd_record", "k_mesh_raycast_bwd_vertex",
                                             "k_nn_points", "k_nn_points_bwd_record", "k_nn_points_bwd_vertex",
                                             "k_pair_sums", "k_pair_sums_finish",
-                                            "k_match_auction"};
+                                            "k_match_auction",
+                                            "k_farthest_points"};
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1711,6 +1713,17 @@ int icn_match_clouds(const float* queries, const float* targets, int G, int R, i
         if (!match_sizes_ok(G, R, N, paired, phases, max_rounds)) throw std::invalid_argument("icn_match_clouds: bad sizes");
         check_workspace("icn_match_clouds", ws, ws_bytes, icn::match_clouds_workspace_bytes(G, R, N, paired));
         icn::launch_match_clouds(queries, targets, G, R, N, paired, phases, max_rounds, match, prices, cost, rounds, ws, s);
+    });
+}
+
+// ---- farthest point sampling (include/icn_fps.h): one workgroup a cloud, every point in a register ----------------------------------------
+int icn_farthest_points(const float* points, int B, int N, int S, int start, int* idx, float* cover, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!points || !idx) throw std::invalid_argument("icn_farthest_points: null pointer");
+        if (B < 1 || B > 65535 || N < 1 || !icn::farthest_points_fits(N) || S < 1 || S > N || start < 0 || start >= N)
+            throw std::invalid_argument("icn_farthest_points: bad sizes");
+        icn::launch_farthest_points(points, B, N, S, start, idx, cover, s);
     });
 }
 

@@ -353,6 +353,13 @@ size_t match_clouds_workspace_bytes(int G, int R, int N, int paired);
 void launch_match_clouds(const float* qry, const float* tgt, int G, int R, int N, int paired, int phases, int max_rounds, int* match,
                          double* prices, double* cost, int* rounds, void* ws, hipStream_t s);
 
+// farthest point sampling (icn_fps.hip; include/icn_fps.h): one workgroup a cloud, grid (B); every thread holds
+// farthest_points_per_thread(N) points and their distances in registers (farthest_points_fits(N)); cover may be null.  One launch on s,
+// no workspace.
+bool farthest_points_fits(int N);
+int farthest_points_per_thread(int N);
+void launch_farthest_points(const float* pts, int B, int N, int S, int start, int* idx, float* cover, hipStream_t s);
+
 // developer routing flags (ICN_DEBUG / icn_set_debug_flags): 16 = convs on k_gather_gemm, 32 = wgrads on k_wgrad,
 // 128 = no stream-K, 256 = fault injection: every stream-K finisher reports its partners lost (tests of the failure path),
 // 512 = masked launches walk tiles b, b + G, ... instead of the balanced tile lists, 1024 = the sparse passes of the decoder-block
@@ -390,6 +397,7 @@ enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA
                 PROF_NN, PROF_NN_BWD_RECORD, PROF_NN_BWD_VERTEX,                                    // nearest-neighbour search and its backward
                 PROF_PAIR_SUMS, PROF_PAIR_SUMS_FINISH,                                              // sided sums of every pair of clouds
                 PROF_MATCH_AUCTION,                                                                 // optimal matching of two clouds
+                PROF_FARTHEST_POINTS,                                                               // farthest point sampling
                 PROF_KINDS };
 extern const char* const PROF_NAMES[PROF_KINDS];
 void prof_mark_begin(int kind, double flops, hipStream_t s);   // no-ops unless profiling is on

@@ -107,6 +107,9 @@ D 4^-phases of the optimum, D the diagonal of the joint bounding box, and the ou
 The HIP path reproduces the torch restatement on CPU tensors bit for bit in the matching, the round count and the prices.
 generation_metrics(distance='emd') reads MMD-EMD, COV-EMD and 1-NNA-EMD off pairwise_emd, evaluate_distance(mode='emd') gives one mesh
 pair's, and earth_movers_distance is differentiable in both sets at the matching found.
+
+generation_metrics, evaluate_distance and generation.evaluate_generation take points = P to run on P well-spread points of every cloud
+instead of the whole cloud: sampling.farthest_points (icn_farthest_points, include/icn_fps.h), the protocol those tables come from.
 """
 import torch
 
@@ -2449,14 +2452,37 @@ def earth_movers_distance(p1, p2, phases=6):
 GENERATION_DISTANCES = ('chamfer', 'emd')
 
 
-def generation_metrics(generated, reference, distance='chamfer'):
+def _check_subset_size(who, points):
+    """The check of the `points=` option -> points.  ValueError."""
+    if isinstance(points, bool) or not isinstance(points, int) or points < 0:
+        raise ValueError('%s: points must be a non-negative integer, got %r' % (who, points))
+    return points
+
+
+def _farthest_subsets(who, clouds, points):
+    """The `points=` option: every cloud of `clouds` (B, N, 3) thinned to its `points` farthest points (sampling.farthest_points from
+    index 0), without a gradient.  A cloud smaller than that raises ValueError."""
+    if points > clouds.shape[1]:
+        raise ValueError('%s: points=%d is more than the %d points of a cloud' % (who, points, clouds.shape[1]))
+    from .sampling import farthest_points
+    with torch.no_grad():
+        return farthest_points(clouds.detach(), points)
+
+
+def generation_metrics(generated, reference, distance='chamfer', points=0):
     """dict(mmd=, cov=, one_nna=) of Python floats for a set of generated clouds (G, N, 3) against a set of reference clouds (R, M, 3):
     minimum_matching_distance and coverage of pairwise_chamfer(generated, reference), one_nn_accuracy with the two within-set matrices
     as well.  Three pairwise_chamfer calls (squared distances, unit weights) and one read-back at the end.
-    distance='emd' takes the three matrices from pairwise_emd instead (MMD-EMD, COV-EMD, 1-NNA-EMD; M == N then)."""
+    distance='emd' takes the three matrices from pairwise_emd instead (MMD-EMD, COV-EMD, 1-NNA-EMD; M == N then).
+    points = P > 0 replaces both sets by sampling.farthest_points(., P) first -- the protocol of the shape-generation tables, P
+    well-spread points a shape (2 048 there), which is what makes the EMD matrices affordable; P larger than a cloud raises
+    ValueError.  points=0 (default) matches whole clouds."""
     if distance not in GENERATION_DISTANCES:
         raise ValueError('generation_metrics: distance must be one of %s, got %r' % (GENERATION_DISTANCES, distance))
+    _check_subset_size('generation_metrics', points)
     generated, reference = _check_cloud_sets('generation_metrics', generated, reference)
+    if points:
+        generated, reference = (_farthest_subsets('generation_metrics', x, points) for x in (generated, reference))
     if distance == 'emd':
         d_gr, d_gg, d_rr = pairwise_emd(generated, reference), pairwise_emd(generated, generated), pairwise_emd(reference, reference)
         mmd, cov, nna = torch.stack([minimum_matching_distance(d_gr), coverage(d_gr), one_nn_accuracy(d_gg, d_gr, d_rr)]).tolist()
@@ -2487,7 +2513,7 @@ def compute_distance(outvertices, refvertices, reffaces, mode='point2mesh', sear
 EVALUATION_MODES = ('point2point', 'point2mesh', 'chamfer', 'f_<radius>', 'hausdorff', 'emd')
 
 
-def evaluate_distance(outvertices, refvertices, reffaces, mode, samples=0, seed=0):
+def evaluate_distance(outvertices, refvertices, reffaces, mode, samples=0, seed=0, points=0):
     """The test modes the reference names (run.py:630: point2point, point2mesh, chamfer, f_<radius>) and 'hausdorff', for one mesh
     pair ((V, 3) tensors; `reffaces` (F, 3) is the face table of both, as everywhere in the reference), as a Python float.
     compute_distance itself keeps answering None to every mode but 'point2mesh', as the reference's computeDistance does.
@@ -2499,7 +2525,9 @@ def evaluate_distance(outvertices, refvertices, reffaces, mode, samples=0, seed=
         'emd'          earth_movers_distance of the two point sets, which have one size (the vertices, or S samples each)
     The point sets of the last four are the vertices, or with samples = S > 0 sampling.sample_points of the two surfaces from
     uniforms torch.rand((2, S, 3), generator=g), g a CPU generator seeded with `seed` (the output's surface takes the first S): the
-    same samples on every device.  An unknown mode raises ValueError."""
+    same samples on every device.  points = P > 0 then thins both point sets of those four modes to their P farthest points
+    (sampling.farthest_points; after the surface sampling, so samples=S, points=P is "S surface samples thinned to P"); P larger than a
+    point set raises ValueError, and points=0 (default) keeps the sets whole.  An unknown mode raises ValueError."""
     who = 'evaluate_distance'
     radius = None
     if isinstance(mode, str) and mode.startswith('f_'):
@@ -2513,6 +2541,7 @@ def evaluate_distance(outvertices, refvertices, reffaces, mode, samples=0, seed=
         raise ValueError('%s: mode must be one of %s, got %r' % (who, EVALUATION_MODES, mode))
     if isinstance(samples, bool) or not isinstance(samples, int) or samples < 0:
         raise ValueError('%s: samples must be a non-negative integer, got %r' % (who, samples))
+    _check_subset_size(who, points)
     if outvertices.dim() != 2 or refvertices.dim() != 2 or outvertices.shape[-1] != 3 or refvertices.shape[-1] != 3:
         raise ValueError('%s: expected two (V, 3) vertex tensors, got %s and %s' % (who, tuple(outvertices.shape), tuple(refvertices.shape)))
     if mode == 'point2mesh':
@@ -2528,6 +2557,8 @@ def evaluate_distance(outvertices, refvertices, reffaces, mode, samples=0, seed=
             from .sampling import sample_points
             u = torch.rand((2, 1, samples, 3), generator=torch.Generator().manual_seed(seed)).to(device=out.device, dtype=out.dtype)
             out, ref = sample_points(out, reffaces, uniforms=u[0])[0], sample_points(ref, reffaces, uniforms=u[1])[0]
+        if points:
+            out, ref = _farthest_subsets(who, out, points), _farthest_subsets(who, ref, points)
         if mode == 'chamfer':
             return float(chamfer_distance(out, ref)[0])
         if mode == 'hausdorff':

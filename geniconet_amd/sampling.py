@@ -16,7 +16,12 @@ face choice held constant (as kaolin and pytorch3d differentiate): dvertices[b, 
 HIP path it is summed in a fixed order without floating-point atomics (bit-identical run to run, an untouched vertex gets an exact 0).
 
 ROCm fp32 tensors run on the HIP kernels; CPU tensors, other dtypes and ICN_NO_HIP_LOSS=1 take the torch formulation (cumsum in
-float64, searchsorted(..., right=True)), which computes areas, weights and points in the dtype of `vertices`."""
+float64, searchsorted(..., right=True)), which computes areas, weights and points in the dtype of `vertices`.
+
+farthest_point_sample and farthest_points (below) thin a cloud -- the vertices, or such surface samples -- to a fixed number of
+WELL-SPREAD points: farthest point sampling, the subset the shape-generation tables (MMD / COV / 1-NNA on 2 048 points a shape) are
+computed on, where random surface samples have clumps and holes (icn_farthest_points, include/icn_fps.h: one workgroup a cloud, every
+point in a register, one barrier a step)."""
 import torch
 
 from . import metrics
@@ -132,3 +137,109 @@ def sample_points(vertices, faces, num_samples=None, uniforms=None, generator=No
         uniforms = uniforms.to(torch.float32)                                  # uniforms of another dtype must not leave the HIP path
     points, face, _ = _sample_points_unchecked(vertices, f32, uniforms)
     return points, face
+
+
+# ---- farthest point sampling: a fixed number of well-spread points of every cloud ---------------------------------------------------------
+_FPS_MAX_N = 13312                 # points a cloud may hold on the HIP path: every point in a register of its workgroup (include/icn_fps.h)
+
+
+def _torch_farthest_point_sample(points, count, start=0):
+    """THE DEFINITION of farthest_point_sample restated in torch (include/icn_fps.h, where it is written out), in the dtype of `points`
+    on any device -> (idx (B, count) int64, cover (B, count)); no graph, nothing read back.  Every difference, product and sum is a
+    torch operation of its own, in the order of the header; the lowest index among equal distances is picked explicitly (torch's own
+    argmax promises no tie rule on every device).  A cloud with a non-finite coordinate is masked BEFORE the loop (it runs on zeros
+    and its rows are overwritten with -1 / NaN), so no NaN ever enters the loop.  `count` dependent steps of about eight small
+    operations each: the restatement, not the fast path."""
+    B, N, _ = points.shape
+    dev = points.device
+    with torch.no_grad():
+        p = points.detach()
+        finite = torch.isfinite(p).all(-1).all(-1)                                        # (B,)
+        x, y, z = torch.where(finite[:, None, None], p, torch.zeros_like(p)).unbind(-1)   # (B, N) each
+        dist = torch.full((B, N), float('inf'), dtype=p.dtype, device=dev)
+        idx = torch.empty((B, count), dtype=torch.int64, device=dev)
+        cover = torch.empty((B, count), dtype=p.dtype, device=dev)
+        everyone = torch.arange(N, device=dev)[None]
+        nobody = torch.full_like(everyone, N)
+        cur = torch.full((B, 1), start, dtype=torch.int64, device=dev)
+        for s in range(count):
+            idx[:, s] = cur[:, 0]
+            dx, dy, dz = x - x.gather(1, cur), y - y.gather(1, cur), z - z.gather(1, cur)
+            dist = torch.minimum(dist, (dx * dx + dy * dy) + dz * dz)
+            top = dist.amax(1, keepdim=True)
+            cover[:, s] = top[:, 0]
+            cur = torch.where(dist == top, everyone, nobody).amin(1, keepdim=True)       # the lowest index among equals
+        idx = torch.where(finite[:, None], idx, torch.full_like(idx, -1))
+        cover = torch.where(finite[:, None], cover, torch.full_like(cover, float('nan')))
+    return idx, cover
+
+
+def _hip_farthest_point_sample(pts, count, start):
+    """icn_farthest_points on a contiguous fp32 ROCm tensor of at most _FPS_MAX_N points a cloud -> (idx int32, cover fp32)."""
+    B, N, _ = pts.shape
+    idx = torch.empty(B, count, dtype=torch.int32, device=pts.device)
+    cover = torch.empty(B, count, dtype=torch.float32, device=pts.device)
+    _launch('icn_farthest_points', _per_mesh(pts), _NB, N, count, start, _per_mesh(idx), _per_mesh(cover))
+    return idx, cover
+
+
+def _check_farthest_arguments(who, points, count, start):
+    """The checks of the farthest-point functions.  ValueError."""
+    if not torch.is_tensor(points) or not points.is_floating_point() or points.dim() != 3 or points.shape[-1] != 3 or points.shape[0] < 1 \
+            or points.shape[1] < 1:
+        raise ValueError('%s: expected the point set as a floating-point (B, N, 3) tensor with B, N >= 1, got %s'
+                         % (who, tuple(points.shape) if torch.is_tensor(points) else type(points).__name__))
+    N = points.shape[1]
+    if 3 * N > 0x7fffffff:
+        raise ValueError('%s: %d points: 3 N must fit an int32' % (who, N))
+    if isinstance(count, bool) or not isinstance(count, int) or not 1 <= count <= N:
+        raise ValueError('%s: count must be an integer in [1, %d], the size of a cloud, got %r' % (who, N, count))
+    if isinstance(start, bool) or not isinstance(start, int) or not 0 <= start < N:
+        raise ValueError('%s: start must be an integer in [0, %d), got %r' % (who, N, start))
+
+
+def _farthest_point_sample_unchecked(points, count, start):
+    """farthest_point_sample after its checks."""
+    if metrics._on_hip_path(points) and points.shape[1] <= _FPS_MAX_N:
+        idx, cover = _hip_farthest_point_sample(points.detach().contiguous(), count, start)
+        return idx.long(), cover
+    return _torch_farthest_point_sample(points, count, start)
+
+
+def farthest_point_sample(points, count, start=0):
+    """(idx (B, count) int64, cover (B, count) in the dtype of points): farthest point sampling of every cloud of points (B, N, 3) --
+    `count` indices of well-spread points, beginning with `start`, each next one the point farthest from all chosen so far; cover[b, s]
+    is the largest squared distance of a point of the cloud to its nearest chosen point after s + 1 choices (the covering radius,
+    squared).  The subset that the shape-generation tables match instead of whole clouds.  No gradient; farthest_points gathers the
+    points themselves.
+
+    One definition for the HIP kernel (include/icn_fps.h), the torch restatement (_torch_farthest_point_sample) and the tests.  All
+    arithmetic is in the dtype of points (fp32 on the device), every product and sum rounded on its own:
+        d(i, c) = (dx dx + dy dy) + dz dz,  dx = p_i.x - p_c.x, dy and dz likewise     (the d_j of sided_distance; symmetric bit for bit)
+        dist_i = +inf, cur = start;  for s = 0 ... count - 1:
+            idx[b, s] = cur;  dist_i = fminf(dist_i, d(i, cur)) for every i;  cover[b, s] = max_i dist_i;
+            cur = the LOWEST i with dist_i == cover[b, s]
+    Decided before the loop: a cloud with a non-finite coordinate gives idx -1 and cover NaN in its rows and leaves the other clouds of
+    the batch alone.  fminf, max and the lowest-index argmax are order-free, so idx and cover are fixed bit for bit; with finite
+    coordinates no NaN arises (an overflowing d is +inf).  Exactly, in the dtype: cover is non-increasing; cover[:, -1] is
+    sided_distance(points, points[idx])[0].amax(-1); for count >= 2 the smallest d between two chosen points is cover[:, -2];
+    count == N with distinct points gives a permutation with final cover 0; once the distinct points are used up cover is 0 and idx
+    repeats index 0 -- duplicates are defined, not an error.
+    ROCm fp32 tensors of at most 13312 points a cloud run on icn_farthest_points: one workgroup of 512 threads owns a cloud from
+    start to finish, every point and its dist in registers, one 64-bit key (dist bits, ~index) a thread reduced over the wave and
+    through one LDS slot a wave, one barrier a step; a batch costs about what one cloud does until there are more clouds than compute
+    units, and idx and cover equal the restatement on CPU tensors bit for bit.  Batches beyond 65535 clouds go in several launches.
+    CPU tensors, other dtypes, ICN_NO_HIP_LOSS=1 and ROCm clouds of MORE than 13312 points take the restatement: `count` dependent
+    steps of about eight small operations each, so subsampling 100 000 surface samples stays possible, slowly.  Arguments are checked
+    (ValueError): count and start integers with 1 <= count <= N and 0 <= start < N.  Nothing is read back."""
+    _check_farthest_arguments('farthest_point_sample', points, count, start)
+    return _farthest_point_sample_unchecked(points, count, start)
+
+
+def farthest_points(points, count, start=0):
+    """(B, count, 3): the points farthest_point_sample(points, count, start) chooses, by torch.gather -- differentiable in `points` at
+    the fixed choice (the choice itself carries no gradient).  A cloud with a non-finite coordinate (idx -1) gives NaN rows."""
+    _check_farthest_arguments('farthest_points', points, count, start)
+    idx, _ = _farthest_point_sample_unchecked(points, count, start)
+    chosen = torch.gather(points, 1, idx.clamp(min=0)[..., None].expand(-1, -1, 3))
+    return torch.where((idx < 0)[..., None], torch.full_like(chosen, float('nan')), chosen)

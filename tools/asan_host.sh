@@ -13,7 +13,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="-O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -fsanitize=address,undefined -fno-gpu-sanitize -fno-omit-frame-pointer -shared-libsan"
 cd "$ROOT/geniconet_amd/csrc"
 pids=()
-for f in icn_api.cpp icn_geometry.cpp icn_kernels.hip icn_bn.hip icn_loss.hip icn_sample.hip icn_measure.hip icn_curvature.hip icn_gauss.hip icn_isect.hip icn_sdf.hip icn_voxel.hip icn_optim.hip icn_raycast.hip icn_nn.hip icn_pairs.hip icn_match.hip icn_fused.hip; do
+for f in icn_api.cpp icn_geometry.cpp icn_kernels.hip icn_bn.hip icn_loss.hip icn_sample.hip icn_measure.hip icn_curvature.hip icn_gauss.hip icn_isect.hip icn_sdf.hip icn_voxel.hip icn_optim.hip icn_raycast.hip icn_nn.hip icn_pairs.hip icn_match.hip icn_fused.hip icn_fps.hip; do
     $HIPCC $FLAGS -c "$f" -o "$OUT/${f%.*}.o" &
     pids+=($!)
 done
