@@ -109,7 +109,7 @@ SIGNATURES = {
 # source_files() hashes it.  tests/test_abi_mesh.py holds this table to one row per header, so a header added after that test goes into
 # LATER_HEADERS below, which is bound and hashed the same way and has a test of its own; tests/test_abi_pairs.py in turn holds that one
 # to its one row, so a header added after it goes into MATCH_HEADERS; tests/test_abi_match.py holds that to its one row: FUSED_HEADERS; tests/test_abi_fused.py
-# holds that to its one row: SUBSET_HEADERS.
+# holds that to its one row: SUBSET_HEADERS; tests/test_abi_fps.py holds that to its one row: OCCUPANCY_HEADERS.
 EXTENSION_HEADERS = {
     'icn_ext.h': {                     # normal agreement of two sampled surfaces
         'icn_face_normal_agree_bwd_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4, PLAIN),
@@ -187,6 +187,15 @@ SUBSET_HEADERS = {
         'icn_farthest_points': (ctypes.c_int, [_c_float_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2 + [ctypes.c_void_p], RC),
     },
 }
+# ... and for the headers added after tests/test_abi_fps.py (checked by tests/test_abi_occupancy.py)
+OCCUPANCY_HEADERS = {
+    'icn_occupancy.h': {               # occupancy histograms of point clouds on a lattice, and their Jensen-Shannon divergence
+        'icn_point_occupancy_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4, PLAIN),
+        'icn_point_occupancy': (ctypes.c_int, [_c_float_p] + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 2
+                                + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], RC),
+        'icn_occupancy_jsd': (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 2, RC),
+    },
+}
 
 
 class ProfileEntry(ctypes.Structure):
@@ -222,7 +231,7 @@ def lib():
                 '(or `make -C geniconet_amd/csrc`).' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
         checked = types.SimpleNamespace()
-        for name, (res, args, reply) in [item for table in (SIGNATURES, *EXTENSION_HEADERS.values(), *LATER_HEADERS.values(), *MATCH_HEADERS.values(), *FUSED_HEADERS.values(), *SUBSET_HEADERS.values()) for item in table.items()]:
+        for name, (res, args, reply) in [item for table in (SIGNATURES, *EXTENSION_HEADERS.values(), *LATER_HEADERS.values(), *MATCH_HEADERS.values(), *FUSED_HEADERS.values(), *SUBSET_HEADERS.values(), *OCCUPANCY_HEADERS.values()) for item in table.items()]:
             fn = getattr(handle, name)   # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             fn = handle[name]            # a function object of its own (handle.name is cached, handle[name] is not)
@@ -286,9 +295,9 @@ def set_arith(mode):
 
 def source_files():
     """The files source_sha256() hashes, sorted: the kernel / library sources under csrc/, include/icn.h and every header of
-    EXTENSION_HEADERS, LATER_HEADERS, MATCH_HEADERS, FUSED_HEADERS and SUBSET_HEADERS."""
+    EXTENSION_HEADERS, LATER_HEADERS, MATCH_HEADERS, FUSED_HEADERS, SUBSET_HEADERS and OCCUPANCY_HEADERS."""
     import glob
-    headers = [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('icn.h', *EXTENSION_HEADERS, *LATER_HEADERS, *MATCH_HEADERS, *FUSED_HEADERS, *SUBSET_HEADERS)]
+    headers = [os.path.join(os.path.dirname(_HERE), 'include', h) for h in ('icn.h', *EXTENSION_HEADERS, *LATER_HEADERS, *MATCH_HEADERS, *FUSED_HEADERS, *SUBSET_HEADERS, *OCCUPANCY_HEADERS)]
     return sorted([f for pattern in ('*.hip', '*.h', '*.cpp') for f in glob.glob(os.path.join(_HERE, 'csrc', pattern))] + headers)
 
 

@@ -25,6 +25,7 @@
 #include "../../include/icn_match.h"
 #include "../../include/icn_fused.h"
 #include "../../include/icn_fps.h"
+#include "../../include/icn_occupancy.h"
 #include "../../include/icn_measure.h"
 #include "icn_geometry.h"
 #include "icn_launch.h"
@@ -807,7 +808,8 @@ const char* const PROF_NAMES[PROF_KINDS] = {"k_conv_dma<128, 128, false>", "k_co
                                             "k_nn_points", "k_nn_points_bwd_record", "k_nn_points_bwd_vertex",
                                             "k_pair_sums", "k_pair_sums_finish",
                                             "k_match_auction",
-                                            "k_farthest_points"};
+                                            "k_farthest_points",
+                                            "k_point_occupancy", "k_occupancy_reduce", "k_occupancy_jsd"};
 void prof_mark_begin(int kind, double flops, hipStream_t s) {
     if (!g_prof_on) return;
     g_prof_mu.lock();
@@ -1724,6 +1726,39 @@ int icn_farthest_points(const float* points, int B, int N, int S, int start, int
         if (B < 1 || B > 65535 || N < 1 || !icn::farthest_points_fits(N) || S < 1 || S > N || start < 0 || start >= N)
             throw std::invalid_argument("icn_farthest_points: bad sizes");
         icn::launch_farthest_points(points, B, N, S, start, idx, cover, s);
+    });
+}
+
+// ---- occupancy histograms of point clouds and their divergence (include/icn_occupancy.h): B is a grid dimension, B N fits an int ---------
+namespace {
+bool occupancy_sizes_ok(int B, int N, int R) {
+    return B >= 1 && B <= 65535 && N >= 1 && (long long)B * N <= 0x7fffffffLL && R >= 1 && R <= 32;
+}
+}  // namespace
+
+size_t icn_point_occupancy_workspace_bytes(int B, int N, int R, int per_cloud) {
+    return occupancy_sizes_ok(B, N, R) ? icn::point_occupancy_workspace_bytes(B, N, R, per_cloud) : 0;
+}
+
+int icn_point_occupancy(const float* points, int B, int N, int R, float lo, float inv_spacing, int per_cloud, int32_t* counts,
+                        int32_t* dropped, void* workspace, size_t workspace_bytes, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!points || !counts || !workspace) throw std::invalid_argument("icn_point_occupancy: null pointer");
+        if (!occupancy_sizes_ok(B, N, R) || !std::isfinite(lo) || !std::isfinite(inv_spacing) || !(inv_spacing > 0.f) ||
+            workspace_bytes < icn::point_occupancy_workspace_bytes(B, N, R, per_cloud))
+            throw std::invalid_argument("icn_point_occupancy: bad sizes");
+        if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) throw std::invalid_argument("icn_point_occupancy: workspace must be 16-byte aligned");
+        icn::launch_point_occupancy(points, B, N, R, lo, inv_spacing, per_cloud, counts, dropped, workspace, s);
+    });
+}
+
+int icn_occupancy_jsd(const int32_t* counts_a, const int32_t* counts_b, int R, double* jsd, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return launched([&] {
+        if (!counts_a || !counts_b || !jsd) throw std::invalid_argument("icn_occupancy_jsd: null pointer");
+        if (R < 1 || R > 32) throw std::invalid_argument("icn_occupancy_jsd: bad sizes");
+        icn::launch_occupancy_jsd(counts_a, counts_b, R, jsd, s);
     });
 }
 

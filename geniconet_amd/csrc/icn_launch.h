@@ -321,6 +321,15 @@ constexpr int VOXEL_MAX_DEPTH = 512;
 void launch_mesh_voxelize(const float* vts, const int32_t* faces, int B, int V, int F, double ox, double oy, double oz, double h, int n0,
                           int n1, int n2, uint8_t* occ, hipStream_t s);
 
+// occupancy histograms of point clouds on an R^3 lattice (icn_voxel.hip; include/icn_occupancy.h): every workgroup a private histogram
+// in LDS filled by integer LDS atomics, one histogram for the set or (per_cloud) one a cloud; dropped may be null.  One launch on s, a
+// second when a histogram was split among workgroups; ws: point_occupancy_workspace_bytes(B, N, R, per_cloud) bytes, 16-byte aligned.
+size_t point_occupancy_workspace_bytes(int B, int N, int R, int per_cloud);
+void launch_point_occupancy(const float* pts, int B, int N, int R, float lo, float inv_spacing, int per_cloud, int32_t* counts,
+                            int32_t* dropped, void* ws, hipStream_t s);
+// the Jensen-Shannon divergence (base 2) of two such histograms of R^3 int32: one workgroup, one double out.  One launch on s.
+void launch_occupancy_jsd(const int32_t* counts_a, const int32_t* counts_b, int R, double* jsd, hipStream_t s);
+
 // ray casting (icn_raycast.hip; include/icn_raycast.h): one thread per (mesh, ray) against the faces of its mesh through LDS tiles,
 // double arithmetic: first hit (depth, face) and crossing count per ray.  One launch on s, no workspace.
 void launch_mesh_raycast(const float* org, const float* dir, const float* vts, const int32_t* faces, int B, int R, int V, int F, float* depth,
@@ -398,6 +407,7 @@ enum ProfKind { PROF_DMA_128x128 = 0, PROF_DMA_128x64, PROF_DMA_64x128, PROF_DMA
                 PROF_PAIR_SUMS, PROF_PAIR_SUMS_FINISH,                                              // sided sums of every pair of clouds
                 PROF_MATCH_AUCTION,                                                                 // optimal matching of two clouds
                 PROF_FARTHEST_POINTS,                                                               // farthest point sampling
+                PROF_POINT_OCCUPANCY, PROF_OCCUPANCY_REDUCE, PROF_OCCUPANCY_JSD,                    // occupancy histograms and their divergence
                 PROF_KINDS };
 extern const char* const PROF_NAMES[PROF_KINDS];
 void prof_mark_begin(int kind, double flops, hipStream_t s);   // no-ops unless profiling is on

@@ -162,4 +162,190 @@ void launch_mesh_voxelize(const float* vts, const int32_t* faces, int B, int V, 
     prof_mark_end(s);
 }
 
+
+// ---- occupancy histograms of point clouds and their Jensen-Shannon divergence (include/icn_occupancy.h, where the definition is written
+// out; metrics._torch_occupancy_counts and _torch_occupancy_jsd restate it) -- the other "what lies in which lattice cell" operator.
+// k_point_occupancy: grid (S, nb), 1024 threads.  A HISTOGRAM (the whole set: nb = 1; or one cloud: nb = B) is a run of P consecutive
+// points of the flat (B N, 3) array, cut into S pieces of `per` points (a multiple of 4); workgroup (s, b) owns piece s of histogram b
+// and a PRIVATE copy of all R^3 cells in dynamic LDS (87 808 bytes at R = 28, 131 072 at 32: one workgroup a CU, which is why a piece
+// is not smaller than OCC_POINTS points -- zeroing, reading and storing R^3 words is the fixed cost, about what 7 300 points cost to
+// read at R = 28).  It zeroes the copy, streams its piece, adds 1 with ds_add_u32 (integer, no return value: order-free, so the counts
+// are the definition's whatever the split) and stores the copy once: to `counts` itself when S == 1, else to slice b S + s of the
+// workspace for k_occupancy_reduce.  No global atomics, no memset, nothing waits on another workgroup, every loop is bounded by sizes.
+// Loads: a thread takes an ALIGNED group of four points, 48 bytes = three float4 loads off a 16-byte aligned address (group g starts
+// at float 12 g of the array, so the alignment is that of `points`), and masks the points of the group outside its piece -- a cloud may
+// start anywhere in a group.  The group that would read past the array's end, and a `points` that is not 16-byte aligned (a view),
+// take the same points with three scalar loads each.  A wave reads 3 KiB of consecutive bytes per group round either way.
+// The worst case for the atomics is every point in one cell: the 64 lanes of a wave then hit one address and the LDS serialises them
+// (bank conflicts of a spread-out cloud cost at most the few lanes that share a bank); profiles/occupancy_jsd.txt holds both.
+// The cell arithmetic must not be contracted: the file is compiled with fp contract(off), and t + 0.5f stays an addition.
+constexpr int OCC_BLOCK = 1024;             // threads of a k_point_occupancy workgroup
+constexpr int OCC_POINTS = 16384;           // points a piece holds at least (while there are workgroups left): 4 group rounds
+constexpr int OCC_MAX_WG = 256;             // workgroups a launch splits its histograms into at most: one a CU of an MI355X
+constexpr int JSD_BLOCK = 256;              // T of the header: the order of the divergence's sum
+
+namespace {
+
+struct OccPlan {
+    int nb, S;                              // histograms, pieces a histogram
+    long long P, per;                       // points a histogram, points a piece (a multiple of 4)
+};
+
+OccPlan occupancy_plan(int B, int N, int per_cloud) {
+    OccPlan p;
+    p.nb = per_cloud ? B : 1;
+    p.P = per_cloud ? (long long)N : (long long)B * N;
+    const long long want = (p.P + OCC_POINTS - 1) / OCC_POINTS, room = OCC_MAX_WG / p.nb > 1 ? OCC_MAX_WG / p.nb : 1;
+    p.S = (int)(want < room ? want : room);
+    p.per = ((p.P + p.S - 1) / p.S + 3) & ~3LL;
+    return p;
+}
+
+__device__ __forceinline__ int occ_axis(float x, float lo, float inv, float top) {
+    const float t = (x - lo) * inv;
+    const float u = floorf(t + 0.5f);
+    return (int)fminf(fmaxf(u, 0.0f), top);
+}
+
+__device__ __forceinline__ void occ_point(float x, float y, float z, float lo, float inv, float top, int R, unsigned* hist, int& dropped) {
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) {
+        ++dropped;
+        return;
+    }
+    const int c = (occ_axis(x, lo, inv, top) * R + occ_axis(y, lo, inv, top)) * R + occ_axis(z, lo, inv, top);   // < R^3 by the clamps
+    atomicAdd(&hist[c], 1u);
+}
+
+__global__ __launch_bounds__(OCC_BLOCK) void k_point_occupancy(const float* __restrict__ pts, long long total, long long P, long long per,
+                                                                int R, float lo, float inv, int wide, int32_t* __restrict__ out,
+                                                                int32_t* __restrict__ dropped_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned occ_hist[];      // [R^3]
+    __shared__ int s_dropped;
+    const int tid = threadIdx.x, cells = R * R * R;
+    const size_t w = (size_t)blockIdx.y * gridDim.x + blockIdx.x;           // the piece: its slice of `out`, its word of `dropped_out`
+    for (int i = tid; i < cells; i += OCC_BLOCK) occ_hist[i] = 0u;
+    if (tid == 0) s_dropped = 0;
+    __syncthreads();
+    const long long h0 = (long long)blockIdx.y * P;                          // the histogram's first point
+    const long long f0 = h0 + (long long)blockIdx.x * per;                   // the piece [f0, f1)
+    const long long f1 = f0 + per < h0 + P ? f0 + per : h0 + P;
+    const float top = (float)(R - 1);
+    int nd = 0;
+    for (long long g = (f0 >> 2) + tid; 4 * g < f1; g += OCC_BLOCK) {        // aligned groups of four points that meet the piece
+        const long long first = 4 * g;
+        if (wide && first + 4 <= total) {
+            const float4* q = reinterpret_cast<const float4*>(pts + 12 * (size_t)g);
+            const float4 a = q[0], b = q[1], c = q[2];
+            if (first >= f0 && first < f1) occ_point(a.x, a.y, a.z, lo, inv, top, R, occ_hist, nd);
+            if (first + 1 >= f0 && first + 1 < f1) occ_point(a.w, b.x, b.y, lo, inv, top, R, occ_hist, nd);
+            if (first + 2 >= f0 && first + 2 < f1) occ_point(b.z, b.w, c.x, lo, inv, top, R, occ_hist, nd);
+            if (first + 3 >= f0 && first + 3 < f1) occ_point(c.y, c.z, c.w, lo, inv, top, R, occ_hist, nd);
+        } else {
+            for (int k = 0; k < 4; ++k) {
+                const long long p = first + k;
+                if (p < f0 || p >= f1) continue;                             // f1 <= total: the loads below stay inside the array
+                const float* q = pts + 3 * (size_t)p;
+                occ_point(q[0], q[1], q[2], lo, inv, top, R, occ_hist, nd);
+            }
+        }
+    }
+    if (nd) atomicAdd(&s_dropped, nd);
+    __syncthreads();
+    int32_t* o = out + w * (size_t)cells;
+    for (int i = tid; i < cells; i += OCC_BLOCK) o[i] = (int32_t)occ_hist[i];
+    if (tid == 0 && dropped_out) dropped_out[w] = s_dropped;
+}
+
+// counts[b, c] = the sum over the S pieces of histogram b, dropped[b] likewise: one thread per output word, every word written once
+__global__ __launch_bounds__(256) void k_occupancy_reduce(const int32_t* __restrict__ part, const int32_t* __restrict__ part_dropped, int S,
+                                                           int cells, int nb, int32_t* __restrict__ counts, int32_t* __restrict__ dropped) {
+    const long long n_out = (long long)nb * cells, i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_out) {
+        const long long b = i / cells, c = i - b * cells;
+        const int32_t* p = part + (size_t)b * S * cells + c;
+        int32_t sum = 0;
+#pragma unroll 8                                                             // eight loads in flight: the pieces are independent
+        for (int s = 0; s < S; ++s) sum += p[(size_t)s * cells];
+        counts[i] = sum;
+    } else if (dropped && i - n_out < nb) {
+        const long long b = i - n_out;
+        int32_t sum = 0;
+        for (int s = 0; s < S; ++s) sum += part_dropped[b * S + s];
+        dropped[b] = sum;
+    }
+}
+
+// the Jensen-Shannon divergence of two histograms: one workgroup, the totals as 64-bit integers, the sum in double in the header's order
+__global__ __launch_bounds__(JSD_BLOCK) void k_occupancy_jsd(const int32_t* __restrict__ ca, const int32_t* __restrict__ cb, int cells,
+                                                              double* __restrict__ jsd) {
+    __shared__ long long tot_a[JSD_BLOCK], tot_b[JSD_BLOCK];
+    __shared__ double part[JSD_BLOCK];
+    const int tid = threadIdx.x;
+    long long sa = 0, sb = 0;
+    for (int c = tid; c < cells; c += JSD_BLOCK) sa += ca[c], sb += cb[c];
+    tot_a[tid] = sa, tot_b[tid] = sb;
+    __syncthreads();
+    for (int h = JSD_BLOCK / 2; h > 0; h >>= 1) {
+        if (tid < h) tot_a[tid] += tot_a[tid + h], tot_b[tid] += tot_b[tid + h];
+        __syncthreads();
+    }
+    const long long A = tot_a[0], B = tot_b[0];
+    if (A == 0 || B == 0) {                                                  // uniform: every thread leaves here
+        if (tid == 0) *jsd = __longlong_as_double(0x7ff8000000000000LL);
+        return;
+    }
+    const double dA = (double)A, dB = (double)B;
+    double acc = 0.0;
+    for (int c = tid; c < cells; c += JSD_BLOCK) {
+        const int a = ca[c], b = cb[c];
+        const double p = (double)a / dA, q = (double)b / dB;
+        const double m = 0.5 * (p + q);
+        const double tp = a > 0 ? p * log2(p / m) : 0.0;
+        const double tq = b > 0 ? q * log2(q / m) : 0.0;
+        acc += 0.5 * (tp + tq);
+    }
+    part[tid] = acc;
+    __syncthreads();
+    for (int h = JSD_BLOCK / 2; h > 0; h >>= 1) {
+        if (tid < h) part[tid] += part[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) *jsd = part[0];
+}
+
+}  // namespace
+
+size_t point_occupancy_workspace_bytes(int B, int N, int R, int per_cloud) {
+    const OccPlan p = occupancy_plan(B, N, per_cloud);
+    return p.S == 1 ? 16 : (size_t)p.nb * p.S * ((size_t)R * R * R + 1) * sizeof(int32_t);
+}
+
+void launch_point_occupancy(const float* pts, int B, int N, int R, float lo, float inv_spacing, int per_cloud, int32_t* counts,
+                            int32_t* dropped, void* ws, hipStream_t s) {
+    const OccPlan p = occupancy_plan(B, N, per_cloud);
+    const int cells = R * R * R;
+    const size_t lds = (size_t)cells * sizeof(unsigned);
+    // the most a launch may ask for: 32^3 words, which leaves the kernel's one static word inside the 160 KiB
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_point_occupancy), hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 32 * 32 * 4);
+    const int wide = reinterpret_cast<uintptr_t>(pts) % 16 == 0;
+    int32_t* part = static_cast<int32_t*>(ws);
+    int32_t* part_dropped = part + (size_t)p.nb * p.S * cells;
+    prof_mark_begin(PROF_POINT_OCCUPANCY, 0.0, s);
+    hipLaunchKernelGGL(k_point_occupancy, dim3(p.S, p.nb), dim3(OCC_BLOCK), lds, s, pts, (long long)B * N, p.P, p.per, R, lo, inv_spacing, wide,
+                       p.S == 1 ? counts : part, p.S == 1 ? dropped : part_dropped);
+    prof_mark_end(s);
+    if (p.S == 1) return;
+    const long long words = (long long)p.nb * cells + p.nb;
+    prof_mark_begin(PROF_OCCUPANCY_REDUCE, 0.0, s);
+    hipLaunchKernelGGL(k_occupancy_reduce, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, part, part_dropped, p.S, cells, p.nb, counts,
+                       dropped);
+    prof_mark_end(s);
+}
+
+void launch_occupancy_jsd(const int32_t* counts_a, const int32_t* counts_b, int R, double* jsd, hipStream_t s) {
+    prof_mark_begin(PROF_OCCUPANCY_JSD, 0.0, s);
+    hipLaunchKernelGGL(k_occupancy_jsd, dim3(1), dim3(JSD_BLOCK), 0, s, counts_a, counts_b, R * R * R, jsd);
+    prof_mark_end(s);
+}
+
 }  // namespace icn

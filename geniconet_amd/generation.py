@@ -76,7 +76,7 @@ def generate_vertices(model, latents, batch_size=16):
         model.train(was_training)
 
 
-def evaluate_generation(model, reference_vertices, count, seed=0, samples=0, faces=None, misc=None, batch_size=16, distance='chamfer', points=0):
+def evaluate_generation(model, reference_vertices, count, seed=0, samples=0, faces=None, misc=None, batch_size=16, distance='chamfer', points=0, jsd=0):
     """dict(mmd=, cov=, one_nna=) of Python floats (metrics.generation_metrics): `count` shapes drawn from the model (sample_prior with
     `seed` and `misc`, generate_vertices) against the reference shapes reference_vertices (R, V, 3).  The point sets are the vertices,
     or with samples = S > 0 metrics' convention for surface samples: sampling.sample_points of both sets of surfaces over `faces`
@@ -84,13 +84,18 @@ def evaluate_generation(model, reference_vertices, count, seed=0, samples=0, fac
     generator seeded with `seed` -- every generated surface takes the first S, every reference surface the second: the same samples on
     every device.  distance: 'chamfer' (default) or 'emd', as in metrics.generation_metrics.  points = P > 0 thins every point set to
     its P farthest points (sampling.farthest_points) after the optional surface sampling, so samples=S, points=P is "S surface samples
-    thinned to P", as in metrics.generation_metrics; points=0 (default) keeps them whole."""
+    thinned to P", as in metrics.generation_metrics; points=0 (default) keeps them whole.  jsd = R > 0 adds the key 'jsd', the
+    Jensen-Shannon divergence of the occupancy distributions of the two sets on a lattice of R lattice points an axis over (-1, 1)
+    (metrics.jensen_shannon_divergence; 28 in the shape-generation tables, at most 32), on exactly the point sets the matrices see --
+    after samples= and points=; the lattice is the whole cube, not the lattice points inside the inscribed sphere that some code
+    bases keep.  jsd=0 (default) returns the three keys alone."""
     who = 'evaluate_generation'
     if distance not in metrics.GENERATION_DISTANCES:
         raise ValueError('%s: distance must be one of %s, got %r' % (who, metrics.GENERATION_DISTANCES, distance))
     if isinstance(samples, bool) or not isinstance(samples, int) or samples < 0:
         raise ValueError('%s: samples must be a non-negative integer, got %r' % (who, samples))
     metrics._check_subset_size(who, points)
+    metrics._check_jsd_resolution(who, jsd)
     if not torch.is_tensor(reference_vertices) or reference_vertices.dim() != 3 or reference_vertices.shape[-1] != 3:
         raise ValueError('%s: expected reference_vertices (R, V, 3), got %s'
                          % (who, tuple(reference_vertices.shape) if torch.is_tensor(reference_vertices) else type(reference_vertices).__name__))
@@ -104,4 +109,4 @@ def evaluate_generation(model, reference_vertices, count, seed=0, samples=0, fac
         with torch.no_grad():
             generated = sample_points(generated, faces, uniforms=u[0].expand(generated.shape[0], -1, -1))[0]
             reference = sample_points(reference, faces, uniforms=u[1].expand(reference.shape[0], -1, -1))[0]
-    return metrics.generation_metrics(generated, reference, distance, points)
+    return metrics.generation_metrics(generated, reference, distance, points, jsd)

@@ -110,6 +110,14 @@ pair's, and earth_movers_distance is differentiable in both sets at the matching
 
 generation_metrics, evaluate_distance and generation.evaluate_generation take points = P to run on P well-spread points of every cloud
 instead of the whole cloud: sampling.farthest_points (icn_farthest_points, include/icn_fps.h), the protocol those tables come from.
+
+occupancy_counts, occupancy_jsd and jensen_shannon_divergence (below) give those tables their first column, the JENSEN-SHANNON
+DIVERGENCE of the occupancy distributions of two sets: every point of every cloud of a set dropped into a lattice (28^3 in the papers),
+the two normalised histograms compared -- the one figure of the four that is a property of the whole set, and the one that sees a
+generator put mass where the data has none (icn_point_occupancy and icn_occupancy_jsd, include/icn_occupancy.h: every workgroup a
+private histogram in LDS filled by integer LDS atomics, no global atomics; the divergence in double in a fixed order).  Integer counts
+are order-free, so the HIP path reproduces the torch restatement on CPU tensors bit for bit in the counts.  generation_metrics and
+generation.evaluate_generation take jsd = R to add it.
 """
 import torch
 
@@ -2449,6 +2457,200 @@ def earth_movers_distance(p1, p2, phases=6):
     return torch.where(torch.isnan(cost), cost, value).to(p1.dtype)
 
 
+# ---- occupancy histograms of point sets on a lattice, and their Jensen-Shannon divergence ------------------------------------------------
+_OCCUPANCY_MAX_R = 32              # lattice points per axis at most: the 32^3 cells of a workgroup's histogram fill 128 KiB of LDS
+_OCCUPANCY_BOUNDS = (-1.0, 1.0)    # the cube of the tanh head's range: the default lattice needs no read-back of the data
+
+
+def _fp32(value):
+    """The fp32 number nearest to the Python number `value`, as a Python float (inf where it overflows; no warning)."""
+    return torch.tensor(float(value), dtype=torch.float64).to(torch.float32).item()
+
+
+def _check_lattice(who, resolution, bounds, name='resolution'):
+    """The checks of a lattice -> (lo, inv_spacing), the two fp32 numbers of include/icn_occupancy.h as Python floats.  ValueError."""
+    if isinstance(resolution, bool) or not isinstance(resolution, int) or not 1 <= resolution <= _OCCUPANCY_MAX_R:
+        raise ValueError('%s: %s must be an integer in [1, %d], got %r' % (who, name, _OCCUPANCY_MAX_R, resolution))
+    if not isinstance(bounds, (tuple, list)) or len(bounds) != 2 \
+            or any(isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float('inf'), -float('inf')) for v in bounds) \
+            or not bounds[0] < bounds[1]:
+        raise ValueError('%s: bounds must be two finite numbers (lo, hi) with lo < hi, got %r' % (who, bounds))
+    lo = _fp32(bounds[0])
+    inv_spacing = _fp32((resolution - 1) / (float(bounds[1]) - float(bounds[0]))) if resolution > 1 else 1.0
+    if lo in (float('inf'), -float('inf')) or inv_spacing == float('inf') or not inv_spacing > 0.0:
+        raise ValueError('%s: bounds %r give no fp32 lattice of %d points an axis' % (who, bounds, resolution))
+    return lo, inv_spacing
+
+
+def _check_clouds(who, clouds):
+    """The shape checks of one set of clouds.  ValueError."""
+    if not torch.is_tensor(clouds) or not clouds.is_floating_point() or clouds.dim() != 3 or clouds.shape[-1] != 3 or clouds.shape[0] < 1 \
+            or clouds.shape[1] < 1:
+        raise ValueError('%s: expected the set as a floating-point (clouds, points, 3) tensor with clouds, points >= 1, got %s'
+                         % (who, tuple(clouds.shape) if torch.is_tensor(clouds) else type(clouds).__name__))
+    if clouds.shape[0] * clouds.shape[1] > 0x7fffffff:
+        raise ValueError('%s: %d clouds of %d points: B N must fit an int32' % (who, clouds.shape[0], clouds.shape[1]))
+
+
+def _torch_occupancy_counts(clouds, resolution, lo, inv_spacing, per_cloud=False):
+    """THE DEFINITION of occupancy_counts restated in torch (include/icn_occupancy.h, where it is written out), on any device ->
+    (counts int32 (R, R, R) or (B, R, R, R), dropped int32 () or (B,)).  fp32 whatever the dtype of `clouds` (they are converted first:
+    exact for the narrower types, to the nearest for float64), every operation a torch operation of its own in the header's order:
+    t = (x - lo) * inv_spacing, u = floor(t + 0.5), i = clamp(u, 0, R - 1), c = (ix R + iy) R + iz, then one bincount.  A point with a
+    non-finite coordinate is masked before the arithmetic (it runs on zeros and lands in a bin of its own that is cut off)."""
+    B, N, _ = clouds.shape
+    R = resolution
+    cells = R * R * R
+    with torch.no_grad():
+        p = clouds.detach().to(torch.float32)
+        dev = p.device
+        finite = torch.isfinite(p).all(-1)                                                 # (B, N)
+        p = torch.where(finite[..., None], p, torch.zeros_like(p))
+        t = (p - torch.tensor(lo, dtype=torch.float32, device=dev)) * torch.tensor(inv_spacing, dtype=torch.float32, device=dev)
+        u = torch.floor(t + torch.tensor(0.5, dtype=torch.float32, device=dev))
+        i = u.clamp(0.0, float(R - 1)).to(torch.int64)
+        c = (i[..., 0] * R + i[..., 1]) * R + i[..., 2]
+        rows = B if per_cloud else 1
+        if per_cloud:
+            c = c + cells * torch.arange(B, device=dev)[:, None]
+        c = torch.where(finite, c, torch.full_like(c, rows * cells))
+        counts = torch.bincount(c.reshape(-1), minlength=rows * cells + 1)[:rows * cells].to(torch.int32)
+        dropped = (~finite).sum(-1) if per_cloud else (~finite).sum()
+    return counts.reshape((B, R, R, R) if per_cloud else (R, R, R)), dropped.to(torch.int32)
+
+
+def _hip_occupancy_counts(pts, resolution, lo, inv_spacing, per_cloud):
+    """icn_point_occupancy on a contiguous fp32 ROCm tensor -> (counts, dropped) int32."""
+    B, N, _ = pts.shape
+    R = resolution
+    L = _lib.api()
+    if per_cloud:
+        counts = torch.empty(B, R, R, R, dtype=torch.int32, device=pts.device)
+        dropped = torch.empty(B, dtype=torch.int32, device=pts.device)
+        with torch.cuda.device(pts.device):
+            for b0, nb in _batch_slices(B):                                  # (the workspace is asked per slice: fewer clouds may take more pieces)
+                ws_bytes = L.icn_point_occupancy_workspace_bytes(nb, N, R, 1)
+                ws = _lib.workspace(ws_bytes, pts.device)
+                L.icn_point_occupancy(pts[b0:].data_ptr(), nb, N, R, lo, inv_spacing, 1, counts[b0:].data_ptr(), dropped[b0:].data_ptr(),
+                                      ws.data_ptr(), ws_bytes, _lib.stream())
+        return counts, dropped
+    if B > _MAX_GRID_Y:                                                      # the set's histogram does not see where a cloud ends
+        B, N = 1, B * N
+    counts = torch.empty(R, R, R, dtype=torch.int32, device=pts.device)
+    dropped = torch.empty((), dtype=torch.int32, device=pts.device)
+    ws_bytes = L.icn_point_occupancy_workspace_bytes(B, N, R, 0)
+    ws = _lib.workspace(ws_bytes, pts.device)
+    with torch.cuda.device(pts.device):
+        L.icn_point_occupancy(pts.data_ptr(), B, N, R, lo, inv_spacing, 0, counts.data_ptr(), dropped.data_ptr(), ws.data_ptr(), ws_bytes,
+                              _lib.stream())
+    return counts, dropped
+
+
+def _occupancy_counts_unchecked(clouds, resolution, lo, inv_spacing, per_cloud=False):
+    """occupancy_counts after its checks; no host synchronisation on the HIP path."""
+    if _on_hip_path(clouds):
+        return _hip_occupancy_counts(clouds.detach().contiguous(), resolution, lo, inv_spacing, per_cloud)
+    return _torch_occupancy_counts(clouds, resolution, lo, inv_spacing, per_cloud)
+
+
+def occupancy_counts(clouds, resolution=28, bounds=_OCCUPANCY_BOUNDS, per_cloud=False):
+    """(counts, dropped) int32: the occupancy histogram of a SET of clouds (B, N, 3) on a lattice of R = `resolution` lattice points an
+    axis from bounds[0] to bounds[1] on every axis -- counts (R, R, R), the number of points of the whole set nearest to each lattice
+    point, and dropped (), the number of points with a non-finite coordinate, which are counted in no cell.  per_cloud=True gives one
+    histogram a cloud: counts (B, R, R, R), dropped (B,).  No gradient.
+
+    One definition for the HIP kernel (include/icn_occupancy.h), the torch restatement (_torch_occupancy_counts) and the tests, in
+    fp32 with every operation rounded on its own: with lo = float32(bounds[0]) and inv_spacing = float32((R - 1) / (hi - lo)) (1.0 for
+    R = 1), computed here so that both routes use the same bits,
+        t = (x - lo) * inv_spacing,  u = floor(t + 0.5),  i = clamp(u, 0, R - 1)  per axis;   cell (ix, iy, iz)
+    -- the nearest lattice point, a tie goes up, anything outside the cube is clamped onto the boundary lattice point (a t that
+    overflows included).  Integer counts are order-free, so the result is fixed bit for bit: row b of a per-cloud call equals the
+    call on that cloud alone, the set histogram equals the sum of the rows, counts.sum() + dropped.sum() == B N.
+    The default bounds (-1, 1) are the cube of the tanh head's range, so nothing is read back to place the lattice; (-0.5, 0.5) is the
+    literature's unit cube.  The lattice is the whole cube: the variant of some code bases that keeps only the lattice points inside
+    the inscribed sphere is not offered.
+    ROCm fp32 tensors run on icn_point_occupancy: every workgroup a private histogram of R^3 words in LDS, integer LDS atomics, one
+    workgroup per 16 384 points up to one a CU and a second launch that adds their histograms; no global atomics.  CPU tensors, other
+    dtypes (converted to fp32 first) and ICN_NO_HIP_LOSS=1 take the restatement.  Arguments are checked (ValueError): resolution an
+    integer in [1, 32], bounds two finite Python numbers lo < hi, B N <= 2^31 - 1."""
+    _check_clouds('occupancy_counts', clouds)
+    lo, inv_spacing = _check_lattice('occupancy_counts', resolution, bounds)
+    return _occupancy_counts_unchecked(clouds, resolution, lo, inv_spacing, bool(per_cloud))
+
+
+def _torch_occupancy_jsd(counts_a, counts_b):
+    """THE DEFINITION of occupancy_jsd restated in torch (include/icn_occupancy.h), in float64 on any device -> 0-dim float64.  The
+    totals are integer sums; p = a / A, q = b / B, m = 0.5 (p + q), s = 0.5 (p log2(p / m) + q log2(q / m)) with a term of an empty
+    cell exactly 0, summed by torch (the header's order is the kernel's: the two agree within 2^-44); NaN if a histogram is empty."""
+    a, b = counts_a.reshape(-1).to(torch.int64), counts_b.reshape(-1).to(torch.int64)
+    A, B = a.sum(), b.sum()
+    p, q = a.double() / A.double(), b.double() / B.double()
+    m = 0.5 * (p + q)
+    one, zero = torch.ones_like(p), torch.zeros_like(p)
+    tp = torch.where(a > 0, p * torch.log2(torch.where(a > 0, p / m, one)), zero)
+    tq = torch.where(b > 0, q * torch.log2(torch.where(b > 0, q / m, one)), zero)
+    jsd = (0.5 * (tp + tq)).sum()
+    return torch.where((A == 0) | (B == 0), torch.full_like(jsd, float('nan')), jsd)
+
+
+def _occupancy_jsd_unchecked(counts_a, counts_b):
+    """occupancy_jsd after its checks; no host synchronisation."""
+    from . import losses
+    if not losses._NO_HIP_LOSS and counts_a.is_cuda and counts_a.dtype == torch.int32 and counts_b.dtype == torch.int32:
+        a, b = counts_a.contiguous(), counts_b.contiguous()
+        jsd = torch.empty((), dtype=torch.float64, device=a.device)
+        with torch.cuda.device(a.device):
+            _lib.api().icn_occupancy_jsd(a.data_ptr(), b.data_ptr(), a.shape[0], jsd.data_ptr(), _lib.stream())
+        return jsd
+    return _torch_occupancy_jsd(counts_a, counts_b)
+
+
+def occupancy_jsd(counts_a, counts_b):
+    """0-dim float64: the Jensen-Shannon divergence, base 2, of two occupancy histograms (R, R, R) of non-negative integers, as
+    occupancy_counts gives them -- for callers who keep histograms.  All in double (include/icn_occupancy.h): with the totals A and B
+    as integers, p = a / A, q = b / B, m = 0.5 (p + q), jsd = sum over the cells of 0.5 (p log2(p / m) + q log2(q / m)), a term of an
+    empty cell 0; in [0, 1]; NaN if either histogram is empty.  Identical histograms give exactly 0.0 and swapping the two gives the
+    same bits.  ROCm int32 tensors run on icn_occupancy_jsd (one workgroup, a fixed order: bit-identical run to run), anything else
+    on the restatement _torch_occupancy_jsd; the two agree within 2^-44.  Shapes are checked (ValueError); nothing is read back."""
+    for name, x in (('the first', counts_a), ('the second', counts_b)):
+        if not torch.is_tensor(x) or x.is_floating_point() or x.is_complex() or x.dtype == torch.bool or x.dim() != 3 \
+                or not 1 <= x.shape[0] <= _OCCUPANCY_MAX_R or x.shape != (x.shape[0],) * 3:
+            raise ValueError('occupancy_jsd: expected %s histogram as an integer (R, R, R) tensor with 1 <= R <= %d, got %s'
+                             % (name, _OCCUPANCY_MAX_R, '%s %s' % (x.dtype, tuple(x.shape)) if torch.is_tensor(x) else type(x).__name__))
+    if counts_a.shape != counts_b.shape or counts_a.device != counts_b.device:
+        raise ValueError('occupancy_jsd: the histograms must have one shape and one device, got %s on %s and %s on %s'
+                         % (tuple(counts_a.shape), counts_a.device, tuple(counts_b.shape), counts_b.device))
+    return _occupancy_jsd_unchecked(counts_a, counts_b)
+
+
+def jensen_shannon_divergence(generated, reference, resolution=28, bounds=_OCCUPANCY_BOUNDS):
+    """0-dim float64: the Jensen-Shannon divergence (base 2, in [0, 1]) between the occupancy distributions of a set of generated
+    clouds (G, N, 3) and a set of reference clouds (R, M, 3) -- the JSD column of the shape-generation tables (Achlioptas et al. 2018):
+    occupancy_jsd of the two occupancy_counts(., resolution, bounds), which see each set as one heap of points, so the sets need
+    neither one size nor one point count.  0 for two sets that fill the lattice alike, 1 for two sets that share no cell.  The
+    papers use resolution 28 on the unit cube, bounds=(-0.5, 0.5), of shapes normalised into it; the default bounds (-1, 1) are the
+    cube of the tanh head's range.  The lattice is the whole cube: the variant that keeps only the lattice points inside the
+    inscribed sphere is not offered.  NaN if every point of a set is non-finite.  No gradient; nothing is read back."""
+    generated, reference = _check_cloud_sets('jensen_shannon_divergence', generated, reference)
+    for x in (generated, reference):
+        _check_clouds('jensen_shannon_divergence', x)
+    lo, inv_spacing = _check_lattice('jensen_shannon_divergence', resolution, bounds)
+    return _jsd_unchecked(generated, reference, resolution, lo, inv_spacing)
+
+
+def _jsd_unchecked(generated, reference, resolution, lo, inv_spacing):
+    """jensen_shannon_divergence after its checks."""
+    a, b = (_occupancy_counts_unchecked(x, resolution, lo, inv_spacing)[0] for x in (generated, reference))
+    return _occupancy_jsd_unchecked(a, b)
+
+
+def _check_jsd_resolution(who, jsd):
+    """The check of the `jsd=` option -> jsd.  ValueError."""
+    if isinstance(jsd, bool) or not isinstance(jsd, int) or not 0 <= jsd <= _OCCUPANCY_MAX_R:
+        raise ValueError('%s: jsd must be an integer in [0, %d], the lattice points an axis (0: no JSD), got %r' % (who, _OCCUPANCY_MAX_R, jsd))
+    return jsd
+
+
 GENERATION_DISTANCES = ('chamfer', 'emd')
 
 
@@ -2469,28 +2671,36 @@ def _farthest_subsets(who, clouds, points):
         return farthest_points(clouds.detach(), points)
 
 
-def generation_metrics(generated, reference, distance='chamfer', points=0):
+def generation_metrics(generated, reference, distance='chamfer', points=0, jsd=0):
     """dict(mmd=, cov=, one_nna=) of Python floats for a set of generated clouds (G, N, 3) against a set of reference clouds (R, M, 3):
     minimum_matching_distance and coverage of pairwise_chamfer(generated, reference), one_nn_accuracy with the two within-set matrices
     as well.  Three pairwise_chamfer calls (squared distances, unit weights) and one read-back at the end.
     distance='emd' takes the three matrices from pairwise_emd instead (MMD-EMD, COV-EMD, 1-NNA-EMD; M == N then).
     points = P > 0 replaces both sets by sampling.farthest_points(., P) first -- the protocol of the shape-generation tables, P
     well-spread points a shape (2 048 there), which is what makes the EMD matrices affordable; P larger than a cloud raises
-    ValueError.  points=0 (default) matches whole clouds."""
+    ValueError.  points=0 (default) matches whole clouds.
+    jsd = R > 0 adds the key 'jsd', the first column of those tables: jensen_shannon_divergence of the two sets on a lattice of R
+    lattice points an axis (28 there; at most 32) over the default bounds (-1, 1), on exactly the point sets the matrices see (after
+    points=), in the same read-back.  The lattice is the whole cube; the variant that keeps only the lattice points inside the
+    inscribed sphere is not offered.  jsd=0 (default) returns the three keys alone."""
     if distance not in GENERATION_DISTANCES:
         raise ValueError('generation_metrics: distance must be one of %s, got %r' % (GENERATION_DISTANCES, distance))
     _check_subset_size('generation_metrics', points)
+    _check_jsd_resolution('generation_metrics', jsd)
     generated, reference = _check_cloud_sets('generation_metrics', generated, reference)
     if points:
         generated, reference = (_farthest_subsets('generation_metrics', x, points) for x in (generated, reference))
     if distance == 'emd':
         d_gr, d_gg, d_rr = pairwise_emd(generated, reference), pairwise_emd(generated, generated), pairwise_emd(reference, reference)
-        mmd, cov, nna = torch.stack([minimum_matching_distance(d_gr), coverage(d_gr), one_nn_accuracy(d_gg, d_gr, d_rr)]).tolist()
-        return dict(mmd=mmd, cov=cov, one_nna=nna)
-    d_gr = pairwise_chamfer(generated, reference)
-    d_gg, d_rr = pairwise_chamfer(generated, generated), pairwise_chamfer(reference, reference)
-    mmd, cov, nna = torch.stack([minimum_matching_distance(d_gr).double(), coverage(d_gr), one_nn_accuracy(d_gg, d_gr, d_rr)]).tolist()
-    return dict(mmd=mmd, cov=cov, one_nna=nna)
+        figures = [minimum_matching_distance(d_gr), coverage(d_gr), one_nn_accuracy(d_gg, d_gr, d_rr)]
+    else:
+        d_gr = pairwise_chamfer(generated, reference)
+        d_gg, d_rr = pairwise_chamfer(generated, generated), pairwise_chamfer(reference, reference)
+        figures = [minimum_matching_distance(d_gr).double(), coverage(d_gr), one_nn_accuracy(d_gg, d_gr, d_rr)]
+    if jsd:
+        _check_clouds('generation_metrics', generated), _check_clouds('generation_metrics', reference)
+        figures.append(_jsd_unchecked(generated, reference, jsd, *_check_lattice('generation_metrics', jsd, _OCCUPANCY_BOUNDS, 'jsd')))
+    return dict(zip(('mmd', 'cov', 'one_nna', 'jsd'), torch.stack(figures).tolist()))
 
 
 def output2vertices(subdivisions, output):
